@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- spectra/s of the fused IQ -> power-spectrum hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, settles, times K steps and prints the result line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the `roofline` priced from the timed launches themselves.
+--dump-outputs DIR writes the rows the last timed step computed to DIR/<workload>.npy (float32, or float64 for
+f64 rows and int32 block sums; every row when they fit in DUMP_BYTES, else a fixed seeded sample of rows,
+dump_row_indices()).  The inputs come from fixed seeds: the same arguments give the same inputs in every run.
+--full adds everything else the line carries (below): the parity spot check against the f64 oracle, the
+energy / clock leg behind the timed region, `roofline.box`, `cpu_baseline` and `extra_workloads`.
 
 A "step" is one pass of the hot path over one batch: ONE launch of the fused
 kernel over 65 536 frames of 1024 cmplx_u8 (BASELINE.json configs[1]: 128 MiB
@@ -25,7 +33,8 @@ before anything touches a GPU -- relays rank 0's JSON line and exits with the
 child's code; under torch.distributed.run it is a rank.
 
 One JSON line on stdout (rank 0).  `roofline` prices the kernel against HBM
-using the ALGORITHMIC bytes (2*N*R in + 4*N/K out per frame, SURVEY.md §8d);
+using the ALGORITHMIC bytes (2*N*R in + 4*N/K out per frame).
+With --full: `parity` checks 256 rows of what was timed against the f64 oracle;
 `cpu_baseline` times the f64 oracle (oracle/, kind "port") on this host's
 cores -- one thread, the job's CPU quota and the whole affinity mask; `value` is
 the fastest of them, `cores` the thread count that produced it -- on a bounded
@@ -371,6 +380,31 @@ def energy_counter_for(rtlws, device_index):
 
 ENERGY_LAUNCHES = 600          # launches of the leg behind the timed region (energy accumulator, clock stamps)
 CLOCK_SLOTS = 2048             # one-wavefront workgroups of a stamp launch: two per SIMD of an MI355X
+DUMP_BYTES = 32 << 20          # --dump-outputs: at most this many bytes of rows
+DUMP_SEED = 20240607           # ... and the seed of the row sample when the rows do not fit
+
+
+def dump_dtype(np, out_dtype):
+    """float64 for f64 rows and int32 block sums (exact), float32 for f32 rows and payload bytes."""
+    return np.float64 if np.dtype(out_dtype).itemsize == 8 or np.dtype(out_dtype).kind == "i" else np.float32
+
+
+def dump_row_indices(np, rows, cols, itemsize):
+    """The rows --dump-outputs writes: all of them when rows x cols x itemsize fits in DUMP_BYTES, else a fixed
+    seeded sample of as many as fit, ascending."""
+    fit = max(1, DUMP_BYTES // (cols * itemsize))
+    if rows <= fit:
+        return np.arange(rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=fit, replace=False))
+
+
+def dump_rows(torch, np, out):
+    """The rows of `out` (a device tensor, rows x cols) that --dump-outputs writes, on the host, as float32 /
+    float64."""
+    dt = dump_dtype(np, str(out.dtype).replace("torch.", ""))
+    idx = dump_row_indices(np, out.shape[0], out.shape[1], np.dtype(dt).itemsize)
+    sel = out.index_select(0, torch.from_numpy(idx).to(out.device))
+    return sel.cpu().numpy().astype(dt)
 
 
 def run_workload(ctx, name, steps, warmup, sets, frames_override=0, cpu_baseline=False, cpu_budget_scale=1.0):
@@ -464,6 +498,9 @@ def run_workload(ctx, name, steps, warmup, sets, frames_override=0, cpu_baseline
     ev_ms = L.rtlws_event_elapsed_ms(ev0, ev1)
     L.rtlws_event_destroy(ev0)
     L.rtlws_event_destroy(ev1)
+    # --dump-outputs: the rows of the last timed step, taken before anything else launches into its buffers
+    if ctx.get("dump") and rank == 0:
+        ctx.setdefault("dumped", {})[name] = dump_rows(torch, np, outs[(steps - 1) % sets])
     # The leg behind the timed region (after the clock has stopped, outside `value`): ENERGY_LAUNCHES more launches
     # of the same step, in the same steady state, with
     #  * the package energy accumulator of this device read before and after (one-GPU jobs) -- joules per launch and
@@ -600,17 +637,19 @@ def run_workload(ctx, name, steps, warmup, sets, frames_override=0, cpu_baseline
                                   "note": "own = each rank's wall clock around its launches + synchronise, before "
                                           "the closing barrier; ms_per_step is the MAX over ranks incl. the barrier"}
 
-        # parity spot check of what was just timed (first 256 rows of set 0)
-        from oracle import pyoracle as po
-        nchk = 256 * k_avg
-        host_in = ins[0][:nchk].cpu().numpy()
-        got = outs[0][:nchk if cic_only else 256].cpu().numpy()
-        result["parity"] = parity_block(np, po, wl, host_in, got, nchk, f64)
-        bad = parity_failures(result["parity"], parity_bounds_for(name))
-        if bad:
-            result["parity"]["failed"] = bad
+        # parity spot check of what was just timed (first 256 rows of set 0; --full)
+        if ctx.get("parity", True):
+            from oracle import pyoracle as po
+            nchk = 256 * k_avg
+            host_in = ins[0][:nchk].cpu().numpy()
+            got = outs[0][:nchk if cic_only else 256].cpu().numpy()
+            result["parity"] = parity_block(np, po, wl, host_in, got, nchk, f64)
+            bad = parity_failures(result["parity"], parity_bounds_for(name))
+            if bad:
+                result["parity"]["failed"] = bad
 
         if cpu_baseline:
+            from oracle import pyoracle as po
             # the CPU path is the f64 oracle whatever the GPU rows are: one timing per configuration and run
             key = (n_fft, k_avg, window, output, cic_r, frames)
             cache = ctx.setdefault("cpu_baseline_cache", {})
@@ -1033,8 +1072,7 @@ def box_calibration(rtlws, device_index, ec, settle_s=0.15, measure_s=0.25):
     return box
 
 
-def main(argv=None):
-    argv = sys.argv[1:] if argv is None else list(argv)
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
@@ -1054,7 +1092,21 @@ def main(argv=None):
     ap.add_argument("--no-clock-probe", action="store_true",
                     help="no clock stamps around the leg behind the timed region (with --no-energy: no such leg at all)")
     ap.add_argument("--plumbing-cpu", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the f64 oracle, the energy / clock leg behind the timed region, "
+                         "roofline.box, cpu_baseline and extra_workloads (the --no-* options leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows the last timed step computed to DIR/<workload>.npy (float32 / float64; a "
+                         "fixed seeded sample of rows when they exceed %d MiB)" % (DUMP_BYTES >> 20))
+    return ap
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    ap = parser()
     args = ap.parse_args(argv)
+    if args.dump_outputs is not None and args.workload in (REALTIME_WORKLOAD, MULTI_BATCH_WORKLOAD):
+        ap.error("--dump-outputs: the C drivers of --workload %s keep their rows" % args.workload)
 
     if args.workload == REALTIME_WORKLOAD:          # one process drives every device (threads, no ranks)
         return realtime_main(args)
@@ -1084,15 +1136,17 @@ def main(argv=None):
     rank_topology = pin_rank_to_its_gpu(rtlws, local_rank, planned_topology(rtlws, local_rank)) if world > 1 else None
 
     eng = rtlws.Engine(local_rank)
+    full = args.full
     ctx = {"torch": torch, "np": np, "rtlws": rtlws, "eng": eng, "dist": dist, "world": world,
            "rank": rank, "device": device,
            # ONE side stream carries input synthesis and every launch (run_workload, "Stream order")
-           "input": args.input, "clock_probe": not args.no_clock_probe, "energy": not args.no_energy,
+           "input": args.input, "clock_probe": full and not args.no_clock_probe, "energy": full and not args.no_energy,
+           "parity": full, "dump": args.dump_outputs is not None,
            "stream": torch.cuda.Stream(device=device),
            "cu_count": torch.cuda.get_device_properties(device).multi_processor_count,
            "local_rank": local_rank, "rank_topology": rank_topology,
            # the package energy accumulator of THIS device, by PCI bus id (one-GPU jobs)
-           "energy_counter": energy_counter_for(rtlws, local_rank) if (world == 1 and not args.no_energy) else None}
+           "energy_counter": energy_counter_for(rtlws, local_rank) if (full and world == 1 and not args.no_energy) else None}
 
     # First collective = RCCL's lazy communicator set-up (~16 ms): do it here, not
     # between the warm-up launches and the timed region, where that much idle
@@ -1102,11 +1156,15 @@ def main(argv=None):
         torch.cuda.synchronize()
 
     result = run_workload(ctx, args.workload, args.steps, args.warmup, args.sets, args.frames,
-                          cpu_baseline=(world == 1 and not args.no_cpu_baseline))
+                          cpu_baseline=(full and world == 1 and not args.no_cpu_baseline))
+    if rank == 0 and args.dump_outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, rows in ctx.pop("dumped").items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), rows)
 
     # what this chip gives a fixed instruction stream at the cap (roofline.box): right behind the headline's energy
     # leg, the package still at its cap
-    if world == 1 and rank == 0 and not args.no_box and not args.no_energy and ctx["clock_probe"]:
+    if full and world == 1 and rank == 0 and not args.no_box and not args.no_energy and ctx["clock_probe"]:
         try:
             box = box_calibration(rtlws, local_rank, ctx["energy_counter"])
         except Exception as ex:            # an auxiliary measurement: the line goes out without it
@@ -1115,9 +1173,10 @@ def main(argv=None):
         if box is not None:
             result["roofline"]["box"] = box
 
-    # The default line also carries configs[2], configs[3] and the reference's own CIC
+    # The --full line also carries configs[2], configs[3] and the reference's own CIC
     # factor, measured the same way with fewer steps (rank 0 of a 1-GPU job only).
-    if world == 1 and args.workload == HEADLINE and not args.no_extra and args.frames == 0:
+    if full and world == 1 and args.workload == HEADLINE and not args.no_extra and args.frames == 0:
+        ctx["dump"] = False                     # --dump-outputs: the timed path's rows only
         extras = []
         for name in EXTRA_WORKLOADS:
             with_cpu = name in EXTRA_CPU_BASELINE and not args.no_cpu_baseline
@@ -1156,7 +1215,7 @@ def main(argv=None):
     if rank == 0:
         # A parity block that is non-finite or over its bound is a FAILED run: the line is still
         # printed (strict JSON: a non-finite number becomes a string), the exit code says so.
-        blocks = [(result["config"]["workload"], result["parity"])]
+        blocks = [(result["config"]["workload"], result["parity"])] if "parity" in result else []
         blocks += [(x["workload"], x["parity"]) for x in result.get("extra_workloads", [])]
         failed = {n: b["failed"] for n, b in blocks if b.get("failed")}
         if failed:

@@ -202,6 +202,31 @@ def test_parity_failures_and_strict_json():
     assert json.loads(line) == {"a": "nan", "b": [1.0, "inf"], "c": {"d": 2}}
 
 
+def test_plain_and_full_options_and_dumped_rows():
+    """A plain line measures only the headline; --full adds the rest.  --dump-outputs writes the rows of the last
+    step as float32 / float64: all of them when they fit in DUMP_BYTES, else the same seeded sample in every run."""
+    import torch
+    import bench
+    a = bench.parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    a = bench.parser().parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.main(["--workload", "multi_batch", "--dump-outputs", "out"])     # the C drivers keep their rows
+    for dt, want, shape in ((torch.float32, np.float32, (65536, 1024)), (torch.float64, np.float64, (600, 1024)),
+                            (torch.int32, np.float64, (100, 4096)), (torch.uint8, np.float32, (65532, 1024))):
+        t = (torch.arange(shape[0] * shape[1]) % 251).to(dt).reshape(shape)
+        rows = bench.dump_rows(torch, np, t)
+        idx = bench.dump_row_indices(np, shape[0], shape[1], np.dtype(want).itemsize)
+        assert rows.dtype == want and rows.nbytes <= bench.DUMP_BYTES
+        assert np.array_equal(rows, t.numpy()[idx].astype(want))
+        assert np.all(np.diff(idx) > 0) and idx[-1] < shape[0]
+        if t.numel() * np.dtype(want).itemsize <= bench.DUMP_BYTES:
+            assert idx.size == shape[0]
+        else:
+            assert np.array_equal(idx, bench.dump_row_indices(np, shape[0], shape[1], np.dtype(want).itemsize))
+
+
 def test_valu_issue_frac_arithmetic(tmp_path, monkeypatch):
     import json
     import bench

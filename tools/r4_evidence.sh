@@ -4,9 +4,10 @@
 # drop-in latencies with and without the fused f64 kernel, the power / clock probe of the new kernels.
 TAG=r04
 mkdir -p gpurun_out
-python3 bench.py > gpurun_out/${TAG}_bench_default_line.json 2> gpurun_out/${TAG}_bench_default_line.err
+export BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"      # bench.py --full lines
+python3 bench.py --full > $BENCH_OUT/${TAG}_bench_default_line.json 2> $BENCH_OUT/${TAG}_bench_default_line.err
 echo "default line rc=$?"
-python3 bench.py --steps 20 > gpurun_out/${TAG}_bench_default_line_steps20.json 2>> gpurun_out/${TAG}_bench_default_line.err
+python3 bench.py --full --steps 20 > $BENCH_OUT/${TAG}_bench_default_line_steps20.json 2>> $BENCH_OUT/${TAG}_bench_default_line.err
 echo "steps20 line rc=$?"
 for wl in batched_1024pt_64k_frames batched_1024pt_64k_frames_f64c_f32o batched_1024pt_64k_frames_f64 cic8_2048pt_f64 cic8_2048pt hann_4096pt_k8_db cic12_2048pt cic8_2048pt_f64c_f32o; do
   bash tools/profile_gpu.sh ${TAG}_$wl $wl > gpurun_out/prof_${TAG}_$wl.log 2>&1

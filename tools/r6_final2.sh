@@ -7,11 +7,12 @@ timeout -k 10 600 python3 -m pytest tests -x -q -m gpu > gpurun_out/r06_gpu_suit
 tail -5 gpurun_out/r06_gpu_suite.txt
 [ $rc -eq 0 ] || { grep -n "Error\|assert\|FAILED" gpurun_out/r06_gpu_suite.txt | head -30; exit $rc; }
 timeout -k 10 60 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-timeout -k 10 300 python3 bench.py > gpurun_out/r06_bench_default_line.json 2> gpurun_out/r06_bench_default_line.err || { tail -20 gpurun_out/r06_bench_default_line.err; exit 1; }
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > gpurun_out/r06_bench_default_line_steps20.json 2> gpurun_out/r06_bench_steps20.err || { tail -20 gpurun_out/r06_bench_steps20.err; exit 1; }
+export BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"      # bench.py --full lines
+timeout -k 10 300 python3 bench.py --full > $BENCH_OUT/r06_bench_default_line.json 2> $BENCH_OUT/r06_bench_default_line.err || { tail -20 $BENCH_OUT/r06_bench_default_line.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $BENCH_OUT/r06_bench_default_line_steps20.json 2> $BENCH_OUT/r06_bench_steps20.err || { tail -20 $BENCH_OUT/r06_bench_steps20.err; exit 1; }
 python3 - <<'PY'
-import json
-for f in ("gpurun_out/r06_bench_default_line.json", "gpurun_out/r06_bench_default_line_steps20.json"):
+import json, os
+for f in (os.path.join(os.environ["BENCH_OUT"], "r06_bench_default_line.json"), os.path.join(os.environ["BENCH_OUT"], "r06_bench_default_line_steps20.json")):
     d = json.loads(open(f).read().strip().splitlines()[-1])
     r = d["roofline"]
     print(f)

@@ -11,11 +11,12 @@ timeout -k 10 200 python3 bench.py --workload multi_batch --steps 500 > gpurun_o
 timeout -k 10 200 python3 bench.py --workload multi_batch --steps 500 --shards-per-device 2 >> gpurun_out/r06_multi_batch.jsonl 2>> gpurun_out/r06_multi_batch.err || echo "multi_batch 2 FAILED" >> $OUT
 timeout -k 10 200 python3 bench.py --workload realtime_8x2400k --steps 4000 > gpurun_out/r06_multi_stream.jsonl 2> gpurun_out/r06_multi_stream.err || echo "realtime FAILED" >> $OUT
 timeout -k 10 200 python3 tools/dropin_latency.py > gpurun_out/r06_dropin_latency.txt 2>&1 || echo "dropin latency FAILED" >> $OUT
-timeout -k 10 300 python3 bench.py --frames 1048576 --sets 2 --steps 200 --no-cpu-baseline --no-extra > gpurun_out/r06_bench_1Mi_frames.json 2> gpurun_out/r06_bench_1Mi.err || echo "1Mi FAILED" >> $OUT
-timeout -k 10 300 python3 bench.py --input uniform --no-cpu-baseline --no-extra > gpurun_out/r06_bench_uniform_input.json 2> gpurun_out/r06_bench_uniform.err || echo "uniform FAILED" >> $OUT
+export BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"      # bench.py --full lines
+timeout -k 10 300 python3 bench.py --full --frames 1048576 --sets 2 --steps 200 --no-cpu-baseline --no-extra > $BENCH_OUT/r06_bench_1Mi_frames.json 2> $BENCH_OUT/r06_bench_1Mi.err || echo "1Mi FAILED" >> $OUT
+timeout -k 10 300 python3 bench.py --full --input uniform --no-cpu-baseline --no-extra > $BENCH_OUT/r06_bench_uniform_input.json 2> $BENCH_OUT/r06_bench_uniform.err || echo "uniform FAILED" >> $OUT
 python3 - >> $OUT <<'PY'
-import json
-for f in ("gpurun_out/r06_bench_1Mi_frames.json", "gpurun_out/r06_bench_uniform_input.json"):
+import json, os
+for f in (os.path.join(os.environ["BENCH_OUT"], "r06_bench_1Mi_frames.json"), os.path.join(os.environ["BENCH_OUT"], "r06_bench_uniform_input.json")):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1]); r = d["roofline"]; e = r.get("energy") or {}
         print("%s: %.3g spectra/s, frac %.4f (%.1f us), %.1f mJ per launch, parity %s" % (f, d["value"], r["frac"], r["avg_launch_us"], e.get("mj_per_launch", 0), d["parity"]))
