@@ -97,7 +97,9 @@ int rtlws_engine_device(const rtlws_engine* e);
  * in f64 arithmetic, 0.54 against 0.65 in f32, profiles/r05_split_priority_queues.txt: the fork and the join are
  * cross-queue dependencies that cost more than the overlapped fill and drain phases win.  The overlap pays only
  * for INDEPENDENT batches on independent queues: rtlws_multi.h, shards per device.)
- * set: 0, -1 for an unknown name.  get: the value ("cu_count" is readable too), -2 if unknown.  An option must not be changed while another thread launches on the same engine
+ * The environment and set take a value alike: v2 < 0 is -1, any other v2 and every flag != 0 is 1, a count <= 0 is
+ * 0, f64_x_waves and cic_round outside the values listed are 0.
+ * set: 0, -1 for an unknown name.  get: the value as taken ("cu_count" is readable too), -2 if unknown.  An option must not be changed while another thread launches on the same engine
  * (the launch paths read the options without the engine's lock). */
 int rtlws_engine_set_option(rtlws_engine* e, const char* name, int value);
 int rtlws_engine_get_option(const rtlws_engine* e, const char* name);
@@ -301,24 +303,6 @@ int rtlws_fm_demod(rtlws_engine* e, const void* d_iq_cs32, long len, const float
  * gave that interval (take the median; 2 048 slots cover the 1 024 SIMDs of an MI355X).  Nothing is resident beside
  * the launches in between: bench.py's roofline.sclk_ghz uses this since round 6.  0 / -1 / -3. */
 int rtlws_clock_stamp(rtlws_engine* e, unsigned long long* d_out, int slots, void* stream);
-
-/* The earlier instrument, kept for kernels with registers to spare and for the record of what it costs
- * (profiles/r06_clock_probe_perturbation.txt: +1 .. 7 % on the launches it sits beside, +38 % on kernels that fill a
- * SIMD's registers -- one of their workgroups then cannot be resident -- because it IS resident, on a hardware queue
- * of its own):
- * rtlws_clock_probe_start puts ONE wavefront on a queue of its own beside whatever the caller
- * enqueues next; it records s_memtime (shader clocks) and s_memrealtime (100 MHz) when it starts and
- * again when told to leave (rtlws_clock_probe_signal: returns at once; rtlws_clock_probe_stop:
- * signals if that has not been done, then waits for the wavefront) or after ~10 s by itself, sleeping
- * in between.  *sclk_ghz = d(memtime) / d(memrealtime) x 100 MHz: the clock the package power governor
- * actually gave the kernels that ran in that interval (bench.py's roofline.valu_issue_frac uses
- * it); *seconds = the interval.  start: NULL on failure; stop: 0 / -1 / -3 (the handle is consumed). */
-void* rtlws_clock_probe_start(rtlws_engine* e);
-void rtlws_clock_probe_signal(void* probe);
-/* The same signal, given by the device: written when everything enqueued on `stream` so far has
- * completed (a stream write-value packet), so the host need not wait for the stream first.  0 / -1 / -3. */
-int rtlws_clock_probe_signal_on_stream(void* probe, void* stream);
-int rtlws_clock_probe_stop(void* probe, double* sclk_ghz, double* seconds);
 
 /* Device-to-device copy on `stream` (delay-line upkeep of chained kernels). */
 int rtlws_copy_d2d(rtlws_engine* e, void* dst_dev, const void* src_dev, size_t bytes, void* stream);

@@ -225,40 +225,11 @@ hipError_t launch_halfband(const float* d_x, float* d_y, long out_len, hipStream
     return hipGetLastError();
 }
 
-// ---- shader-clock probe (measurement infrastructure; include/rtlws_hip.h, rtlws_clock_probe_*) ----
-// ONE wavefront that sits beside the kernels being timed and reads the two hardware counters at its
-// start and when told to stop: s_memtime counts shader clocks, s_memrealtime a fixed 100 MHz
-// (MI355X_MICROARCH.md, DVFS): d(memtime) / d(memrealtime) x 100 MHz is the clock the chip actually
-// ran at over that interval -- the interval of the timed launches, not of another launch series.
-// It sleeps between polls (s_sleep: no issue slots, no memory traffic but one 4-byte read per ~0.5 us)
-// and ALWAYS terminates: on the stop flag, after max_ticks of the 100 MHz counter (a bound in TIME: a poll is a
-// sleep plus a system-scope load whose latency depends on what else runs), or after max_polls polls.
-__global__ __launch_bounds__(64) void clock_probe_kernel(const int* stop, unsigned long long* out,
-                                                         int max_polls, unsigned long long max_ticks)
-{
-    const unsigned long long c0 = clock64(), r0 = wall_clock64();
-    if (threadIdx.x == 0) {                 // tells the host it is resident: the caller's clock starts after this
-        __hip_atomic_store(&out[3], 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    int polls = 0;
-    while (polls < max_polls) {
-        __builtin_amdgcn_s_sleep(16);       // ~0.5 us between polls
-        ++polls;
-        if (__hip_atomic_load(stop, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM)) break;   // past every cache
-        if (wall_clock64() - r0 > max_ticks) break;
-    }
-    if (threadIdx.x == 0) {
-        out[0] = clock64() - c0;
-        out[1] = wall_clock64() - r0;
-        out[2] = (unsigned long long)polls;
-    }
-}
-
 // ---- shader-clock stamp (measurement infrastructure; include/rtlws_hip.h, rtlws_clock_stamp) ----
 // `slots` one-wavefront workgroups that each write the two hardware counters and WHERE they ran, and leave.  Two such
 // launches in one stream, around the launches being measured, bracket them with NOTHING resident beside them (the
-// probe above takes registers and a second hardware queue: round 6 measured what that costs the launches it sits
-// beside).  s_memtime is a counter of the place it is read at (two one-wavefront stamps on different CUs differ by
+// retired clock probe, a wavefront resident on a hardware queue of its own, slowed the launches it sat beside:
+// profiles/r06_clock_probe_perturbation.txt).  s_memtime is a counter of the place it is read at (two one-wavefront stamps on different CUs differ by
 // arbitrary offsets), so the host pairs the records of the two launches BY PLACE -- XCC, SE, SH, CU, SIMD -- and
 // takes d(memtime) / d(memrealtime) per place.
 __global__ __launch_bounds__(64) void clock_stamp_kernel(unsigned long long* out)
@@ -277,13 +248,6 @@ __global__ __launch_bounds__(64) void clock_stamp_kernel(unsigned long long* out
 hipError_t launch_clock_stamp(unsigned long long* d_out, int slots, hipStream_t st)
 {
     hipLaunchKernelGGL(clock_stamp_kernel, dim3(slots), dim3(64), 0, st, d_out);
-    return hipGetLastError();
-}
-
-hipError_t launch_clock_probe(const int* stop_flag, unsigned long long* out, int max_polls, hipStream_t st)
-{
-    // 10 s of the 100 MHz counter, whatever a poll costs
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, st, stop_flag, out, max_polls, 1000000000ull);
     return hipGetLastError();
 }
 

@@ -1,23 +1,28 @@
 // shim.hip -- the extern-"C" layer declared in include/rtlws_hip.h.
 //
 // Host C code (rtl-ws_amd/host/*.c) and the Python test/bench plumbing reach
-// the kernels only through these functions.  The twiddle tables are computed
-// here in f64 and rounded once to f32.
+// the kernels only through these functions.  The twiddle tables come from
+// twiddle_tables.cpp, uploaded once per engine and N.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <ctime>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rtlws_hip.h"
 #include "rtlws_internal.h"
+#include "twiddle_tables.h"
+
+using rtlws::is_fused_n;
 
 namespace {
 
@@ -47,272 +52,106 @@ void set_err(const char* what, hipError_t e)
         }                                                     \
     } while (0)
 
-struct Tables {
-    float2* tw1 = nullptr;          // fused: input scale 1 (real f32); direct: W_N^e
-    float2* tw1_128 = nullptr;      // fused: input scale 1/128 (u8, s32, CIC)
-    float2* tw2 = nullptr;          // fused: last-pass (c, s/c) pairs
-    float* hann = nullptr;
-    float2* hann_cs = nullptr;      // fused: [T] (0.5 cos, 0.5 sin)(2 pi t / N)
-    double2* tw64 = nullptr;        // f64 kernel: W_N^k, k < N
-    double* hann64 = nullptr;
-    double2* tw1_64 = nullptr;      // f64 fused kernel: [T][16] W_N^(t*rev16(s)) / 128
-    double2* tw1u_64 = nullptr;     //   ... unscaled (real f32 input)
-    double2* tw2_64 = nullptr;      //   [16][R3/2] last-pass (cos, sin/cos) pairs
-    double2* hann_cs64 = nullptr;   //   [T] (0.5 cos, 0.5 sin)(2 pi t / N)
-    double2* twxa_64 = nullptr;     // spectrum_f64_1024x.hip (N = 1024): [4][8] pass-A (cos, tan) pairs
-    double2* twxb_64 = nullptr;     //   [64][16] inner twiddles x lane constant / 128
+struct DevFree {
+    void operator()(void* p) const { (void)hipFree(p); }
 };
 
-constexpr double kTwoPi = 6.283185307179586476925286766559;
+// The device copies of one size's rtlws::HostTables (null where that table is empty); `mem` owns them.
+struct Tables {
+    float2 *tw1 = nullptr, *tw1_128 = nullptr, *tw2 = nullptr, *hann_cs = nullptr;
+    float* hann = nullptr;
+    double2 *tw64 = nullptr, *tw1_64 = nullptr, *tw1u_64 = nullptr, *tw2_64 = nullptr, *hann_cs64 = nullptr,
+            *twxa_64 = nullptr, *twxb_64 = nullptr;
+    double* hann64 = nullptr;
+    std::vector<std::unique_ptr<void, DevFree>> mem;
+};
 
-}  // namespace
+enum class Prec { F32, F64 };
 
 // Kernel-selection switches (experiments, A/B runs, tests).  Read from the environment ONCE, when
 // the engine is created, and changed afterwards only through rtlws_engine_set_option: nothing on a
 // launch path calls getenv (tests/test_abi_cpu.py checks the library's imports per function).
 struct EngineOpts {
-    int v2 = -1;                 // RTLWS_V2: -1 = default rule (K = 1 rows), 0 / 1 = never / always
-    int blocks_per_cu = 0;       // RTLWS_BLOCKS_PER_CU: > 0 overrides the f32 fused kernels' grid
-    int f64_fused = 1;           // RTLWS_F64_FUSED=0: f64 batches stay on the row-per-workgroup kernel
-    int f64_blocks_per_cu = 0;   // RTLWS_F64_BLOCKS_PER_CU
-    int f64_x1024 = 1;           // RTLWS_F64_X1024=0: rectangular 1024-point u8 frames stay on the two-transposition kernel
-    int f64_x_waves = 0;         // RTLWS_F64_X_WAVES: wavefronts per workgroup of that kernel: 0 = by batch size, 1, 8
-    bool f64_x_waves8_ok = true; // the device's LDS limit per workgroup holds the eight-wavefront form (136 KiB)
-    int cic_direct = 0;          // RTLWS_CIC_DIRECT=1: every R != 8 on per-lane direct loads
-    int cic_round = 0;           // RTLWS_CIC_ROUND=1|2|4: LDS staging depth where R fits it
+    int v2, blocks_per_cu, f64_fused, f64_blocks_per_cu, f64_x1024, f64_x_waves, cic_direct, cic_round;
 };
+
+int norm_tristate(int v) { return v < 0 ? -1 : v != 0; }
+int norm_flag(int v) { return v != 0; }
+int norm_count(int v) { return v > 0 ? v : 0; }
+int norm_waves(int v) { return v == 1 || v == 8 ? v : 0; }
+int norm_round(int v) { return v == 1 || v == 2 || v == 4 ? v : 0; }
+
+// include/rtlws_hip.h documents each; the environment and rtlws_engine_set_option both go through `norm`
+struct OptionDef {
+    const char* name;
+    const char* env;
+    int EngineOpts::*field;
+    int dflt;
+    int (*norm)(int);
+};
+const OptionDef kOptions[] = {
+    {"v2", "RTLWS_V2", &EngineOpts::v2, -1, norm_tristate},                     // -1: the default rule (use_v2)
+    {"blocks_per_cu", "RTLWS_BLOCKS_PER_CU", &EngineOpts::blocks_per_cu, 0, norm_count},
+    {"f64_fused", "RTLWS_F64_FUSED", &EngineOpts::f64_fused, 1, norm_flag},
+    {"f64_blocks_per_cu", "RTLWS_F64_BLOCKS_PER_CU", &EngineOpts::f64_blocks_per_cu, 0, norm_count},
+    {"f64_x1024", "RTLWS_F64_X1024", &EngineOpts::f64_x1024, 1, norm_flag},
+    {"f64_x_waves", "RTLWS_F64_X_WAVES", &EngineOpts::f64_x_waves, 0, norm_waves},   // 0: by batch size
+    {"cic_direct", "RTLWS_CIC_DIRECT", &EngineOpts::cic_direct, 0, norm_flag},
+    {"cic_round", "RTLWS_CIC_ROUND", &EngineOpts::cic_round, 0, norm_round},
+};
+
+const OptionDef* find_option(const char* name)
+{
+    for (const OptionDef& o : kOptions)
+        if (name && std::strcmp(o.name, name) == 0) return &o;
+    return nullptr;
+}
+
+}  // namespace
 
 struct rtlws_engine {
     int device = 0;
     int cu_count = 256;
     hipStream_t stream = nullptr;
     EngineOpts opt;
+    bool x_waves8_ok = true;     // the device's LDS limit per workgroup holds spectrum_f64_1024x.hip's eight-wavefront form (136 KiB)
     std::mutex mu;
-    std::map<int, Tables> tables;   // by n_fft (fused) or -n_fft (direct)
+    std::map<std::pair<Prec, int>, Tables> tables;   // by precision and n_fft
 };
 
 namespace {
 
-int rev16h(int s) { return 4 * (s & 3) + (s >> 2); }
-
-bool is_fused_n(int n) { return n == 1024 || n == 2048 || n == 4096; }
-
-// (cos, sin/cos) of -2*pi*num/den, the form the last pass multiplies by
-// (spectrum_fused.hip, "last pass"); cos = 0 is stored as 1e-20.
-float2 cos_tan_pair(long num, long den)
+template <typename D, typename H>
+bool upload(Tables& tb, const std::vector<H>& host, D** dev)
 {
-    num %= den;
-    double c, sn;
-    if (4 * num == den) { c = 0.0; sn = -1.0; }
-    else if (4 * num == 3 * den) { c = 0.0; sn = 1.0; }
-    else if (2 * num == den) { c = -1.0; sn = 0.0; }
-    else if (num == 0) { c = 1.0; sn = 0.0; }
-    else {
-        const double a = -kTwoPi * (double)num / (double)den;
-        c = std::cos(a);
-        sn = std::sin(a);
+    static_assert(sizeof(D) == sizeof(H), "host and device table layouts differ");
+    if (host.empty()) return true;
+    hipError_t err = hipMalloc(dev, host.size() * sizeof(H));
+    if (err == hipSuccess) {
+        tb.mem.emplace_back(*dev);
+        err = hipMemcpy(*dev, host.data(), host.size() * sizeof(H), hipMemcpyHostToDevice);
     }
-    if (c == 0.0) c = 1e-20;
-    return make_float2((float)c, (float)(sn / c));
-}
-
-template <typename V>
-bool upload_table(const std::vector<V>& host, V** dev)
-{
-    hipError_t err = hipMalloc(dev, host.size() * sizeof(V));
-    if (err == hipSuccess) err = hipMemcpy(*dev, host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice);
     if (err != hipSuccess) set_err("twiddle table upload", err);
     return err == hipSuccess;
 }
 
-void free_tables(Tables& tb)
-{
-    (void)hipFree(tb.tw1);
-    (void)hipFree(tb.tw1_128);
-    (void)hipFree(tb.tw2);
-    (void)hipFree(tb.hann);
-    (void)hipFree(tb.hann_cs);
-    (void)hipFree(tb.tw64);
-    (void)hipFree(tb.hann64);
-    (void)hipFree(tb.tw1_64);
-    (void)hipFree(tb.tw1u_64);
-    (void)hipFree(tb.tw2_64);
-    (void)hipFree(tb.hann_cs64);
-    (void)hipFree(tb.twxa_64);
-    (void)hipFree(tb.twxb_64);
-    tb = Tables();
-}
-
-// Build (once per engine and N) the per-thread twiddle tables of the fused
-// kernel: tw1[t][s] = scale * W_N^(t * rev16(s)) (s >= 1; the kernel scales slot
-// 0 itself), tw2[q2][.] = the R3/2 pairs of alpha = W_T^q2: for sub-size
-// L = 2, 4, .. R3 and p < max(1, L/4) the pair of alpha^(R3/L) * W_L^p.
-int get_tables(rtlws_engine* e, int n_fft, bool fused, Tables* out)
+// The tables of one precision and N, built and uploaded once per engine: nullptr on failure.
+const Tables* get_tables(rtlws_engine* e, Prec prec, int n_fft)
 {
     std::lock_guard<std::mutex> lk(e->mu);
-    const int key = fused ? n_fft : -n_fft;
+    const auto key = std::make_pair(prec, n_fft);
     auto it = e->tables.find(key);
-    if (it != e->tables.end()) { *out = it->second; return 0; }
+    if (it != e->tables.end()) return &it->second;
+    HIP_TRY(hipSetDevice(e->device), nullptr);
+    const rtlws::HostTables h = prec == Prec::F64 ? rtlws::tables_f64(n_fft) : rtlws::tables_f32(n_fft);
     Tables tb;
-    HIP_TRY(hipSetDevice(e->device), -3);
-    if (fused) {
-        const int T = n_fft / 16, R3 = n_fft / 256, NP = R3 / 2;
-        std::vector<float2> h1((size_t)T * 16), h1s((size_t)T * 16), h2((size_t)NP * 16);
-        for (int t = 0; t < T; ++t)
-            for (int s = 0; s < 16; ++s) {
-                const long ex = ((long)t * rev16h(s)) % n_fft;
-                const double a = -kTwoPi * (double)ex / (double)n_fft;
-                const float c = (float)std::cos(a), sn = (float)std::sin(a);
-                h1[(size_t)t * 16 + s] = make_float2(c, sn);
-                h1s[(size_t)t * 16 + s] = make_float2(c * 0.0078125f, sn * 0.0078125f);
-            }
-        for (int q2 = 0; q2 < 16; ++q2) {
-            int k = 0;
-            for (int L = 2; L <= R3; L *= 2)
-                for (int p = 0; p < (L >= 4 ? L / 4 : 1); ++p)
-                    // alpha^(R3/L) * W_L^p = W_(T*L)^(q2*R3 + p*T)
-                    h2[(size_t)q2 * NP + k++] = cos_tan_pair((long)q2 * R3 + (long)p * T, (long)T * L);
-        }
-        std::vector<float2> hcs((size_t)T);
-        for (int t = 0; t < T; ++t) {
-            const double a = kTwoPi * (double)t / (double)n_fft;
-            hcs[t] = make_float2((float)(0.5 * std::cos(a)), (float)(0.5 * std::sin(a)));
-        }
-        if (!upload_table(h1, &tb.tw1) || !upload_table(h1s, &tb.tw1_128) || !upload_table(h2, &tb.tw2) ||
-            !upload_table(hcs, &tb.hann_cs)) {
-            free_tables(tb);
-            return -3;
-        }
-    } else {
-        std::vector<float2> h1((size_t)n_fft);
-        for (int k = 0; k < n_fft; ++k) {
-            const double a = -kTwoPi * (double)k / (double)n_fft;
-            h1[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-        }
-        if (!upload_table(h1, &tb.tw1)) return -3;
-    }
-    {
-        std::vector<float> hw((size_t)n_fft);
-        for (int n = 0; n < n_fft; ++n)
-            hw[n] = (float)(0.5 - 0.5 * std::cos(kTwoPi * (double)n / (double)n_fft));
-        if (!upload_table(hw, &tb.hann)) {
-            free_tables(tb);
-            return -3;
-        }
-    }
-    e->tables[key] = tb;
-    *out = tb;
-    return 0;
-}
-
-// Tables of the f64 kernel (spectrum_f64.hip), once per engine and N: W_N^k for
-// k < N evaluated in long double and rounded once (axis values exact); periodic
-// Hann in double.
-constexpr int kF64Key = 1 << 24;
-
-int get_tables_f64(rtlws_engine* e, int n_fft, Tables* out)
-{
-    std::lock_guard<std::mutex> lk(e->mu);
-    auto it = e->tables.find(kF64Key + n_fft);
-    if (it != e->tables.end()) { *out = it->second; return 0; }
-    Tables tb;
-    HIP_TRY(hipSetDevice(e->device), -3);
-    std::vector<double2> hw((size_t)n_fft);
-    std::vector<double> hh((size_t)n_fft);
-    const long double two_pi = 6.283185307179586476925286766559005768L;
-    for (int k = 0; k < n_fft; ++k) {
-        long double c, sn;                         // exp(-2*pi*i*k/N)
-        if (k == 0) { c = 1.0L; sn = 0.0L; }
-        else if (4L * k == n_fft) { c = 0.0L; sn = -1.0L; }
-        else if (2L * k == n_fft) { c = -1.0L; sn = 0.0L; }
-        else if (4L * k == 3L * n_fft) { c = 0.0L; sn = 1.0L; }
-        else {
-            const long double a = -two_pi * (long double)k / (long double)n_fft;
-            c = cosl(a);
-            sn = sinl(a);
-        }
-        hw[k] = make_double2((double)c, (double)sn);
-        hh[k] = (double)(0.5L - 0.5L * cosl(two_pi * (long double)k / (long double)n_fft));
-    }
-    if (!upload_table(hw, &tb.tw64) || !upload_table(hh, &tb.hann64)) {
-        free_tables(tb);
-        return -3;
-    }
-    if (is_fused_n(n_fft)) {
-        // the fused f64 kernel's tables: the f32 kernel's (get_tables), evaluated in long double
-        // and rounded once to double; the u8 input scale 1/128 folded into tw1 (exact)
-        const int T = n_fft / 16, R3 = n_fft / 256, NP = R3 / 2;
-        auto wn = [&](long num, long den, long double* c, long double* sn) {     // exp(-2 pi i num/den)
-            num %= den;
-            if (num == 0) { *c = 1.0L; *sn = 0.0L; }
-            else if (4 * num == den) { *c = 0.0L; *sn = -1.0L; }
-            else if (2 * num == den) { *c = -1.0L; *sn = 0.0L; }
-            else if (4 * num == 3 * den) { *c = 0.0L; *sn = 1.0L; }
-            else {
-                const long double a = -two_pi * (long double)num / (long double)den;
-                *c = cosl(a);
-                *sn = sinl(a);
-            }
-        };
-        std::vector<double2> h1((size_t)T * 16), h1u((size_t)T * 16), h2((size_t)NP * 16), hcs((size_t)T);
-        for (int t = 0; t < T; ++t) {
-            for (int s = 0; s < 16; ++s) {
-                long double c, sn;
-                wn((long)t * rev16h(s), n_fft, &c, &sn);
-                h1[(size_t)t * 16 + s] = make_double2((double)(c * 0.0078125L), (double)(sn * 0.0078125L));
-                h1u[(size_t)t * 16 + s] = make_double2((double)c, (double)sn);
-            }
-            const long double a = two_pi * (long double)t / (long double)n_fft;
-            hcs[t] = make_double2((double)(0.5L * cosl(a)), (double)(0.5L * sinl(a)));
-        }
-        for (int q2 = 0; q2 < 16; ++q2) {
-            int k = 0;
-            for (int L = 2; L <= R3; L *= 2)
-                for (int pp = 0; pp < (L >= 4 ? L / 4 : 1); ++pp) {
-                    long double c, sn;       // alpha^(R3/L) * W_L^p = W_(T*L)^(q2*R3 + p*T), as (cos, sin/cos)
-                    wn((long)q2 * R3 + (long)pp * T, (long)T * L, &c, &sn);
-                    if (c == 0.0L) c = 1e-20L;
-                    h2[(size_t)q2 * NP + k++] = make_double2((double)c, (double)(sn / c));
-                }
-        }
-        if (!upload_table(h1, &tb.tw1_64) || !upload_table(h1u, &tb.tw1u_64) || !upload_table(h2, &tb.tw2_64) ||
-            !upload_table(hcs, &tb.hann_cs64)) {
-            free_tables(tb);
-            return -3;
-        }
-        if (n_fft == 1024) {
-            // spectrum_f64_1024x.hip: 1024 = 4 x 16 x 16.  Pass A (radix-16 over r on lane (p, c)) absorbs
-            // the geometric part (W_64^p)^r of the twiddle W_1024^(p (c + 16 r)): the pairs of
-            // alpha^(16/L) W_L^p', alpha = W_64^p, = W_(64 L)^(16 p + 64 p'), in fft_last<16>'s order.
-            // The inner twiddles W_256^(c q) carry the lane constant W_1024^(p c) and the exact 1/128.
-            std::vector<double2> ha((size_t)4 * 8), hb((size_t)64 * 16);
-            for (int pq = 0; pq < 4; ++pq) {
-                int k = 0;
-                for (int L = 2; L <= 16; L *= 2)
-                    for (int pp = 0; pp < (L >= 4 ? L / 4 : 1); ++pp) {
-                        long double c, sn;
-                        wn((long)pq * 16 + (long)pp * 64, (long)64 * L, &c, &sn);
-                        if (c == 0.0L) c = 1e-20L;
-                        ha[(size_t)pq * 8 + k++] = make_double2((double)c, (double)(sn / c));
-                    }
-            }
-            for (int t = 0; t < 64; ++t) {
-                const int pq = t >> 4, cc = t & 15;
-                for (int s = 0; s < 16; ++s) {
-                    long double c, sn;
-                    wn((long)cc * (4 * rev16h(s) + pq), 1024, &c, &sn);
-                    hb[(size_t)t * 16 + s] = make_double2((double)(c * 0.0078125L), (double)(sn * 0.0078125L));
-                }
-            }
-            if (!upload_table(ha, &tb.twxa_64) || !upload_table(hb, &tb.twxb_64)) {
-                free_tables(tb);
-                return -3;
-            }
-        }
-    }
-    e->tables[kF64Key + n_fft] = tb;
-    *out = tb;
-    return 0;
+    if (!upload(tb, h.tw1, &tb.tw1) || !upload(tb, h.tw1_128, &tb.tw1_128) || !upload(tb, h.tw2, &tb.tw2) ||
+        !upload(tb, h.hann_cs, &tb.hann_cs) || !upload(tb, h.hann, &tb.hann) || !upload(tb, h.tw64, &tb.tw64) ||
+        !upload(tb, h.hann64, &tb.hann64) || !upload(tb, h.tw1_64, &tb.tw1_64) || !upload(tb, h.tw1u_64, &tb.tw1u_64) ||
+        !upload(tb, h.tw2_64, &tb.tw2_64) || !upload(tb, h.hann_cs64, &tb.hann_cs64) ||
+        !upload(tb, h.twxa_64, &tb.twxa_64) || !upload(tb, h.twxb_64, &tb.twxb_64))
+        return nullptr;
+    return &(e->tables[key] = std::move(tb));
 }
 
 // include/rtlws_hip.h "Streams": NULL = the engine's own non-blocking stream,
@@ -348,22 +187,102 @@ bool use_v2(const rtlws_engine* e, int n_fft, int in_kind, int k_avg)
     return e->opt.v2 >= 0 ? (e->opt.v2 != 0) : (RTLWS_V2_DEFAULT != 0 && k_avg == 1);
 }
 
-int fused_blocks(const rtlws_engine* e, int n_fft, long ngroups, int in_kind = 0, bool win = false,
-                 bool kone = false, int k_avg = 0)
+// Input stage of the fused kernels for a CIC factor.  For A/B experiments
+// (tools/cic_fused_rates.py): option cic_direct keeps every R != 8 on the
+// per-lane direct loads, cic_round = 1|2|4 forces the LDS staging depth
+// where R fits it.
+int cic_in_kind(const rtlws_engine* e, int R)
 {
-    // 4 x waves-per-SIMD wavefronts per CU, n_fft/1024 wavefronts per workgroup.
+    if (R == 8) return rtlws::IN_CU8_CIC8;
+    if (e->opt.cic_direct) return rtlws::cicr_direct_kind(R);
+    if (e->opt.cic_round) {
+        const int k = rtlws::cicr_lds_kind(R, e->opt.cic_round);
+        if (k >= 0) return k;
+    }
+    return rtlws::cicr_kind(R);
+}
+
+// The f32 kernel a descriptor takes and its grid: rtlws_spectra_batch launches it, rtlws_spectra_grid reports it.
+struct PlanF32 {
+    int in_kind;
+    bool v2;
+    int blocks, threads, lds_bytes;
+};
+
+PlanF32 plan_f32(const rtlws_engine* e, const rtlws_spectra_desc* d, long ngroups)
+{
+    const int n = d->n_fft;
+    if (!is_fused_n(n))   // the direct kernel: a workgroup per row; it sums the R bytes of a CIC factor itself
+        return {d->input, false, (int)ngroups, 256, (int)(sizeof(float2) * n)};
+    PlanF32 p;
+    p.in_kind = d->cic_r > 1 ? cic_in_kind(e, d->cic_r) : d->input;
+    p.v2 = use_v2(e, n, p.in_kind, d->k_avg);
+    const bool win = d->window == RTLWS_WIN_HANN;
+    const bool kone = d->k_avg == 1 && rtlws::fused_kone_kind(p.in_kind);
+    // 4 x waves-per-SIMD wavefronts per CU, n/1024 wavefronts per workgroup.
     // Persistent: each workgroup strides over the output rows.
-    int per_cu = 4 * rtlws::fused_waves_per_simd(n_fft, in_kind, win, kone) / (n_fft / 1024);
-    if (use_v2(e, n_fft, in_kind, k_avg)) per_cu = rtlws::v2_blocks_per_cu(n_fft);
+    int per_cu = p.v2 ? rtlws::v2_blocks_per_cu(n) : 4 * rtlws::fused_waves_per_simd(n, p.in_kind, win, kone) / (n / 1024);
     if (e->opt.blocks_per_cu > 0) per_cu = e->opt.blocks_per_cu;   // experiments only
-    long blocks = (long)e->cu_count * per_cu;
-    if (blocks > ngroups) blocks = ngroups;
-    return (int)(blocks < 1 ? 1 : blocks);
+    const long blocks = std::min((long)e->cu_count * per_cu, ngroups);
+    p.blocks = (int)(blocks < 1 ? 1 : blocks);
+    p.threads = p.v2 ? n / 32 : n / 16;
+    p.lds_bytes = p.v2 ? rtlws::v2_lds_bytes(n) : rtlws::fused_lds_bytes(n, p.in_kind, win);
+    return p;
+}
+
+// The f64 kernel a descriptor takes: the fused throughput kernel (spectrum_f64_fused.hip) where it exists and
+// the pointers suit it, else the row-per-workgroup kernel (spectrum_f64.hip).
+struct PlanF64 {
+    int in_kind;
+    bool fused, x1024;
+    int waves, blocks;
+};
+
+PlanF64 plan_f64(const rtlws_engine* e, const rtlws_spectra_desc* d, long ngroups, const void* d_in, const void* d_out)
+{
+    PlanF64 p{d->cic_r > 1 ? cic_in_kind(e, d->cic_r) : d->input, false, false, 0, 0};
+    // the fused kernel's vector accesses: 16-byte rows at N = 1024 (either row precision), 16-byte
+    // input pieces on the CIC-fused kinds; anything less aligned takes the general kernel
+    const bool aligned = !(reinterpret_cast<uintptr_t>(d_out) & 15u) &&
+                         (p.in_kind < rtlws::IN_CU8_CIC8 || !(reinterpret_cast<uintptr_t>(d_in) & 15u));
+    // option f64_fused = 0 keeps everything on the row-per-workgroup kernel (A/B runs, tests)
+    p.fused = rtlws::f64_fused_kind(d->n_fft, p.in_kind) && e->opt.f64_fused && aligned;
+    if (!p.fused) return p;
+    int per_cu = rtlws::f64_fused_blocks_per_cu(d->n_fft);
+    if (e->opt.f64_blocks_per_cu > 0 && e->opt.f64_blocks_per_cu <= 2 * per_cu) per_cu = e->opt.f64_blocks_per_cu;   // experiments only
+    p.blocks = (int)std::min((long)e->cu_count * per_cu, ngroups);
+    // rectangular 1024-point cmplx_u8 frames: one LDS transposition instead of two
+    // (its dB / payload epilogues beside K-frame accumulators would spill: those stay where they were)
+    p.x1024 = d->n_fft == 1024 && p.in_kind == rtlws::IN_CU8 && d->window != RTLWS_WIN_HANN && e->opt.f64_x1024 &&
+              (d->output == RTLWS_OUT_POWER_SUM || d->k_avg == 1);
+    if (p.x1024) {
+        // batches with at least four rows per wavefront: one eight-wavefront workgroup per CU whose
+        // wavefronts take the workgroup's rows one at a time (spectrum_f64_1024x.hip, WAVES)
+        p.waves = e->opt.f64_x_waves;
+        if (p.waves == 0) p.waves = (ngroups >= 32L * e->cu_count) ? 8 : 1;
+        if (!e->x_waves8_ok) p.waves = 1;
+        if (p.waves >= 8) p.blocks = e->cu_count;
+    }
+    return p;
 }
 
 // hipStreamWaitEvent dereferences its stream argument: the hipStreamLegacy token ((hipStream_t)1) crashes it
 // (ROCm 7.2).  This library is built with the legacy default-stream semantics, where stream 0 IS that stream.
 hipStream_t waitable(hipStream_t st) { return st == hipStreamLegacy ? nullptr : st; }
+
+// The tail of every launching entry point, after its argument checks: hipSetDevice, then `launch` on the
+// caller's stream (include/rtlws_hip.h "Streams").  0, or -3 with the error under the name `what`.
+template <typename Launch>
+int launch_on(rtlws_engine* e, void* stream, const char* what, Launch&& launch)
+{
+    HIP_TRY(hipSetDevice(e->device), -3);
+    const hipError_t err = launch(pick_stream(e, stream));
+    if (err != hipSuccess) {
+        set_err(what, err);
+        return -3;
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -402,24 +321,16 @@ rtlws_engine* rtlws_engine_create(int device)
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         e->cu_count = prop.multiProcessorCount;
     // the only place the library reads these variables
-    auto env_int = [](const char* name, int dflt) {
-        const char* v = getenv(name);
-        return (v && *v) ? atoi(v) : dflt;
-    };
-    e->opt.v2 = env_int("RTLWS_V2", -1);
-    e->opt.blocks_per_cu = env_int("RTLWS_BLOCKS_PER_CU", 0);
-    e->opt.f64_fused = env_int("RTLWS_F64_FUSED", 1);
-    e->opt.f64_blocks_per_cu = env_int("RTLWS_F64_BLOCKS_PER_CU", 0);
-    e->opt.f64_x1024 = env_int("RTLWS_F64_X1024", 1);
-    e->opt.f64_x_waves = env_int("RTLWS_F64_X_WAVES", 0);
-    e->opt.cic_direct = env_int("RTLWS_CIC_DIRECT", 0) == 1;
-    e->opt.cic_round = env_int("RTLWS_CIC_ROUND", 0);
+    for (const OptionDef& o : kOptions) {
+        const char* v = getenv(o.env);
+        e->opt.*o.field = (v && *v) ? o.norm(atoi(v)) : o.dflt;
+    }
     // the eight-wavefront workgroups of spectrum_f64_1024x.hip need 136 KiB of LDS: where the device cannot give
     // a workgroup that much, large batches keep the one-wavefront form (17 KiB) instead of failing
     int lds_max = 0;
     if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess ||
         (size_t)lds_max < rtlws::spectra_f64_1024x_lds_bytes(8))
-        e->opt.f64_x_waves8_ok = false;
+        e->x_waves8_ok = false;
     hipError_t err = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
     if (err != hipSuccess) {
         set_err("hipStreamCreate", err);
@@ -434,7 +345,7 @@ void rtlws_engine_destroy(rtlws_engine* e)
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
-    for (auto& kv : e->tables) free_tables(kv.second);
+    e->tables.clear();
     (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -445,37 +356,22 @@ int rtlws_engine_set_option(rtlws_engine* e, const char* name, int value)
 {
     g_err.clear();
     NEED_ENGINE(e, -1);
-    const std::string k = name ? name : "";
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (k == "v2") e->opt.v2 = value < 0 ? -1 : (value != 0);
-    else if (k == "blocks_per_cu") e->opt.blocks_per_cu = value > 0 ? value : 0;
-    else if (k == "f64_fused") e->opt.f64_fused = value != 0;
-    else if (k == "f64_blocks_per_cu") e->opt.f64_blocks_per_cu = value > 0 ? value : 0;
-    else if (k == "f64_x1024") e->opt.f64_x1024 = value != 0;
-    else if (k == "f64_x_waves") e->opt.f64_x_waves = (value == 1 || value == 8) ? value : 0;
-    else if (k == "cic_direct") e->opt.cic_direct = value != 0;
-    else if (k == "cic_round") e->opt.cic_round = (value == 1 || value == 2 || value == 4) ? value : 0;
-    else {
-        g_err = "rtlws_engine_set_option: unknown option '" + k + "'";
+    const OptionDef* o = find_option(name);
+    if (!o) {
+        g_err = std::string("rtlws_engine_set_option: unknown option '") + (name ? name : "") + "'";
         return -1;
     }
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->opt.*o->field = o->norm(value);
     return 0;
 }
 
 int rtlws_engine_get_option(const rtlws_engine* e, const char* name)
 {
     if (!e || !name) return -2;
-    const std::string k = name;
-    if (k == "v2") return e->opt.v2;
-    if (k == "blocks_per_cu") return e->opt.blocks_per_cu;
-    if (k == "f64_fused") return e->opt.f64_fused;
-    if (k == "f64_blocks_per_cu") return e->opt.f64_blocks_per_cu;
-    if (k == "f64_x1024") return e->opt.f64_x1024;
-    if (k == "f64_x_waves") return e->opt.f64_x_waves;
-    if (k == "cic_direct") return e->opt.cic_direct;
-    if (k == "cic_round") return e->opt.cic_round;
-    if (k == "cu_count") return e->cu_count;
-    return -2;
+    if (std::strcmp(name, "cu_count") == 0) return e->cu_count;
+    const OptionDef* o = find_option(name);
+    return o ? e->opt.*o->field : -2;
 }
 
 int rtlws_engine_prepare(rtlws_engine* e, int n_fft)
@@ -489,8 +385,7 @@ int rtlws_engine_prepare(rtlws_engine* e, int n_fft)
         g_err = "rtlws_engine_prepare: unsupported size";
         return -1;
     }
-    Tables tb;
-    return get_tables(e, n_fft, is_fused_n(n_fft), &tb);
+    return get_tables(e, Prec::F32, n_fft) ? 0 : -3;
 }
 
 int rtlws_engine_prepare_f64(rtlws_engine* e, int n_fft)
@@ -500,12 +395,11 @@ int rtlws_engine_prepare_f64(rtlws_engine* e, int n_fft)
     std::memset(&d, 0, sizeof d);
     d.n_fft = n_fft;
     d.k_avg = 1;
-    if (!e || !desc_ok(&d) || n_fft > 8192) {
+    if (!e || !desc_ok(&d)) {
         g_err = "rtlws_engine_prepare_f64: unsupported size (2 <= n_fft <= 8192)";
         return -1;
     }
-    Tables tb;
-    if (get_tables_f64(e, n_fft, &tb) != 0) return -3;
+    if (!get_tables(e, Prec::F64, n_fft)) return -3;
     // Instantiations that need more than 64 KiB of LDS raise their limit with hipFuncSetAttribute, once per
     // instantiation and device: do that for every instantiation of this size NOW (launchers called with an
     // empty grid set the attribute and enqueue nothing), so that a launch -- under hipGraph capture too --
@@ -524,7 +418,7 @@ int rtlws_engine_prepare_f64(rtlws_engine* e, int n_fft)
                 p.rows_f32 = rows_f32 && out != rtlws::OUT_PAYLOAD;
                 if (n_fft == 1024 && (out == rtlws::OUT_SUM || k_avg == 1)) {
                     p.window = nullptr;
-                    if (e->opt.f64_x_waves8_ok) err = rtlws::launch_spectra_f64_1024x(p, 0, 8, e->stream);
+                    if (e->x_waves8_ok) err = rtlws::launch_spectra_f64_1024x(p, 0, 8, e->stream);
                 }
                 if (n_fft == 4096)
                     for (int w = 0; w <= 1 && err == hipSuccess; ++w) {
@@ -714,22 +608,6 @@ float rtlws_event_elapsed_ms(void* start, void* stop)
     return ms;
 }
 
-// Input stage of the fused kernel for a CIC factor.  For A/B experiments
-// (tools/cic_fused_rates.py): option cic_direct keeps every R != 8 on the
-// per-lane direct loads, cic_round = 1|2|4 forces the LDS staging depth
-// where R fits it.
-static int cic_in_kind(const rtlws_engine* e, int R)
-{
-    if (R == 8) return rtlws::IN_CU8_CIC8;
-    const int force = e->opt.cic_direct ? -1 : e->opt.cic_round;
-    if (force < 0) return rtlws::cicr_direct_kind(R);
-    if (force == 1 || force == 2 || force == 4) {
-        const int k = rtlws::cicr_lds_kind(R, force);
-        if (k >= 0) return k;
-    }
-    return rtlws::cicr_kind(R);
-}
-
 int rtlws_spectra_kernel_kind(const rtlws_spectra_desc* d)
 {
     if (!desc_ok(d)) return 0;
@@ -740,20 +618,10 @@ int rtlws_spectra_grid(rtlws_engine* e, const rtlws_spectra_desc* d, long nframe
                        int* threads, int* lds_bytes)
 {
     if (!e || !desc_ok(d) || nframes < 0 || nframes % d->k_avg) return -1;
-    const long ngroups = nframes / d->k_avg;
-    if (is_fused_n(d->n_fft)) {
-        int in_kind = d->input;
-        if (d->cic_r > 1) in_kind = cic_in_kind(e, d->cic_r);
-        if (blocks) *blocks = fused_blocks(e, d->n_fft, ngroups, in_kind, d->window == RTLWS_WIN_HANN,
-                                           d->k_avg == 1 && rtlws::fused_kone_kind(in_kind), d->k_avg);
-        const bool v2 = use_v2(e, d->n_fft, in_kind, d->k_avg);
-        if (threads) *threads = v2 ? d->n_fft / 32 : d->n_fft / 16;
-        if (lds_bytes) *lds_bytes = v2 ? rtlws::v2_lds_bytes(d->n_fft) : rtlws::fused_lds_bytes(d->n_fft, in_kind, d->window == RTLWS_WIN_HANN);
-    } else {
-        if (blocks) *blocks = (int)ngroups;
-        if (threads) *threads = 256;
-        if (lds_bytes) *lds_bytes = (int)(sizeof(float2) * d->n_fft);
-    }
+    const PlanF32 k = plan_f32(e, d, nframes / d->k_avg);
+    if (blocks) *blocks = k.blocks;
+    if (threads) *threads = k.threads;
+    if (lds_bytes) *lds_bytes = k.lds_bytes;
     return 0;
 }
 
@@ -772,10 +640,10 @@ int rtlws_spectra_batch(rtlws_engine* e, const rtlws_spectra_desc* d, const void
         g_err = "rtlws_spectra_batch: d_in and d_out must be 16-byte aligned";
         return -1;
     }
-    const bool fused = is_fused_n(d->n_fft);
-    Tables tb;
-    if (get_tables(e, d->n_fft, fused, &tb) != 0) return -3;
+    const Tables* tb = get_tables(e, Prec::F32, d->n_fft);
+    if (!tb) return -3;
 
+    const bool fused = is_fused_n(d->n_fft);
     rtlws::SpectraParams p;
     std::memset(&p, 0, sizeof p);
     p.in = d_in;
@@ -786,40 +654,25 @@ int rtlws_spectra_batch(rtlws_engine* e, const rtlws_spectra_desc* d, const void
     p.n_fft = d->n_fft;
     p.out_mode = d->output;
     const bool scaled = (d->input != RTLWS_IN_RF32);
-    p.tw1 = (fused && scaled) ? tb.tw1_128 : tb.tw1;
-    p.tw2 = tb.tw2;
+    p.tw1 = (fused && scaled) ? tb->tw1_128 : tb->tw1;
+    p.tw2 = tb->tw2;
     p.in_scale = scaled ? 0.0078125f : 1.0f;
-    p.window = (d->window == RTLWS_WIN_HANN) ? tb.hann : nullptr;
-    p.hann_cs = tb.hann_cs;
+    p.window = (d->window == RTLWS_WIN_HANN) ? tb->hann : nullptr;
+    p.hann_cs = tb->hann_cs;
     p.db_offset = (float)(-10.0 * std::log10((double)d->k_avg));
     // reference src/cbb_main.c:112: pow(10, gain_db/10) with C integer division
     p.lin_gain = (float)(std::pow(10.0, (double)(d->gain_db / 10)) / (double)d->k_avg);
 
-    int in_kind = d->input;
-    if (d->cic_r > 1) in_kind = cic_in_kind(e, d->cic_r);
-
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipStream_t st = pick_stream(e, stream);
-    auto launch = [&](const rtlws::SpectraParams& pp, hipStream_t s) -> hipError_t {
-        if (fused) {
-            const int blocks = fused_blocks(e, d->n_fft, pp.ngroups, in_kind, pp.window != nullptr,
-                                            d->k_avg == 1 && rtlws::fused_kone_kind(in_kind), d->k_avg);
-            if (use_v2(e, d->n_fft, in_kind, d->k_avg)) return rtlws::launch_spectra_fused_v2(pp, blocks, s);
-            switch (d->n_fft) {
-            case 1024: return rtlws::launch_spectra_fused_1024(pp, in_kind, blocks, s);
-            case 2048: return rtlws::launch_spectra_fused_2048(pp, in_kind, blocks, s);
-            default: return rtlws::launch_spectra_fused_4096(pp, in_kind, blocks, s);
-            }
+    const PlanF32 k = plan_f32(e, d, p.ngroups);
+    return launch_on(e, stream, "spectra kernel launch", [&](hipStream_t s) {
+        if (!fused) return rtlws::launch_spectra_direct(p, k.in_kind, s);
+        if (k.v2) return rtlws::launch_spectra_fused_v2(p, k.blocks, s);
+        switch (d->n_fft) {
+        case 1024: return rtlws::launch_spectra_fused_1024(p, k.in_kind, k.blocks, s);
+        case 2048: return rtlws::launch_spectra_fused_2048(p, k.in_kind, k.blocks, s);
+        default: return rtlws::launch_spectra_fused_4096(p, k.in_kind, k.blocks, s);
         }
-        // the direct kernel sums R bytes itself
-        return rtlws::launch_spectra_direct(pp, in_kind >= rtlws::IN_CU8_CIC8 ? (int)rtlws::IN_CU8 : in_kind, s);
-    };
-    const hipError_t err = launch(p, st);
-    if (err != hipSuccess) {
-        set_err("spectra kernel launch", err);
-        return -3;
-    }
-    return 0;
+    });
 }
 
 int rtlws_payload_from_sums(rtlws_engine* e, const float* d_sums, int n, int count, int gain_db,
@@ -830,22 +683,17 @@ int rtlws_payload_from_sums(rtlws_engine* e, const float* d_sums, int n, int cou
         g_err = "rtlws_payload_from_sums: bad argument";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    const float lin = (float)(std::pow(10.0, (double)(gain_db / 10)) / (double)count);
-    hipError_t err = rtlws::launch_payload(d_sums, n, lin, reinterpret_cast<uint8_t*>(d_out),
-                                           pick_stream(e, stream));
-    if (err != hipSuccess) {
-        set_err("payload kernel launch", err);
-        return -3;
-    }
-    return 0;
+    return launch_on(e, stream, "payload kernel launch", [&](hipStream_t s) {
+        const float lin = (float)(std::pow(10.0, (double)(gain_db / 10)) / (double)count);
+        return rtlws::launch_payload(d_sums, n, lin, reinterpret_cast<uint8_t*>(d_out), s);
+    });
 }
 
 int rtlws_spectra_batch_f64(rtlws_engine* e, const rtlws_spectra_desc* d, const void* d_in,
                             long nframes, void* d_out, void* stream)
 {
     g_err.clear();
-    if (!e || !desc_ok(d) || d->n_fft > 8192 || !d_in || !d_out || nframes < 0 || nframes % d->k_avg) {
+    if (!e || !desc_ok(d) || !d_in || !d_out || nframes < 0 || nframes % d->k_avg) {
         g_err = "rtlws_spectra_batch_f64: bad descriptor (2 <= n_fft <= 8192), pointer or frame count";
         return -1;
     }
@@ -855,8 +703,8 @@ int rtlws_spectra_batch_f64(rtlws_engine* e, const rtlws_spectra_desc* d, const 
         g_err = "rtlws_spectra_batch_f64: d_in must be 8-byte aligned, d_out 8-byte (4-byte for f32 rows and payload bytes)";
         return -1;
     }
-    Tables tb;
-    if (get_tables_f64(e, d->n_fft, &tb) != 0) return -3;
+    const Tables* tb = get_tables(e, Prec::F64, d->n_fft);
+    if (!tb) return -3;
 
     rtlws::SpectraParamsF64 p;
     std::memset(&p, 0, sizeof p);
@@ -871,61 +719,29 @@ int rtlws_spectra_batch_f64(rtlws_engine* e, const rtlws_spectra_desc* d, const 
         for (int n = d->n_fft; n > 1; n >>= 1) ++p.log2n;
     p.out_mode = d->output;
     p.count = d->k_avg;
-    p.tw = tb.tw64;
-    p.window = (d->window == RTLWS_WIN_HANN) ? tb.hann64 : nullptr;
+    p.tw = tb->tw64;
+    p.window = (d->window == RTLWS_WIN_HANN) ? tb->hann64 : nullptr;
     // reference src/cbb_main.c:112: pow(10, gain_db/10) with C integer division
     p.lin_gain = std::pow(10.0, (double)(d->gain_db / 10));
     p.in_scale = (d->input != RTLWS_IN_RF32) ? 0.0078125 : 1.0;
 
-    p.tw1f = (d->input == RTLWS_IN_RF32) ? tb.tw1u_64 : tb.tw1_64;
-    p.tw2f = tb.tw2_64;
-    p.hann_csf = tb.hann_cs64;
+    p.tw1f = (d->input == RTLWS_IN_RF32) ? tb->tw1u_64 : tb->tw1_64;
+    p.tw2f = tb->tw2_64;
+    p.hann_csf = tb->hann_cs64;
     p.rows_f32 = (d->flags & RTLWS_FLAG_ROWS_F32) && d->output != RTLWS_OUT_PAYLOAD_U8;
-    p.twxa = tb.twxa_64;
-    p.twxb = tb.twxb_64;
+    p.twxa = tb->twxa_64;
+    p.twxb = tb->twxb_64;
 
-    int in_kind = d->input;
-    if (d->cic_r > 1) in_kind = cic_in_kind(e, d->cic_r);
-    // the fused kernel's vector accesses: 16-byte rows at N = 1024 (either row precision), 16-byte
-    // input pieces on the CIC-fused kinds; anything less aligned takes the general kernel
-    const bool aligned = !(reinterpret_cast<uintptr_t>(d_out) & 15u) &&
-                         (in_kind < rtlws::IN_CU8_CIC8 || !(reinterpret_cast<uintptr_t>(d_in) & 15u));
-
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipStream_t st = pick_stream(e, stream);
-    // the fused throughput kernel (spectrum_f64_fused.hip) where it exists; option f64_fused = 0
-    // keeps everything on the row-per-workgroup kernel (A/B runs, tests)
-    const bool fused = rtlws::f64_fused_kind(d->n_fft, in_kind) && e->opt.f64_fused && aligned;
-    auto launch = [&](const rtlws::SpectraParamsF64& pp, hipStream_t s) -> hipError_t {
-        if (!fused) return rtlws::launch_spectra_f64(pp, d->input, s, e->device);
-        int per_cu = rtlws::f64_fused_blocks_per_cu(d->n_fft);
-        if (e->opt.f64_blocks_per_cu > 0 && e->opt.f64_blocks_per_cu <= 2 * per_cu) per_cu = e->opt.f64_blocks_per_cu;   // experiments only
-        long blocks = (long)e->cu_count * per_cu;
-        if (blocks > pp.ngroups) blocks = pp.ngroups;
-        // rectangular 1024-point cmplx_u8 frames: one LDS transposition instead of two
-        // (its dB / payload epilogues beside K-frame accumulators would spill: those stay where they were)
-        if (d->n_fft == 1024 && in_kind == rtlws::IN_CU8 && !pp.window && e->opt.f64_x1024 && pp.twxa &&
-            (d->output == RTLWS_OUT_POWER_SUM || d->k_avg == 1)) {
-            // batches with at least four rows per wavefront: one eight-wavefront workgroup per CU whose
-            // wavefronts take the workgroup's rows one at a time (spectrum_f64_1024x.hip, WAVES)
-            int waves = e->opt.f64_x_waves;
-            if (waves == 0) waves = (pp.ngroups >= 32L * e->cu_count) ? 8 : 1;
-            if (!e->opt.f64_x_waves8_ok) waves = 1;
-            if (waves >= 8) blocks = e->cu_count;
-            return rtlws::launch_spectra_f64_1024x(pp, (int)blocks, waves, s);
-        }
+    const PlanF64 k = plan_f64(e, d, p.ngroups, d_in, d_out);
+    return launch_on(e, stream, "f64 spectra kernel launch", [&](hipStream_t s) {
+        if (!k.fused) return rtlws::launch_spectra_f64(p, d->input, s, e->device);
+        if (k.x1024) return rtlws::launch_spectra_f64_1024x(p, k.blocks, k.waves, s);
         switch (d->n_fft) {
-        case 1024: return rtlws::launch_spectra_f64_fused_1024(pp, in_kind, (int)blocks, s, e->device);
-        case 2048: return rtlws::launch_spectra_f64_fused_2048(pp, in_kind, (int)blocks, s, e->device);
-        default: return rtlws::launch_spectra_f64_fused_4096(pp, in_kind, (int)blocks, s, e->device);
+        case 1024: return rtlws::launch_spectra_f64_fused_1024(p, k.in_kind, k.blocks, s, e->device);
+        case 2048: return rtlws::launch_spectra_f64_fused_2048(p, k.in_kind, k.blocks, s, e->device);
+        default: return rtlws::launch_spectra_f64_fused_4096(p, k.in_kind, k.blocks, s, e->device);
         }
-    };
-    const hipError_t err = launch(p, st);
-    if (err != hipSuccess) {
-        set_err("f64 spectra kernel launch", err);
-        return -3;
-    }
-    return 0;
+    });
 }
 
 int rtlws_payload_from_sums_f64(rtlws_engine* e, const double* d_sums, int n, int count, int gain_db,
@@ -936,14 +752,10 @@ int rtlws_payload_from_sums_f64(rtlws_engine* e, const double* d_sums, int n, in
         g_err = "rtlws_payload_from_sums_f64: bad argument";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipError_t err = rtlws::launch_payload_f64(d_sums, n, std::pow(10.0, (double)(gain_db / 10)), count,
-                                               reinterpret_cast<uint8_t*>(d_out), pick_stream(e, stream));
-    if (err != hipSuccess) {
-        set_err("f64 payload kernel launch", err);
-        return -3;
-    }
-    return 0;
+    return launch_on(e, stream, "f64 payload kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_payload_f64(d_sums, n, std::pow(10.0, (double)(gain_db / 10)), count,
+                                         reinterpret_cast<uint8_t*>(d_out), s);
+    });
 }
 
 int rtlws_welch_accumulate_f64(rtlws_engine* e, double* d_acc, const double* d_part, int n,
@@ -954,10 +766,9 @@ int rtlws_welch_accumulate_f64(rtlws_engine* e, double* d_acc, const double* d_p
         g_err = "rtlws_welch_accumulate_f64: bad argument";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipError_t err = rtlws::launch_welch_accumulate(d_acc, d_part, n, frames_end, d_b, pick_stream(e, stream));
-    if (err != hipSuccess) { set_err("welch accumulate kernel launch", err); return -3; }
-    return 0;
+    return launch_on(e, stream, "welch accumulate kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_welch_accumulate(d_acc, d_part, n, frames_end, d_b, s);
+    });
 }
 
 int rtlws_welch_finish_f64(rtlws_engine* e, double* d_acc, int n, long total, double* d_b, void* stream)
@@ -967,10 +778,9 @@ int rtlws_welch_finish_f64(rtlws_engine* e, double* d_acc, int n, long total, do
         g_err = "rtlws_welch_finish_f64: bad argument";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipError_t err = rtlws::launch_welch_finish(d_acc, n, total, d_b, pick_stream(e, stream));
-    if (err != hipSuccess) { set_err("welch finish kernel launch", err); return -3; }
-    return 0;
+    return launch_on(e, stream, "welch finish kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_welch_finish(d_acc, n, total, d_b, s);
+    });
 }
 
 int rtlws_cic_block_sums(rtlws_engine* e, int R, const void* d_src, long dst_len, void* d_dst,
@@ -985,13 +795,9 @@ int rtlws_cic_block_sums(rtlws_engine* e, int R, const void* d_src, long dst_len
         g_err = "rtlws_cic_block_sums: d_src must be 16-byte and d_dst 8-byte aligned";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipError_t err = rtlws::launch_cic_block_sums(R, d_src, dst_len, d_dst, pick_stream(e, stream), e->cu_count);
-    if (err != hipSuccess) {
-        set_err("cic kernel launch", err);
-        return -3;
-    }
-    return 0;
+    return launch_on(e, stream, "cic kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_cic_block_sums(R, d_src, dst_len, d_dst, s, e->cu_count);
+    });
 }
 
 int rtlws_fm_demod(rtlws_engine* e, const void* d_iq, long len, const float* d_prev_in,
@@ -1007,27 +813,14 @@ int rtlws_fm_demod(rtlws_engine* e, const void* d_iq, long len, const float* d_p
         g_err = "rtlws_fm_demod: d_iq must be 8-byte and d_out 4-byte aligned";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    if (len == 0) {   // nothing to demodulate: the carried phase passes through
-        HIP_TRY(hipMemcpyAsync(d_prev_out, d_prev_in, sizeof(float), hipMemcpyDeviceToDevice,
-                               pick_stream(e, stream)), -3);
-        return 0;
-    }
-    hipError_t err = rtlws::launch_fm_demod(d_iq, len, d_prev_in, d_prev_out, d_out, pick_stream(e, stream), e->cu_count);
-    if (err != hipSuccess) {
-        set_err("fm_demod kernel launch", err);
-        return -3;
-    }
-    return 0;
+    if (len == 0)   // nothing to demodulate: the carried phase passes through
+        return launch_on(e, stream, "fm_demod phase copy", [&](hipStream_t s) {
+            return hipMemcpyAsync(d_prev_out, d_prev_in, sizeof(float), hipMemcpyDeviceToDevice, s);
+        });
+    return launch_on(e, stream, "fm_demod kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_fm_demod(d_iq, len, d_prev_in, d_prev_out, d_out, s, e->cu_count);
+    });
 }
-
-// ---- shader-clock probe -------------------------------------------------------------------
-struct rtlws_clock_probe {
-    rtlws_engine* e = nullptr;
-    hipStream_t q = nullptr;            // its own queue: runs beside whatever the caller times
-    int* stop = nullptr;                // pinned, device-visible
-    unsigned long long* out = nullptr;  // pinned: {shader clocks, 100 MHz ticks, polls, resident flag}
-};
 
 int rtlws_clock_stamp(rtlws_engine* e, unsigned long long* d_out, int slots, void* stream)
 {
@@ -1037,86 +830,9 @@ int rtlws_clock_stamp(rtlws_engine* e, unsigned long long* d_out, int slots, voi
         g_err = "rtlws_clock_stamp: d_out must be an 8-byte aligned device pointer to slots x 4 64-bit words, 1 <= slots <= 65536";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    const hipError_t err = rtlws::launch_clock_stamp(d_out, slots, pick_stream(e, stream));
-    if (err != hipSuccess) { set_err("clock stamp kernel launch", err); return -3; }
-    return 0;
-}
-
-void* rtlws_clock_probe_start(rtlws_engine* e)
-{
-    g_err.clear();
-    NEED_ENGINE(e, nullptr);
-    HIP_TRY(hipSetDevice(e->device), nullptr);
-    rtlws_clock_probe* p = new rtlws_clock_probe;
-    p->e = e;
-    hipError_t err = hipStreamCreateWithFlags(&p->q, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipHostMalloc(reinterpret_cast<void**>(&p->stop), sizeof(int), hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
-    if (err == hipSuccess) err = hipHostMalloc(reinterpret_cast<void**>(&p->out), 4 * sizeof(unsigned long long), hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
-    if (err == hipSuccess) {
-        *p->stop = 0;
-        p->out[0] = p->out[1] = p->out[2] = p->out[3] = 0;
-        // at most 2^24 polls of ~0.5 us: the wavefront leaves after ~10 s whatever the host does
-        err = rtlws::launch_clock_probe(p->stop, p->out, 1 << 24, p->q);
-        // The first launch on a new queue sets the queue up (about a millisecond, during which launches
-        // on other queues wait): return only once the wavefront is resident, so none of that lands in
-        // the interval the caller is about to time.  Bounded: ~2 s, then the probe is used as it is.
-        for (long spin = 0; err == hipSuccess && spin < 2000000L; ++spin) {
-            if (__atomic_load_n(&p->out[3], __ATOMIC_ACQUIRE)) break;
-            struct timespec ts = {0, 1000};
-            nanosleep(&ts, nullptr);
-        }
-    }
-    if (err != hipSuccess) {
-        set_err("rtlws_clock_probe_start", err);
-        if (p->q) (void)hipStreamDestroy(p->q);
-        if (p->stop) (void)hipHostFree(p->stop);
-        if (p->out) (void)hipHostFree(p->out);
-        delete p;
-        return nullptr;
-    }
-    return p;
-}
-
-void rtlws_clock_probe_signal(void* probe)
-{
-    rtlws_clock_probe* p = reinterpret_cast<rtlws_clock_probe*>(probe);
-    if (p) __atomic_store_n(p->stop, 1, __ATOMIC_RELEASE);
-}
-
-int rtlws_clock_probe_signal_on_stream(void* probe, void* stream)
-{
-    g_err.clear();
-    rtlws_clock_probe* p = reinterpret_cast<rtlws_clock_probe*>(probe);
-    if (!p) { g_err = "rtlws_clock_probe_signal_on_stream: null probe"; return -1; }
-    HIP_TRY(hipSetDevice(p->e->device), -3);
-    // the command processor writes the flag when it reaches this packet, i.e. once everything enqueued on
-    // `stream` before it has completed: no host round trip between the last launch and the probe's exit
-    HIP_TRY(hipStreamWriteValue32(pick_stream(p->e, stream), p->stop, 1, 0), -3);
-    return 0;
-}
-
-int rtlws_clock_probe_stop(void* probe, double* sclk_ghz, double* seconds)
-{
-    g_err.clear();
-    rtlws_clock_probe* p = reinterpret_cast<rtlws_clock_probe*>(probe);
-    if (!p) { g_err = "rtlws_clock_probe_stop: null probe"; return -1; }
-    int rc = 0;
-    (void)hipSetDevice(p->e->device);
-    __atomic_store_n(p->stop, 1, __ATOMIC_RELEASE);
-    hipError_t err = hipStreamSynchronize(p->q);
-    if (err != hipSuccess) { set_err("rtlws_clock_probe_stop", err); rc = -3; }
-    const double clocks = (double)p->out[0], ticks = (double)p->out[1];
-    if (rc == 0 && ticks <= 0.0) { g_err = "rtlws_clock_probe_stop: the probe recorded no interval"; rc = -3; }
-    if (rc == 0) {
-        if (sclk_ghz) *sclk_ghz = clocks / ticks * 0.1;       // ticks are 10 ns
-        if (seconds) *seconds = ticks * 1e-8;
-    }
-    (void)hipStreamDestroy(p->q);
-    (void)hipHostFree(p->stop);
-    (void)hipHostFree(p->out);
-    delete p;
-    return rc;
+    return launch_on(e, stream, "clock stamp kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_clock_stamp(d_out, slots, s);
+    });
 }
 
 int rtlws_copy_d2d(rtlws_engine* e, void* dst, const void* src, size_t bytes, void* stream)
@@ -1134,13 +850,9 @@ int rtlws_halfband(rtlws_engine* e, const float* d_x, float* d_y, long out_len, 
         g_err = "rtlws_halfband: bad argument";
         return -1;
     }
-    HIP_TRY(hipSetDevice(e->device), -3);
-    hipError_t err = rtlws::launch_halfband(d_x, d_y, out_len, pick_stream(e, stream), e->cu_count);
-    if (err != hipSuccess) {
-        set_err("halfband kernel launch", err);
-        return -3;
-    }
-    return 0;
+    return launch_on(e, stream, "halfband kernel launch", [&](hipStream_t s) {
+        return rtlws::launch_halfband(d_x, d_y, out_len, s, e->cu_count);
+    });
 }
 
 }  // extern "C"

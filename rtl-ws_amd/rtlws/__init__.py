@@ -76,8 +76,7 @@ HIP_SYMBOLS = [
     "rtlws_fm_demod", "rtlws_copy_d2d", "rtlws_spectra_batch_f64", "rtlws_payload_from_sums_f64",
     "rtlws_welch_accumulate_f64", "rtlws_welch_finish_f64",
     "rtlws_queue_create", "rtlws_queue_destroy", "rtlws_queue_wait_event", "rtlws_event_create_blocking",
-    "rtlws_clock_probe_start", "rtlws_clock_probe_signal", "rtlws_clock_probe_signal_on_stream",
-    "rtlws_clock_probe_stop", "rtlws_clock_stamp",
+    "rtlws_clock_stamp",
 ]
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
@@ -180,12 +179,6 @@ def hip_lib():
         L.rtlws_fm_demod.argtypes = [vp, vp, l, vp, vp, vp, vp]
         L.rtlws_copy_d2d.argtypes = [vp, vp, vp, sz, vp]
         L.rtlws_clock_stamp.argtypes = [vp, vp, C.c_int, vp]
-        L.rtlws_clock_probe_start.argtypes = [vp]
-        L.rtlws_clock_probe_start.restype = vp
-        L.rtlws_clock_probe_signal.argtypes = [vp]
-        L.rtlws_clock_probe_signal.restype = None
-        L.rtlws_clock_probe_signal_on_stream.argtypes = [vp, vp]
-        L.rtlws_clock_probe_stop.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.rtlws_spectra_grid.argtypes = [vp, C.POINTER(SpectraDesc), l, C.POINTER(i),
                                          C.POINTER(i), C.POINTER(i)]
         _hip = L
@@ -372,25 +365,6 @@ class Engine:
         if not ghz:
             return None, 0.0, 0
         return float(np.median(ghz)), float(np.median(secs)), len(ghz)
-
-    def clock_probe_start(self):
-        """A wavefront beside the next launches that measures the shader clock they run at."""
-        h = hip_lib().rtlws_clock_probe_start(self.h)
-        if not h:
-            raise RuntimeError("rtlws_clock_probe_start failed: %s" % last_error())
-        return h
-
-    def clock_probe_signal(self, probe):
-        hip_lib().rtlws_clock_probe_signal(probe)
-
-    def clock_probe_signal_on_stream(self, probe, stream=None):
-        self._chk(hip_lib().rtlws_clock_probe_signal_on_stream(probe, stream), "rtlws_clock_probe_signal_on_stream")
-
-    def clock_probe_stop(self, probe):
-        """(sclk_ghz, seconds) of the interval since clock_probe_start."""
-        g, s = C.c_double(0.0), C.c_double(0.0)
-        self._chk(hip_lib().rtlws_clock_probe_stop(probe, C.byref(g), C.byref(s)), "rtlws_clock_probe_stop")
-        return g.value, s.value
 
     def set_option(self, name, value):
         """Kernel-selection switch of this engine (include/rtlws_hip.h: rtlws_engine_set_option)."""

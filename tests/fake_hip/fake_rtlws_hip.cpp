@@ -492,18 +492,4 @@ int rtlws_fm_demod(rtlws_engine* e, const void* iq, long len, const float* prev_
     return 0;
 }
 
-struct Probe { std::chrono::steady_clock::time_point t0; };
-void* rtlws_clock_probe_start(rtlws_engine* e) { return e ? new Probe{std::chrono::steady_clock::now()} : nullptr; }
-void rtlws_clock_probe_signal(void*) {}
-int rtlws_clock_probe_signal_on_stream(void* p, void*) { return p ? 0 : -1; }
-int rtlws_clock_probe_stop(void* p, double* ghz, double* seconds)
-{
-    if (!p) return -1;
-    Probe* x = static_cast<Probe*>(p);
-    if (ghz) *ghz = 2.0;
-    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - x->t0).count();
-    delete x;
-    return 0;
-}
-
 }  // extern "C"

@@ -234,25 +234,3 @@ def test_clock_stamps_bracket_a_plausible_clock(ctx):
     L = built.hip_lib()
     assert L.rtlws_clock_stamp(eng.h, None, 4, None) == -1
     assert L.rtlws_clock_stamp(eng.h, st[0].data_ptr() + 4, 4, None) == -1 and L.rtlws_clock_stamp(eng.h, st[0].data_ptr(), 0, None) == -1
-
-
-def test_clock_probe_measures_a_plausible_clock_and_always_leaves(ctx):
-    """rtlws_clock_probe_*: the probe wavefront beside a series of launches reports a shader clock in
-    the chip's range and the length of the interval; stopping it at once (nothing launched) works too."""
-    import time
-    eng, rtlws = ctx["eng"], ctx["rtlws"]
-    from rtlws import synth
-    iq = eng.upload(synth.tone_noise_iq(4096, 1024, seed=3))
-    out = eng.alloc(4096 * 1024 * 4)
-    desc = rtlws.make_desc(1024)
-    probe = eng.clock_probe_start()
-    t0 = time.perf_counter()
-    for _ in range(300):
-        eng.spectra_batch(desc, iq, 4096, out)
-    eng.sync()
-    dt = time.perf_counter() - t0
-    ghz, secs = eng.clock_probe_stop(probe)
-    assert 0.5 < ghz < 2.6, ghz
-    assert 0.5 * dt < secs < dt + 0.05
-    ghz2, secs2 = eng.clock_probe_stop(eng.clock_probe_start())
-    assert 0.3 < ghz2 < 2.6 and secs2 < 0.05
