@@ -5,6 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+#include <set>
+#include <type_traits>
+#include <utility>
+
 namespace rtlws {
 
 // Input kinds as the kernels see them (the public enum rtlws_input plus the
@@ -121,11 +126,19 @@ constexpr int f64_fused_lds_bytes(int n_fft) { return 16 * f64_fused_lds_elems(n
 // 8 wavefronts per CU (2 per SIMD) at every size: 8 / 4 / 2 workgroups
 constexpr int f64_fused_blocks_per_cu(int n_fft) { return 8 / (n_fft / 1024); }
 // rectangular 1024-point cmplx_u8 frames: the one-transposition kernel (engine option f64_x1024)
-hipError_t launch_spectra_f64_1024x(const SpectraParamsF64&, int blocks, int waves, hipStream_t);
+hipError_t launch_spectra_f64_1024x(const SpectraParamsF64&, int blocks, int waves, hipStream_t, int device);
 size_t spectra_f64_1024x_lds_bytes(int waves);      // dynamic LDS per workgroup of that form (waves = 1 | 8)
 hipError_t launch_spectra_f64_fused_1024(const SpectraParamsF64&, int in_kind, int blocks, hipStream_t, int device);
 hipError_t launch_spectra_f64_fused_2048(const SpectraParamsF64&, int in_kind, int blocks, hipStream_t, int device);
 hipError_t launch_spectra_f64_fused_4096(const SpectraParamsF64&, int in_kind, int blocks, hipStream_t, int device);
+// The launchers whose kernels can need more than 64 KiB of LDS: lds_opt_in for every such kernel the launcher can
+// reach (spectra_f64: at this n_fft), on the current device, so that its launches make no other runtime call than
+// the launch (hipGraph capture).  The 1024x form: only where the device holds its eight-wavefront workgroups.
+hipError_t prepare_spectra_f64_1024x(int device);
+hipError_t prepare_spectra_f64_fused_1024(int device);
+hipError_t prepare_spectra_f64_fused_2048(int device);
+hipError_t prepare_spectra_f64_fused_4096(int device);
+hipError_t prepare_spectra_f64(int n_fft, int device);
 
 // Occupancy the fused kernel is built for (waves per SIMD = __launch_bounds__'
 // second argument), by instantiation, chosen so that NO instantiation spills
@@ -241,6 +254,72 @@ hipError_t launch_spectra_f64(const SpectraParamsF64&, int in_kind, hipStream_t,
 hipError_t launch_welch_accumulate(double* d_acc, const double* d_part, int n, long frames_end, double* d_b, hipStream_t);
 hipError_t launch_welch_finish(double* d_acc, int n, long total, double* d_b, hipStream_t);
 hipError_t launch_payload_f64(const double* d_sums, int n, double gain, int count, uint8_t* d_out, hipStream_t);
+
+
+// ---- epilogues of reference src/cbb_main.c:121-130 ----
+// the payload byte: 10*log10(...) truncated by (int), clamped to 0 .. 255
+__device__ __forceinline__ unsigned payload_byte(float d) { return (d >= 0.0f) ? (d <= 255.0f ? (unsigned)(int)d : 255u) : 0u; }
+__device__ __forceinline__ unsigned payload_byte(double d) { return (d >= 0.0) ? (d <= 255.0 ? (unsigned)(int)d : 255u) : 0u; }
+// in double, in the reference's operation order: 10*log10(a / count), and payload_f64(gain * a, count), the byte of
+// 10*log10|gain * a / count| (the caller forms the product before count is read, as the kernels always did)
+__device__ __forceinline__ double db_f64(double a, int count) { return 10.0 * log10(a / (double)count); }
+__device__ __forceinline__ unsigned payload_f64(double ga, int count) { return payload_byte(10.0 * log10(fabs(ga / (double)count))); }
+
+// ---- launch tables: runtime fields -> one template instantiation ----
+#define RTLWS_CAT2(a, b) a##b
+#define RTLWS_CAT(a, b) RTLWS_CAT2(a, b)      // the per-size launchers' names (-DRTLWS_N)
+
+// A table is a nest of choices choose(list, value, f), each handing f its value as a std::integral_constant.
+// `pick` calls f for the listed value equal to `value` (none: hipErrorInvalidValue); `visit_all` calls f for every
+// listed value, whatever `value`, until one fails.  So one table serves the launcher and its prepare entry.
+template <auto... Vs> struct Vals {};
+using Bools = Vals<false, true>;
+using OutModes = Vals<OUT_SUM, OUT_DB, OUT_PAYLOAD>;
+template <bool Exists> struct Flag {};      // a flag only some instantiations have: false in the rest, whatever the value
+
+template <bool All> struct Choose {
+    template <auto... Vs, typename T, typename F>
+    hipError_t operator()(Vals<Vs...>, T v, F&& f) const
+    {
+        hipError_t r = All ? hipSuccess : hipErrorInvalidValue;
+        if constexpr (All) (void)(((r = f(std::integral_constant<decltype(Vs), Vs>{})) == hipSuccess) && ...);
+        else (void)((v == Vs && ((r = f(std::integral_constant<decltype(Vs), Vs>{})), true)) || ...);
+        return r;
+    }
+    template <bool Exists, typename F>
+    hipError_t operator()(Flag<Exists>, bool v, F&& f) const
+    {
+        if constexpr (Exists) return (*this)(Bools{}, v, f);
+        else return f(std::false_type{});
+    }
+};
+constexpr Choose<false> pick{};
+constexpr Choose<true> visit_all{};
+
+// kernel<<<grid, block, lds_bytes, st>>>(p)
+template <typename P>
+hipError_t launch(void (*kernel)(P), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const P& p)
+{
+    void* args[] = {const_cast<P*>(&p)};
+    (void)hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, args, lds_bytes, st);
+    return hipGetLastError();
+}
+
+// A kernel launched with more than 64 KiB of dynamic LDS raises its limit to `bytes` with hipFuncSetAttribute, once
+// per kernel and device (`device`, the current one) before its first launch there; nothing to do at 64 KiB or less.
+// Thread-safe; once done, a lookup and no runtime call.
+template <typename P>
+hipError_t lds_opt_in(void (*kernel)(P), int device, size_t bytes)
+{
+    if (bytes <= 64 * 1024) return hipSuccess;
+    static std::mutex mu;
+    static std::set<std::pair<void (*)(P), int>> done;
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.count({kernel, device})) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) done.insert({kernel, device});
+    return e;
+}
 
 }  // namespace rtlws
 #endif

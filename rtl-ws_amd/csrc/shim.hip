@@ -400,38 +400,14 @@ int rtlws_engine_prepare_f64(rtlws_engine* e, int n_fft)
         return -1;
     }
     if (!get_tables(e, Prec::F64, n_fft)) return -3;
-    // Instantiations that need more than 64 KiB of LDS raise their limit with hipFuncSetAttribute, once per
-    // instantiation and device: do that for every instantiation of this size NOW (launchers called with an
-    // empty grid set the attribute and enqueue nothing), so that a launch -- under hipGraph capture too --
-    // makes no other runtime call than the launch.
+    // Kernels that need more than 64 KiB of LDS opt in once per kernel and device: every launcher that can take
+    // this size does that NOW, so that a launch -- under hipGraph capture too -- makes no other runtime call.
     HIP_TRY(hipSetDevice(e->device), -3);
-    rtlws::SpectraParamsF64 p;
-    std::memset(&p, 0, sizeof p);
-    p.n_fft = n_fft;
-    static const double dummy_window = 0.0;
-    hipError_t err = hipSuccess;
-    for (int k_avg = 1; k_avg <= 2 && err == hipSuccess; ++k_avg)
-        for (int out = rtlws::OUT_SUM; out <= rtlws::OUT_PAYLOAD && err == hipSuccess; ++out)
-            for (int rows_f32 = 0; rows_f32 <= 1 && err == hipSuccess; ++rows_f32) {
-                p.k_avg = k_avg;
-                p.out_mode = out;
-                p.rows_f32 = rows_f32 && out != rtlws::OUT_PAYLOAD;
-                if (n_fft == 1024 && (out == rtlws::OUT_SUM || k_avg == 1)) {
-                    p.window = nullptr;
-                    if (e->x_waves8_ok) err = rtlws::launch_spectra_f64_1024x(p, 0, 8, e->stream);
-                }
-                if (n_fft == 4096)
-                    for (int w = 0; w <= 1 && err == hipSuccess; ++w) {
-                        p.window = w ? &dummy_window : nullptr;
-                        for (int in_kind : {(int)rtlws::IN_CU8, (int)rtlws::IN_CS32, (int)rtlws::IN_RF32, (int)rtlws::IN_CU8_CIC8,
-                                            (int)rtlws::IN_CU8_CIC10, (int)rtlws::IN_CU8_CIC12})
-                            if (err == hipSuccess) err = rtlws::launch_spectra_f64_fused_4096(p, in_kind, 0, e->stream, e->device);
-                    }
-            }
-    if (err == hipSuccess && n_fft > 4096) {
-        p.ngroups = 0;
-        for (int in = RTLWS_IN_CU8; in <= RTLWS_IN_RF32 && err == hipSuccess; ++in) err = rtlws::launch_spectra_f64(p, in, e->stream, e->device);
-    }
+    hipError_t err = rtlws::prepare_spectra_f64(n_fft, e->device);
+    if (err == hipSuccess && n_fft == 1024) err = rtlws::prepare_spectra_f64_fused_1024(e->device);
+    if (err == hipSuccess && n_fft == 1024 && e->x_waves8_ok) err = rtlws::prepare_spectra_f64_1024x(e->device);
+    if (err == hipSuccess && n_fft == 2048) err = rtlws::prepare_spectra_f64_fused_2048(e->device);
+    if (err == hipSuccess && n_fft == 4096) err = rtlws::prepare_spectra_f64_fused_4096(e->device);
     if (err != hipSuccess) {
         set_err("rtlws_engine_prepare_f64: hipFuncSetAttribute", err);
         return -3;
@@ -735,7 +711,7 @@ int rtlws_spectra_batch_f64(rtlws_engine* e, const rtlws_spectra_desc* d, const 
     const PlanF64 k = plan_f64(e, d, p.ngroups, d_in, d_out);
     return launch_on(e, stream, "f64 spectra kernel launch", [&](hipStream_t s) {
         if (!k.fused) return rtlws::launch_spectra_f64(p, d->input, s, e->device);
-        if (k.x1024) return rtlws::launch_spectra_f64_1024x(p, k.blocks, k.waves, s);
+        if (k.x1024) return rtlws::launch_spectra_f64_1024x(p, k.blocks, k.waves, s, e->device);
         switch (d->n_fft) {
         case 1024: return rtlws::launch_spectra_f64_fused_1024(p, k.in_kind, k.blocks, s, e->device);
         case 2048: return rtlws::launch_spectra_f64_fused_2048(p, k.in_kind, k.blocks, s, e->device);

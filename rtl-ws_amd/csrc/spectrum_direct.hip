@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void spectra_direct(const SpectraParams p)
             if (p.out_mode == OUT_DB) a = fmaf(10.0f, log10f(a), p.db_offset);
             if (p.out_mode == OUT_PAYLOAD) {
                 const float d = 10.0f * log10f(fabsf(a * p.lin_gain));
-                const unsigned m = (d >= 0.0f) ? (d <= 255.0f ? (unsigned)(int)d : 255u) : 0u;
+                const unsigned m = payload_byte(d);
                 reinterpret_cast<uint8_t*>(p.out)[g * N + i] = (uint8_t)m;
             } else {
                 reinterpret_cast<float*>(p.out)[g * N + i] = a;
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void payload_kernel(const float* __restrict__ 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const float d = 10.0f * log10f(fabsf(sums[i] * lin_gain));
-        const unsigned m = (d >= 0.0f) ? (d <= 255.0f ? (unsigned)(int)d : 255u) : 0u;
+        const unsigned m = payload_byte(d);
         out[i] = (uint8_t)m;
     }
 }
@@ -101,15 +101,9 @@ hipError_t launch_payload(const float* d_sums, int n, float lin_gain, uint8_t* d
 
 hipError_t launch_spectra_direct(const SpectraParams& p, int in_kind, hipStream_t st)
 {
-    const size_t lds_bytes = sizeof(float2) * (size_t)p.n_fft;
-    const dim3 grid((unsigned)p.ngroups), block(256);
-    if (in_kind == IN_CS32)
-        hipLaunchKernelGGL((spectra_direct<IN_CS32>), grid, block, lds_bytes, st, p);
-    else if (in_kind == IN_RF32)
-        hipLaunchKernelGGL((spectra_direct<IN_RF32>), grid, block, lds_bytes, st, p);
-    else
-        hipLaunchKernelGGL((spectra_direct<IN_CU8>), grid, block, lds_bytes, st, p);
-    return hipGetLastError();
+    return pick(Vals<IN_CU8, IN_CS32, IN_RF32>{}, in_kind, [&](auto in) {
+        return launch(&spectra_direct<in>, dim3((unsigned)p.ngroups), dim3(256), sizeof(float2) * (size_t)p.n_fft, st, p);
+    });
 }
 
 }  // namespace rtlws

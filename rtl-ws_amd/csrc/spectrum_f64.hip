@@ -20,8 +20,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "rtlws_internal.h"
 
 namespace rtlws {
@@ -131,12 +129,11 @@ __global__ __launch_bounds__(256) void spectra_f64(const SpectraParamsF64 p)
         if (i < N) {
             const double a = acc[j];
             if (p.out_mode == OUT_PAYLOAD) {
-                // src/cbb_main.c:125-128, same operation order, in double
+                // payload_f64() written out: through the helper the register allocation of this kernel differs
                 const double d = 10.0 * log10(fabs(p.lin_gain * a / (double)p.count));
-                const unsigned m = (d >= 0.0) ? (d <= 255.0 ? (unsigned)(int)d : 255u) : 0u;
-                reinterpret_cast<uint8_t*>(p.out)[g * N + i] = (uint8_t)m;
+                reinterpret_cast<uint8_t*>(p.out)[g * N + i] = (uint8_t)payload_byte(d);
             } else {
-                const double o = (p.out_mode == OUT_DB) ? 10.0 * log10(a / (double)p.count) : a;
+                const double o = (p.out_mode == OUT_DB) ? db_f64(a, p.count) : a;
                 if (p.rows_f32) reinterpret_cast<float*>(p.out)[g * N + i] = (float)o;   // RTLWS_FLAG_ROWS_F32
                 else reinterpret_cast<double*>(p.out)[g * N + i] = o;
             }
@@ -151,9 +148,7 @@ __global__ __launch_bounds__(256) void payload_f64_kernel(const double* __restri
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        const double d = 10.0 * log10(fabs(gain * sums[i] / (double)count));
-        const unsigned m = (d >= 0.0) ? (d <= 255.0 ? (unsigned)(int)d : 255u) : 0u;
-        out[i] = (uint8_t)m;
+        out[i] = (uint8_t)payload_f64(gain * sums[i], count);
     }
 }
 
@@ -207,30 +202,23 @@ hipError_t launch_welch_finish(double* d_acc, int n, long total, double* d_b, hi
     return hipGetLastError();
 }
 
-template <int IN>
-static hipError_t launch_f64_in(const SpectraParamsF64& p, hipStream_t st, int device)
-{
-    const size_t lds_bytes = sizeof(double2) * (size_t)p.n_fft;
-    if (lds_bytes > 64 * 1024) {       // 4096 < N <= 8192: raised once per device to the most any N needs
-        static std::atomic<unsigned long long> ready{0};
-        const unsigned long long bit = 1ull << (device & 63);
-        if (!(ready.load(std::memory_order_acquire) & bit)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spectra_f64<IN>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double2) * 8192));
-            if (e != hipSuccess) return e;
-            ready.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    if (p.ngroups <= 0) return hipSuccess;   // rtlws_engine_prepare_f64: the attribute only, nothing enqueued
-    hipLaunchKernelGGL((spectra_f64<IN>), dim3((unsigned)p.ngroups), dim3(256), lds_bytes, st, p);
-    return hipGetLastError();
-}
+// 4096 < N <= 8192 needs more than 64 KiB: the limit is raised once per kernel and device to the most any N needs
+using F64Inputs = Vals<IN_CU8, IN_CS32, IN_RF32>;
+constexpr int F64_LDS_MAX = (int)sizeof(double2) * 8192;
 
 hipError_t launch_spectra_f64(const SpectraParamsF64& p, int in_kind, hipStream_t st, int device)
 {
-    if (in_kind == IN_CS32) return launch_f64_in<IN_CS32>(p, st, device);
-    if (in_kind == IN_RF32) return launch_f64_in<IN_RF32>(p, st, device);
-    return launch_f64_in<IN_CU8>(p, st, device);
+    const size_t lds_bytes = sizeof(double2) * (size_t)p.n_fft;
+    return pick(F64Inputs{}, in_kind, [&](auto in) {
+        const hipError_t e = lds_bytes > 64 * 1024 ? lds_opt_in(&spectra_f64<in>, device, F64_LDS_MAX) : hipSuccess;
+        return e != hipSuccess ? e : launch(&spectra_f64<in>, dim3((unsigned)p.ngroups), dim3(256), lds_bytes, st, p);
+    });
+}
+
+hipError_t prepare_spectra_f64(int n_fft, int device)
+{
+    if (sizeof(double2) * (size_t)n_fft <= 64 * 1024) return hipSuccess;
+    return visit_all(F64Inputs{}, 0, [&](auto in) { return lds_opt_in(&spectra_f64<in>, device, F64_LDS_MAX); });
 }
 
 }  // namespace rtlws

@@ -33,8 +33,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "rtlws_internal.h"
 #include "fft_regs_f64.h"
 
@@ -237,12 +235,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
                 const long i = g * N + 64 * (rev16(u) ^ 8) + t;
                 const double a = acc[u];
                 if constexpr (OUT == OUT_PAYLOAD) {
-                    // src/cbb_main.c:125-128, same operation order, in double
-                    const double d = 10.0 * log10(fabs(p.lin_gain * a / (double)p.count));
-                    const unsigned m = (d >= 0.0) ? (d <= 255.0 ? (unsigned)(int)d : 255u) : 0u;
-                    reinterpret_cast<uint8_t*>(p.out)[i] = (uint8_t)m;
+                    reinterpret_cast<uint8_t*>(p.out)[i] = (uint8_t)payload_f64(p.lin_gain * a, p.count);
                 } else {
-                    const double o = (OUT == OUT_DB) ? 10.0 * log10(a / (double)p.count) : a;
+                    const double o = (OUT == OUT_DB) ? db_f64(a, p.count) : a;
                     if constexpr (ROWF32) __builtin_nontemporal_store((float)o, reinterpret_cast<float*>(p.out) + i);
                     else __builtin_nontemporal_store(o, reinterpret_cast<double*>(p.out) + i);
                 }
@@ -256,49 +251,38 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
 constexpr size_t x_lds_bytes(int waves) { return (size_t)waves * 16 * 17 * 64 + (waves > 1 ? 16 : 0); }
 size_t spectra_f64_1024x_lds_bytes(int waves) { return x_lds_bytes(waves >= 8 ? 8 : 1); }
 
-template <int OUT, bool ROWF32, int WAVES>
-static hipError_t launch_x_k(const SpectraParamsF64& p, int blocks, hipStream_t st)
+// leaf(kernel, threads, dynamic LDS bytes) for the instantiation the fields select (pick) or for each one the
+// launcher can reach (visit_all).  waves = 1: one-wavefront workgroups; waves = 8: workgroups of eight wavefronts
+// (one per CU), 136 KiB of LDS.
+template <typename Choose, typename Leaf>
+static hipError_t x_table(Choose choose, const SpectraParamsF64& p, int waves, Leaf&& leaf)
 {
-    constexpr size_t lds_bytes = x_lds_bytes(WAVES);
-    if constexpr (lds_bytes > 65536) {      // once per instantiation and device
-        static std::atomic<bool> done[64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        if (!done[dev].load(std::memory_order_acquire)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spectra_f64_1024x<OUT, true, ROWF32, WAVES>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e == hipSuccess && OUT == OUT_SUM)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spectra_f64_1024x<OUT_SUM, false, ROWF32, WAVES>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) return e;
-            done[dev].store(true, std::memory_order_release);
-        }
-    }
-    if (blocks <= 0) return hipSuccess;      // rtlws_engine_prepare_f64: the attribute only, nothing enqueued
-    if (p.k_avg == 1) {
-        hipLaunchKernelGGL((spectra_f64_1024x<OUT, true, ROWF32, WAVES>), dim3(blocks), dim3(64 * WAVES), lds_bytes, st, p);
-    } else if constexpr (OUT == OUT_SUM) {     // (dB / payload beside K-frame accumulators: spectrum_f64_fused.hip)
-        hipLaunchKernelGGL((spectra_f64_1024x<OUT_SUM, false, ROWF32, WAVES>), dim3(blocks), dim3(64 * WAVES), lds_bytes, st, p);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return choose(Vals<1, 8>{}, waves >= 8 ? 8 : 1, [&](auto w) {
+        return choose(OutModes{}, p.out_mode, [&](auto out) {
+            // K-frame accumulators beside the dB / payload epilogues: spectrum_f64_fused.hip
+            using Kone = std::conditional_t<out == OUT_SUM, Bools, Vals<true>>;
+            return choose(Kone{}, p.k_avg == 1, [&](auto kone) {
+                return choose(Flag<out != OUT_PAYLOAD>{}, p.rows_f32 != 0, [&](auto rowf32) {
+                    return leaf(&spectra_f64_1024x<out, kone, rowf32, w>, 64 * w, x_lds_bytes(w));
+                });
+            });
+        });
+    });
 }
 
-template <int WAVES>
-static hipError_t launch_x_w(const SpectraParamsF64& p, int blocks, hipStream_t st)
+hipError_t launch_spectra_f64_1024x(const SpectraParamsF64& p, int blocks, int waves, hipStream_t st, int device)
 {
-    switch (p.out_mode) {
-    case OUT_SUM: return p.rows_f32 ? launch_x_k<OUT_SUM, true, WAVES>(p, blocks, st) : launch_x_k<OUT_SUM, false, WAVES>(p, blocks, st);
-    case OUT_DB: return p.rows_f32 ? launch_x_k<OUT_DB, true, WAVES>(p, blocks, st) : launch_x_k<OUT_DB, false, WAVES>(p, blocks, st);
-    default: return launch_x_k<OUT_PAYLOAD, false, WAVES>(p, blocks, st);
-    }
+    return x_table(pick, p, waves, [&](auto kernel, int threads, size_t lds_bytes) {
+        const hipError_t e = lds_opt_in(kernel, device, lds_bytes);
+        return e != hipSuccess ? e : launch(kernel, dim3(blocks), dim3(threads), lds_bytes, st, p);
+    });
 }
 
-// waves = 1: `blocks` one-wavefront workgroups; waves = 8: `blocks` workgroups of eight wavefronts (one per CU)
-hipError_t launch_spectra_f64_1024x(const SpectraParamsF64& p, int blocks, int waves, hipStream_t st)
+hipError_t prepare_spectra_f64_1024x(int device)
 {
-    return waves >= 8 ? launch_x_w<8>(p, blocks, st) : launch_x_w<1>(p, blocks, st);
+    return x_table(visit_all, SpectraParamsF64{}, 0, [&](auto kernel, int, size_t lds_bytes) {
+        return lds_opt_in(kernel, device, lds_bytes);
+    });
 }
 
 }  // namespace rtlws

@@ -40,8 +40,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "rtlws_internal.h"
 #include "cic_lds.h"
 #include "frame_input.h"
@@ -271,10 +269,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
                 unsigned packed = 0;
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
-                    // src/cbb_main.c:125-128, same operation order, in double
-                    const double d = 10.0 * log10(fabs(p.lin_gain * acc[j * R3 + s] / (double)p.count));
-                    const unsigned m = (d >= 0.0) ? (d <= 255.0 ? (unsigned)(int)d : 255u) : 0u;
-                    packed |= m << (8 * j);
+                    packed |= payload_f64(p.lin_gain * acc[j * R3 + s], p.count) << (8 * j);
                 }
                 uint8_t* dst = reinterpret_cast<uint8_t*>(p.out) + g * N + i0;
                 if constexpr (J == 4) *reinterpret_cast<unsigned*>(dst) = packed;
@@ -292,7 +287,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
                     double a = acc[j * R3 + s];
-                    if constexpr (OUT == OUT_DB) a = 10.0 * log10(a / (double)p.count);
+                    if constexpr (OUT == OUT_DB) a = db_f64(a, p.count);
                     o[j] = (float)a;
                 }
                 float* dst = reinterpret_cast<float*>(p.out) + g * N + i0;
@@ -322,7 +317,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
                     o[j] = acc[j * R3 + s];
-                    if constexpr (OUT == OUT_DB) o[j] = 10.0 * log10(o[j] / (double)p.count);
+                    if constexpr (OUT == OUT_DB) o[j] = db_f64(o[j], p.count);
                 }
                 double x[2], y[2];
 #pragma unroll
@@ -349,7 +344,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
                     o[j] = acc[j * R3 + s];
-                    if constexpr (OUT == OUT_DB) o[j] = 10.0 * log10(o[j] / (double)p.count);
+                    if constexpr (OUT == OUT_DB) o[j] = db_f64(o[j], p.count);
                 }
                 double* dst = reinterpret_cast<double*>(p.out) + g * N + i0;
                 if constexpr (J == 2) {
@@ -366,75 +361,43 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
 
 // ---- launch table (this file is compiled once per RTLWS_N) -----------------
 
-// N = 4096 needs 69.6 KiB of LDS per workgroup: the attribute is set once per instantiation and
-// device (a bit per device; the launch path itself makes no other HIP call than the launch)
-template <int N, int IN, bool WIN, int OUT, bool KONE, bool ROWF32>
-static hipError_t launch_f64f_one(const SpectraParamsF64& p, int blocks, hipStream_t st, int device)
+// leaf(kernel, threads, dynamic LDS bytes) for the instantiation the fields select (pick) or for each one the
+// launcher can reach (visit_all).  N = 4096 needs 69.6 KiB of LDS per workgroup.
+template <typename Choose, typename Leaf>
+static hipError_t f64f_table(Choose choose, const SpectraParamsF64& p, int in_kind, Leaf&& leaf)
 {
-    constexpr size_t lds_bytes = f64_fused_lds_bytes(N) + (f64_fused_tw3_regs(N, IN, WIN, KONE) ? 0 : 16 * 16 * (N / 512));
-    if constexpr (lds_bytes > 64 * 1024) {
-        static std::atomic<unsigned long long> ready{0};
-        const unsigned long long bit = 1ull << (device & 63);
-        if (!(ready.load(std::memory_order_acquire) & bit)) {
-            const hipError_t e = hipFuncSetAttribute(
-                reinterpret_cast<const void*>(&spectra_f64_fused<N, IN, WIN, OUT, KONE, ROWF32>),
-                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) return e;
-            ready.fetch_or(bit, std::memory_order_release);
-        }
-    }
-    if (blocks <= 0) return hipSuccess;      // rtlws_engine_prepare_f64: the attribute only, nothing enqueued
-    hipLaunchKernelGGL((spectra_f64_fused<N, IN, WIN, OUT, KONE, ROWF32>), dim3(blocks), dim3(N / 16), lds_bytes, st, p);
-    return hipGetLastError();
+    constexpr int N = RTLWS_N;
+    using Inputs = Vals<IN_CU8, IN_CS32, IN_RF32, IN_CU8_CIC8, IN_CU8_CIC10, IN_CU8_CIC12>;
+    return choose(Inputs{}, in_kind, [&](auto in) {
+        return choose(Bools{}, p.window != nullptr, [&](auto win) {
+            return choose(OutModes{}, p.out_mode, [&](auto out) {
+                // K == 1 gets its own instantiation (no accumulators) on the kinds that have one in the f32
+                // kernel too; cmplx_s32 / real f32 share the general-K code
+                return choose(Flag<fused_kone_kind(in)>{}, p.k_avg == 1, [&](auto kone) {
+                    return choose(Flag<out != OUT_PAYLOAD>{}, p.rows_f32 != 0, [&](auto rowf32) {
+                        return leaf(&spectra_f64_fused<N, in, win, out, kone, rowf32>, N / 16,
+                                    f64_fused_lds_bytes(N) + (f64_fused_tw3_regs(N, in, win, kone) ? 0 : 16 * 16 * (N / 512)));
+                    });
+                });
+            });
+        });
+    });
 }
-
-template <int N, int IN, bool WIN, int OUT, bool ROWF32>
-static hipError_t launch_f64f_k(const SpectraParamsF64& p, int blocks, hipStream_t st, int device)
-{
-    // K == 1 gets its own instantiation (no accumulators) on the kinds that have one in the f32
-    // kernel too; cmplx_s32 / real f32 share the general-K code
-    if constexpr (fused_kone_kind(IN)) {
-        if (p.k_avg == 1) return launch_f64f_one<N, IN, WIN, OUT, true, ROWF32>(p, blocks, st, device);
-    }
-    return launch_f64f_one<N, IN, WIN, OUT, false, ROWF32>(p, blocks, st, device);
-}
-
-template <int N, int IN, bool WIN>
-static hipError_t launch_f64f_o(const SpectraParamsF64& p, int blocks, hipStream_t st, int device)
-{
-    switch (p.out_mode) {
-    case OUT_SUM:
-        return p.rows_f32 ? launch_f64f_k<N, IN, WIN, OUT_SUM, true>(p, blocks, st, device)
-                          : launch_f64f_k<N, IN, WIN, OUT_SUM, false>(p, blocks, st, device);
-    case OUT_DB:
-        return p.rows_f32 ? launch_f64f_k<N, IN, WIN, OUT_DB, true>(p, blocks, st, device)
-                          : launch_f64f_k<N, IN, WIN, OUT_DB, false>(p, blocks, st, device);
-    default: return launch_f64f_k<N, IN, WIN, OUT_PAYLOAD, false>(p, blocks, st, device);
-    }
-}
-
-template <int N, int IN>
-static hipError_t launch_f64f_w(const SpectraParamsF64& p, int blocks, hipStream_t st, int device)
-{
-    return p.window ? launch_f64f_o<N, IN, true>(p, blocks, st, device) : launch_f64f_o<N, IN, false>(p, blocks, st, device);
-}
-
-#define RTLWS_CAT2(a, b) a##b
-#define RTLWS_CAT(a, b) RTLWS_CAT2(a, b)
 
 hipError_t RTLWS_CAT(launch_spectra_f64_fused_, RTLWS_N)(const SpectraParamsF64& p, int in_kind, int blocks,
                                                          hipStream_t st, int device)
 {
-    constexpr int N = RTLWS_N;
-    switch (in_kind) {
-    case IN_CU8: return launch_f64f_w<N, IN_CU8>(p, blocks, st, device);
-    case IN_CS32: return launch_f64f_w<N, IN_CS32>(p, blocks, st, device);
-    case IN_RF32: return launch_f64f_w<N, IN_RF32>(p, blocks, st, device);
-    case IN_CU8_CIC8: return launch_f64f_w<N, IN_CU8_CIC8>(p, blocks, st, device);
-    case IN_CU8_CIC10: return launch_f64f_w<N, IN_CU8_CIC10>(p, blocks, st, device);
-    case IN_CU8_CIC12: return launch_f64f_w<N, IN_CU8_CIC12>(p, blocks, st, device);
-    default: return hipErrorInvalidValue;
-    }
+    return f64f_table(pick, p, in_kind, [&](auto kernel, int threads, size_t lds_bytes) {
+        const hipError_t e = lds_opt_in(kernel, device, lds_bytes);
+        return e != hipSuccess ? e : launch(kernel, dim3(blocks), dim3(threads), lds_bytes, st, p);
+    });
+}
+
+hipError_t RTLWS_CAT(prepare_spectra_f64_fused_, RTLWS_N)(int device)
+{
+    return f64f_table(visit_all, SpectraParamsF64{}, 0, [&](auto kernel, int, size_t lds_bytes) {
+        return lds_opt_in(kernel, device, lds_bytes);
+    });
 }
 
 }  // namespace rtlws

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(N / 32, 2) void spectra_fused_v2(const SpectraParam
 #pragma unroll
                 for (int i = 0; i < 2 * J; ++i) {
                     const float d = o[i];      // (int) truncation toward zero, then clamp; NaN/-inf -> 0
-                    const unsigned m = (d >= 0.0f) ? (d <= 255.0f ? (unsigned)(int)d : 255u) : 0u;
+                    const unsigned m = payload_byte(d);
                     packed |= m << (8 * i);
                 }
                 uint8_t* dst = reinterpret_cast<uint8_t*>(p.out) + g * N + i0;
@@ -305,32 +305,17 @@ __global__ __launch_bounds__(N / 32, 2) void spectra_fused_v2(const SpectraParam
     }
 }
 
-template <int N, bool WIN, int OUT>
-static hipError_t launch_v2_k(const SpectraParams& p, int blocks, hipStream_t st)
-{
-    const size_t lds_bytes = v2_lds_bytes(N);
-    if (p.k_avg == 1)
-        hipLaunchKernelGGL((spectra_fused_v2<N, WIN, OUT, true>), dim3(blocks), dim3(N / 32), lds_bytes, st, p);
-    else
-        hipLaunchKernelGGL((spectra_fused_v2<N, WIN, OUT, false>), dim3(blocks), dim3(N / 32), lds_bytes, st, p);
-    return hipGetLastError();
-}
-
-template <int N, bool WIN>
-static hipError_t launch_v2_o(const SpectraParams& p, int blocks, hipStream_t st)
-{
-    switch (p.out_mode) {
-    case OUT_SUM: return launch_v2_k<N, WIN, OUT_SUM>(p, blocks, st);
-    case OUT_DB: return launch_v2_k<N, WIN, OUT_DB>(p, blocks, st);
-    default: return launch_v2_k<N, WIN, OUT_PAYLOAD>(p, blocks, st);
-    }
-}
-
 hipError_t launch_spectra_fused_v2(const SpectraParams& p, int blocks, hipStream_t st)
 {
-    if (p.n_fft == 2048)
-        return p.window ? launch_v2_o<2048, true>(p, blocks, st) : launch_v2_o<2048, false>(p, blocks, st);
-    return p.window ? launch_v2_o<4096, true>(p, blocks, st) : launch_v2_o<4096, false>(p, blocks, st);
+    return pick(Vals<2048, 4096>{}, p.n_fft, [&](auto n) {
+        return pick(Bools{}, p.window != nullptr, [&](auto win) {
+            return pick(OutModes{}, p.out_mode, [&](auto out) {
+                return pick(Bools{}, p.k_avg == 1, [&](auto kone) {
+                    return launch(&spectra_fused_v2<n, win, out, kone>, dim3(blocks), dim3(n / 32), v2_lds_bytes(n), st, p);
+                });
+            });
+        });
+    });
 }
 
 }  // namespace rtlws
