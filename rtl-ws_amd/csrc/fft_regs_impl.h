@@ -249,3 +249,18 @@ __device__ __forceinline__ void hann_bfly4(f2 e0, f2 e1, f2 o0, f2 o1, const f2 
     a3 = mk(s1.x - s3.y, s1.y + s3.x);   // s1 + i*s3
 }
 
+// ---- the DC-slot rule's broadcast ----
+// lane 63's x in every lane: the DC-slot value of one-wavefront frames, whose bin N-1 is lane 63's
+// (reference src/spectrum.c:25-33; a template so that only the branch of this precision is instantiated)
+template <typename R = real>
+__device__ __forceinline__ R lane63(R x)
+{
+    if constexpr (sizeof(R) == 8) {
+        const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+        const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, 63);
+        const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
+        return __builtin_bit_cast(R, ((unsigned long long)hi << 32) | lo);
+    } else {
+        return __builtin_bit_cast(R, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+    }
+}

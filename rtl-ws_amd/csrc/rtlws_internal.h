@@ -264,6 +264,29 @@ __device__ __forceinline__ unsigned payload_byte(double d) { return (d >= 0.0) ?
 // 10*log10|gain * a / count| (the caller forms the product before count is read, as the kernels always did)
 __device__ __forceinline__ double db_f64(double a, int count) { return 10.0 * log10(a / (double)count); }
 __device__ __forceinline__ unsigned payload_f64(double ga, int count) { return payload_byte(10.0 * log10(fabs(ga / (double)count))); }
+// in f32: 10*log10(x) = 3.0103 * log2(x) on v_log_f32 (1 ulp: <= 1e-5 dB over the f32 range, against the 2e-4 dB the
+// f32 transform itself is held to; log10f() costs six more instructions per value for denormal inputs that a power
+// sum of integer samples never produces).  The dB row value, and the payload's dB value before payload_byte.
+constexpr float DB_PER_LOG2 = 3.01029995663981195f;
+__device__ __forceinline__ float db_f32(float a, float db_offset) { return fmaf(DB_PER_LOG2, __builtin_amdgcn_logf(a), db_offset); }
+__device__ __forceinline__ float payload_db_f32(float a, float lin_gain) { return DB_PER_LOG2 * __builtin_amdgcn_logf(fabsf(a * lin_gain)); }
+
+// ---- row stores ----
+// W consecutive values (W = 1, 2, 4; dst aligned to the W of them) in one nontemporal store: rows are written once
+// and never re-read
+template <typename T, int W>
+__device__ __forceinline__ void store_nt(T* dst, const T (&o)[W])
+{
+    if constexpr (W == 1) {
+        __builtin_nontemporal_store(o[0], dst);
+    } else {
+        typedef T vec __attribute__((ext_vector_type(W)));
+        vec v;
+#pragma unroll
+        for (int i = 0; i < W; ++i) v[i] = o[i];
+        __builtin_nontemporal_store(v, reinterpret_cast<vec*>(dst));
+    }
+}
 
 // ---- launch tables: runtime fields -> one template instantiation ----
 #define RTLWS_CAT2(a, b) a##b

@@ -216,13 +216,8 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
 
         // ---- DC-slot rule (src/spectrum.c:25-33): slot N/2 (bin 0: lane 0, u = 0) takes
         // sum_k (K-k) * P_k[N-1] (bin N-1: lane 63, u = 15)
-        {
-            const unsigned long long b = __builtin_bit_cast(unsigned long long, wdc);
-            const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, 63);
-            const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
-            const double dcv = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-            if (t == 0) acc[0] = dcv;
-        }
+        const double dcv = lane63(wdc);
+        if (t == 0) acc[0] = dcv;
 
         // ---- epilogue + store: slot u holds bin 64 q' + t, q' = rev16(u); fft-shift = flip the top
         // bit of the bin index = q' ^ 8.

@@ -242,10 +242,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
         // ---- DC-slot rule (src/spectrum.c:25-33): slot N/2 (bin 0: thread 0, u = 0) takes
         // sum_k (K-k) * P_k[N-1] (bin N-1: thread T-1, u = 15)
         if constexpr (T == 64) {
-            const unsigned long long b = __builtin_bit_cast(unsigned long long, wdc);
-            const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, 63);
-            const unsigned hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), 63);
-            const double dcv = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+            const double dcv = lane63(wdc);
             if (t == 0) acc[0] = dcv;
         } else {
             double* slot = reinterpret_cast<double*>(ldsd + f64_fused_lds_elems(N) - 1);
@@ -290,18 +287,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
                     if constexpr (OUT == OUT_DB) a = db_f64(a, p.count);
                     o[j] = (float)a;
                 }
-                float* dst = reinterpret_cast<float*>(p.out) + g * N + i0;
-                if constexpr (J == 4) {
-                    typedef float nt_f4 __attribute__((ext_vector_type(4)));
-                    const nt_f4 ov = {o[0], o[1], o[2], o[3]};
-                    __builtin_nontemporal_store(ov, reinterpret_cast<nt_f4*>(dst));
-                } else if constexpr (J == 2) {
-                    typedef float nt_f2 __attribute__((ext_vector_type(2)));
-                    const nt_f2 ov = {o[0], o[1]};
-                    __builtin_nontemporal_store(ov, reinterpret_cast<nt_f2*>(dst));
-                } else {
-                    __builtin_nontemporal_store(o[0], dst);
-                }
+                store_nt(reinterpret_cast<float*>(p.out) + g * N + i0, o);
             }
         } else if constexpr (J == 4) {
             // N = 1024: a lane owns four consecutive bins = 32 bytes = 16-byte pieces A_t | B_t.
@@ -309,7 +295,6 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
             // afterwards one register holds A_0..31 | B_0..31 -- the first 1 KiB of the block, every
             // 16-byte slot once -- and the other A_32..63 | B_32..63, the second KiB (lane l holds
             // slot 2*(l & 31) + (l >> 5) of its KiB).  No LDS, no wait.
-            typedef double nt_d2 __attribute__((ext_vector_type(2)));
             const int slot = 2 * (t & 31) + (t >> 5);
 #pragma unroll
             for (int s = 0; s < R3; ++s) {
@@ -329,10 +314,9 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
                     x[h] = __builtin_bit_cast(double, ((unsigned long long)hi[0] << 32) | lo[0]);
                     y[h] = __builtin_bit_cast(double, ((unsigned long long)hi[1] << 32) | lo[1]);
                 }
-                nt_d2* dst = reinterpret_cast<nt_d2*>(reinterpret_cast<double*>(p.out) + g * N + 256 * (s ^ (R3 / 2)));
-                const nt_d2 vx = {x[0], x[1]}, vy = {y[0], y[1]};
-                __builtin_nontemporal_store(vx, dst + slot);
-                __builtin_nontemporal_store(vy, dst + 64 + slot);
+                double2* dst = reinterpret_cast<double2*>(reinterpret_cast<double*>(p.out) + g * N + 256 * (s ^ (R3 / 2)));
+                store_nt(reinterpret_cast<double*>(dst + slot), x);
+                store_nt(reinterpret_cast<double*>(dst + 64 + slot), y);
             }
         } else {
             // N = 2048 / 4096: a lane owns 2 / 1 consecutive bins per s: every store instruction
@@ -346,14 +330,7 @@ __global__ __launch_bounds__(N / 16, 2) void spectra_f64_fused(const SpectraPara
                     o[j] = acc[j * R3 + s];
                     if constexpr (OUT == OUT_DB) o[j] = db_f64(o[j], p.count);
                 }
-                double* dst = reinterpret_cast<double*>(p.out) + g * N + i0;
-                if constexpr (J == 2) {
-                    typedef double nt_d2 __attribute__((ext_vector_type(2)));
-                    const nt_d2 v2 = {o[0], o[1]};
-                    __builtin_nontemporal_store(v2, reinterpret_cast<nt_d2*>(dst));
-                } else {
-                    __builtin_nontemporal_store(o[0], dst);
-                }
+                store_nt(reinterpret_cast<double*>(p.out) + g * N + i0, o);
             }
         }
     }

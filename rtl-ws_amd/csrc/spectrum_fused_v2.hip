@@ -273,9 +273,8 @@ __global__ __launch_bounds__(N / 32, 2) void spectra_fused_v2(const SpectraParam
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
                     float a = acc[h][j * R3 + s];
-                    constexpr float DB_PER_LOG2 = 3.01029995663981195f;
-                    if constexpr (OUT == OUT_DB) a = fmaf(DB_PER_LOG2, __builtin_amdgcn_logf(a), p.db_offset);
-                    if constexpr (OUT == OUT_PAYLOAD) a = DB_PER_LOG2 * __builtin_amdgcn_logf(fabsf(a * p.lin_gain));
+                    if constexpr (OUT == OUT_DB) a = db_f32(a, p.db_offset);
+                    if constexpr (OUT == OUT_PAYLOAD) a = payload_db_f32(a, p.lin_gain);
                     o[h * J + j] = a;
                 }
             if constexpr (OUT == OUT_PAYLOAD) {
@@ -290,16 +289,7 @@ __global__ __launch_bounds__(N / 32, 2) void spectra_fused_v2(const SpectraParam
                 if constexpr (J == 2) *reinterpret_cast<unsigned*>(dst) = packed;
                 else *reinterpret_cast<uint16_t*>(dst) = (uint16_t)packed;
             } else {
-                float* dst = reinterpret_cast<float*>(p.out) + g * N + i0;
-                if constexpr (J == 2) {
-                    typedef float nt_f4 __attribute__((ext_vector_type(4)));
-                    const nt_f4 ov = {o[0], o[1], o[2], o[3]};
-                    __builtin_nontemporal_store(ov, reinterpret_cast<nt_f4*>(dst));
-                } else {
-                    typedef float nt_f2 __attribute__((ext_vector_type(2)));
-                    const nt_f2 ov = {o[0], o[1]};
-                    __builtin_nontemporal_store(ov, reinterpret_cast<nt_f2*>(dst));
-                }
+                store_nt(reinterpret_cast<float*>(p.out) + g * N + i0, o);
             }
         }
     }
