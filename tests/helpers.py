@@ -38,3 +38,31 @@ def strict_stats(got, ref):
     """(max, 99.9th percentile) of the strict-floor (eps = 1e-9) relative error."""
     e = rel_err(got, ref, EPS_STRICT)
     return float(e.max()), float(np.percentile(e, 99.9))
+
+
+# f32 dB and payload rows (rtlws_spectra_batch's OUT_MEAN_DB / OUT_PAYLOAD_U8) against the f64 oracle's power sums
+# `ref` (rows of K-frame sums).  The f32 error budget in dB of a bin of power p under a row maximum pmax is
+# 4.34 * (2 * 6e-8 * sqrt(pmax / p)) (DESIGN.md, "Error budget"), taken with a 3x margin; the direct-sum kernel
+# (fused=False, O(N^2) f32 accumulation) gets ten times that.
+
+def f32_db_bad(got, ref, K, fused=True):
+    """Mask of the dB values outside the budget, on bins above the strict floor (1e-9 of the row maximum)."""
+    with np.errstate(divide="ignore"):
+        want = 10 * np.log10(ref / K)
+    mx = ref.max(axis=-1, keepdims=True)
+    ok = np.isfinite(want) & (ref > 1e-9 * mx)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        tol_db = np.maximum(3e-4, 4.34 * 4e-7 * np.sqrt(mx / np.maximum(ref, 1e-300)))
+        return ok & (np.abs(got - want) > (tol_db if fused else 10 * tol_db))
+
+
+def f32_payload_bad(got, want, ref, K, gain, fused=True):
+    """Mask of the bytes of one row that differ from the oracle's (`want`, src/cbb_main.c:121-130) other than by one
+    where the f64 dB value sits within the budget of an integer ((int) truncation is discontinuous there)."""
+    diff = got.astype(int) - want.astype(int)
+    g = 10.0 ** (int(gain / 10))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d = 10 * np.log10(np.abs(g * ref / K))
+        tol_db = np.maximum(2e-3, 4.34 * 4e-7 * np.sqrt(ref.max() / np.maximum(ref, 1e-300)))
+        near = np.abs(d - np.round(d)) < (tol_db if fused else 10 * tol_db)
+    return ~((diff == 0) | (near & (np.abs(diff) == 1)))

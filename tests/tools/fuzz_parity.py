@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import rtlws                         # noqa: E402
 from rtlws import synth              # noqa: E402
 from oracle import pyoracle as po    # noqa: E402
-from helpers import rel_err          # noqa: E402
+from helpers import rel_err, f32_db_bad, f32_payload_bad          # noqa: E402
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 budget_s = float(sys.argv[2]) if len(sys.argv) > 2 else 60.0
@@ -67,25 +67,12 @@ while time.time() - t0 < budget_s:
         worst = max(worst, e if fused else 0.0)
         assert e <= tol, (tag, e)
     elif out == "mean_db":
-        with np.errstate(divide="ignore"):
-            want = 10 * np.log10(ref / K)
-        mx = ref.max(axis=1, keepdims=True)
-        ok = np.isfinite(want) & (ref > 1e-9 * mx)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            tol_db = np.maximum(3e-4, 4.34 * 4e-7 * np.sqrt(mx / np.maximum(ref, 1e-300)))
-        bad = ok & (np.abs(got - want) > (tol_db if fused else 10 * tol_db))
-        assert not bad.any(), (tag, float(np.abs(got - want)[bad].max()))
+        bad = f32_db_bad(got, ref, K, fused)
+        assert not bad.any(), (tag, float(np.abs(got - 10 * np.log10(ref / K))[bad].max()))
     else:
         for r in range(rows):
             want = po.spectrum_payload(ref[r], K, gain)
-            diff = got[r].astype(int) - want.astype(int)
-            g = 10.0 ** (int(gain / 10))
-            with np.errstate(divide="ignore", invalid="ignore"):
-                d = 10 * np.log10(np.abs(g * ref[r] / K))
-                # f32 error budget in dB for a bin of power p under a row maximum pmax:
-                # 4.34 * (2 * 6e-8 * sqrt(pmax / p)), with a 3x margin; never below 2e-3
-                tol_db = np.maximum(2e-3, 4.34 * 4e-7 * np.sqrt(ref[r].max() / np.maximum(ref[r], 1e-300)))
-                near = np.abs(d - np.round(d)) < (tol_db if fused else 10 * tol_db)
-            assert np.all((diff == 0) | (near & (np.abs(diff) == 1))), (tag, int(np.abs(diff).max()))
+            bad = f32_payload_bad(got[r], want, ref[r], K, gain, fused)
+            assert not bad.any(), (tag, int(np.abs(got[r].astype(int) - want.astype(int)).max()))
     n_cases += 1
 print("fuzz seed %d: %d cases ok in %.1f s, worst fused power rel err %.2e" % (seed, n_cases, time.time() - t0, worst))
