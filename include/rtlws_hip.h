@@ -128,8 +128,8 @@ int rtlws_memset_dev(rtlws_engine* e, void* dst_dev, int value, size_t bytes, vo
 int rtlws_stream_sync(rtlws_engine* e, void* stream);
 
 /* Additional in-order queues on the engine's device (hipStreamNonBlocking), for callers that
- * overlap copies with kernels: rtlws_stream.h runs copy-in, transform and copy-out of
- * consecutive chunks on three of them, ordered by events.  NULL on failure. */
+ * overlap copies with kernels: rtlws_stream.h keeps a chunk's copy-in, transform and copy-out on
+ * one of them and sends consecutive chunks to different ones, no events between them.  NULL on failure. */
 void* rtlws_queue_create(rtlws_engine* e);
 void rtlws_queue_destroy(rtlws_engine* e, void* queue);
 /* Work enqueued on `stream` after this call starts only once `ev` (recorded earlier, on any

@@ -92,10 +92,24 @@ static void decimate(const cmplx_u8* signal, int len)
     rf_decimator_decimate_cmplx_u8(g_decim, signal, len);
 }
 
+/* publish, with g_mu held: `sums` (count frames behind it) becomes what the server thread reads, and the
+ * buffer it read until now is handed back for reuse -- a swap instead of the reference's 8 KiB memcpy
+ * (src/cbb_main.c:61-69).  cbb_get_spectrum_payload takes g_mu before it reads anything the flag announces. */
+static double* publish(double* sums, int count)
+{
+    double* prev = g_d_pub;
+    g_d_pub = sums;
+    g_pub_count = count;
+    g_last_est_ms = now_ms();                                     /* :61 */
+    FLAG_SET(1);                                                  /* :62 */
+    return prev;
+}
+
 /* callback #3 (reference src/cbb_main.c:40-70) */
 static void estimate_spectrum(const cmplx_u8* signal, int len)
 {
     int blocks = len / FFT_POINTS;
+    int failed = 0;
     rtlws_spectra_desc d;
 
     const int due = now_ms() >= g_last_est_ms + SPECTRUM_EST_MS;  /* :46-47 */
@@ -117,48 +131,23 @@ static void estimate_spectrum(const cmplx_u8* signal, int len)
         if (g_iq_used[slot]) rtlws_event_sync(g_iq_done[slot]);   /* copy of 2 estimates ago */
         memcpy(g_h_iq[slot], signal, bytes);
         g_iq_used[slot] = 1;
-        if (rtlws_copy_h2d(g_eng, g_d_iq, g_h_iq[slot], bytes, NULL) ||
-            rtlws_event_record(g_iq_done[slot], g_eng, NULL) ||
-            rtlws_spectra_batch_f64(g_eng, &d, g_d_iq, blocks, g_d_work, NULL) ||
-            (g_welch && rtlws_welch_accumulate_f64(g_eng, g_d_acc, g_d_work, FFT_POINTS,
-                                                   g_acc_count + blocks, g_d_b, NULL))) {
-            fprintf(stderr, "rtlws: estimate_spectrum: device failure: %s\n", rtlws_last_error());
-            pthread_mutex_unlock(&g_mu);
-            return;                                               /* :54-58 */
-        }
-        g_acc_count += blocks;
+        failed = rtlws_copy_h2d(g_eng, g_d_iq, g_h_iq[slot], bytes, NULL) ||
+                 rtlws_event_record(g_iq_done[slot], g_eng, NULL) ||
+                 rtlws_spectra_batch_f64(g_eng, &d, g_d_iq, blocks, g_d_work, NULL) ||
+                 (g_welch && rtlws_welch_accumulate_f64(g_eng, g_d_acc, g_d_work, FFT_POINTS,
+                                                        g_acc_count + blocks, g_d_b, NULL));
+        if (!failed) g_acc_count += blocks;
     }
-    if (g_welch) {
-        if (!due) {                              /* folded in; the interval is still open */
-            pthread_mutex_unlock(&g_mu);
-            return;
-        }
-        /* close the interval: fix slot N/2 for the whole sequence, publish, start over */
-        if (rtlws_welch_finish_f64(g_eng, g_d_acc, FFT_POINTS, g_acc_count, g_d_b, NULL)) {
-            fprintf(stderr, "rtlws: estimate_spectrum: device failure: %s\n", rtlws_last_error());
-            pthread_mutex_unlock(&g_mu);
-            return;
-        }
-        {
-            double* t = g_d_pub;
-            g_d_pub = g_d_acc;
-            g_d_acc = t;
-            g_pub_count = (int)g_acc_count;
-            g_acc_count = 0;
-            rtlws_memset_dev(g_eng, g_d_acc, 0, FFT_POINTS * sizeof(double), NULL);
-        }
-        g_last_est_ms = now_ms();
-        FLAG_SET(1);
-        pthread_mutex_unlock(&g_mu);
-        return;
-    }
-    g_last_est_ms = now_ms();                                     /* :61 */
-    FLAG_SET(1);                                                  /* :62 */
-    {   /* publish: swap instead of the reference's 8 KiB memcpy (:64-69) */
-        double* t = g_d_pub;
-        g_d_pub = g_d_work;
-        g_d_work = t;
-        g_pub_count = blocks;
+    if (!failed && g_welch && due)               /* close the interval: fix slot N/2 for the whole sequence */
+        failed = rtlws_welch_finish_f64(g_eng, g_d_acc, FFT_POINTS, g_acc_count, g_d_b, NULL);
+    if (failed) {                                /* nothing is published (:54-58) */
+        fprintf(stderr, "rtlws: estimate_spectrum: device failure: %s\n", rtlws_last_error());
+    } else if (!g_welch) {
+        g_d_work = publish(g_d_work, blocks);
+    } else if (due) {                            /* publish, start over (not due: the interval is still open) */
+        g_d_acc = publish(g_d_acc, (int)g_acc_count);
+        g_acc_count = 0;
+        rtlws_memset_dev(g_eng, g_d_acc, 0, FFT_POINTS * sizeof(double), NULL);
     }
     pthread_mutex_unlock(&g_mu);
 }

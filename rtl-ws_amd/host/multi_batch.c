@@ -16,8 +16,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
+#include "host_util.h"
 #include "rtlws_topo.h"
 
 enum { CMD_NONE = 0, CMD_INIT, CMD_UPLOAD, CMD_RUN, CMD_DOWNLOAD, CMD_EXIT };
@@ -61,7 +61,6 @@ struct rtlws_multi {
     char err[320];             /* "shard g (device d): ..." of the first failing shard of the last command */
 };
 
-/* the text of the last failed rtlws_multi_open (there is no handle to keep it in) */
 /* why the calling thread's last rtlws_multi_open failed: per thread, like rtlws_last_error() */
 static __thread char g_open_err[352];
 
@@ -77,39 +76,12 @@ int rtlws_multi_partition(long nframes, int k_avg, int shards, int g, long* firs
     return 0;
 }
 
-static size_t frame_bytes_of(const rtlws_spectra_desc* d)
-{
-    const size_t r = d->cic_r > 1 ? (size_t)d->cic_r : 1u;
-    const size_t per = d->input == RTLWS_IN_CS32 ? 8u : d->input == RTLWS_IN_RF32 ? 4u : 2u * r;
-    return per * (size_t)d->n_fft;
-}
-
-static size_t row_bytes_of(const rtlws_spectra_desc* d, int f64)
-{
-    const size_t e = d->output == RTLWS_OUT_PAYLOAD_U8 ? 1u
-                     : (f64 && !(d->flags & RTLWS_FLAG_ROWS_F32)) ? 8u : 4u;
-    return e * (size_t)d->n_fft;
-}
-
-static double now_ms(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-}
-
 /* a failing call happened on THIS (worker) thread: its text is in this thread's rtlws_last_error() and
  * nowhere the caller can see -- keep it in the shard */
 static int fail(struct shard* s, const char* what, int rc)
 {
     snprintf(s->err, sizeof s->err, "%s: %s", what, rtlws_last_error());
     return rc ? rc : -3;
-}
-
-static int launch_once(rtlws_multi* m, struct shard* s)
-{
-    return m->f64 ? rtlws_spectra_batch_f64(s->eng, &m->desc, s->d_in, s->frames, s->d_out, NULL)
-                  : rtlws_spectra_batch(s->eng, &m->desc, s->d_in, s->frames, s->d_out, NULL);
 }
 
 /* pin, then create everything this shard owns -- in that order */
@@ -218,7 +190,8 @@ static int shard_run(struct shard* s, int launches)
     const double t0 = now_ms();
     s->event_ms = 0.0;
     rc = rtlws_event_record(s->ev0, s->eng, NULL);
-    for (i = 0; i < launches && rc == 0; i++) rc = launch_once(m, s);
+    for (i = 0; i < launches && rc == 0; i++)
+        rc = rtlws_launch_desc(s->eng, &m->desc, m->f64, s->d_in, s->frames, s->d_out, NULL);
     if (rc == 0) rc = rtlws_event_record(s->ev1, s->eng, NULL);
     if (rc == 0) rc = rtlws_stream_sync(s->eng, NULL);
     if (rc == 0) s->event_ms = (double)rtlws_event_elapsed_ms(s->ev0, s->ev1);
@@ -301,8 +274,8 @@ rtlws_multi* rtlws_multi_open(int n_shards, const int* device_ids, const rtlws_s
     m->f64 = f64 != 0;
     m->desc = *desc;
     m->nframes = nframes - nframes % desc->k_avg;        /* whole K-groups */
-    m->frame_bytes = frame_bytes_of(desc);
-    m->row_bytes = row_bytes_of(desc, m->f64);
+    m->frame_bytes = rtlws_frame_bytes(desc);
+    m->row_bytes = rtlws_row_bytes(desc, m->f64);
     pthread_mutex_init(&m->mu, NULL);
     pthread_cond_init(&m->cv_cmd, NULL);
     pthread_cond_init(&m->cv_done, NULL);

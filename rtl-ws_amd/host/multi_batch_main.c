@@ -20,28 +20,12 @@
  *   --bus-ids a,b,...      (with --plan-only) bus id of device 0, 1, ...: "0000:05:00.0,0000:15:00.0"
  *   --sysfs-root DIR       (with --plan-only) read NUMA nodes and cpusets under DIR instead of /sys
  */
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "rtlws_multi.h"
-
-static void synth_iq(unsigned char* buf, long samples)
-{
-    unsigned x = 2463534242u;
-    long i;
-    for (i = 0; i < samples; i++) {      /* tone + noise, quantised like an RTL2832U sample */
-        const double ph = 2.0 * 3.14159265358979 * 0.1373 * (double)i;
-        double re, im;
-        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
-        re = 0.6 * cos(ph) + ((double)(x & 0xffff) / 65536.0 - 0.5) * 0.2;
-        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
-        im = 0.6 * sin(ph) + ((double)(x & 0xffff) / 65536.0 - 0.5) * 0.2;
-        buf[2 * i] = (unsigned char)fmin(255.0, fmax(0.0, floor(re * 128.0 + 128.5)));
-        buf[2 * i + 1] = (unsigned char)fmin(255.0, fmax(0.0, floor(im * 128.0 + 128.5)));
-    }
-}
+#include "driver_util.h"
 
 int main(int argc, char** argv)
 {
@@ -74,16 +58,10 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--window") && i + 1 < argc) window = !strcmp(argv[++i], "hann") ? RTLWS_WIN_HANN : RTLWS_WIN_RECT;
         else if (!strcmp(argv[i], "--precision") && i + 1 < argc) {
             precision = argv[++i];
-            if (!strcmp(precision, "f32")) { f64 = 0; flags = 0; }
-            else if (!strcmp(precision, "f64")) { f64 = 1; flags = 0; }
-            else if (!strcmp(precision, "f64c_f32o")) { f64 = 1; flags = RTLWS_FLAG_ROWS_F32; }
-            else { fprintf(stderr, "--precision f32|f64|f64c_f32o\n"); return 2; }
+            if (parse_precision(precision, &f64, &flags)) return 2;      /* f64 goes to rtlws_multi_open */
         } else if (!strcmp(argv[i], "--output") && i + 1 < argc) {
             output_name = argv[++i];
-            if (!strcmp(output_name, "f32")) output = RTLWS_OUT_POWER_SUM;
-            else if (!strcmp(output_name, "db")) output = RTLWS_OUT_MEAN_DB;
-            else if (!strcmp(output_name, "payload")) output = RTLWS_OUT_PAYLOAD_U8;
-            else { fprintf(stderr, "--output f32|db|payload\n"); return 2; }
+            if (parse_output(output_name, &output)) return 2;
         } else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if (per_dev < 1 || per_dev > 4) { fprintf(stderr, "--shards-per-device 1..4\n"); return 2; }
@@ -94,22 +72,10 @@ int main(int argc, char** argv)
                frames, frames - frames % k, k, devices);
         for (g = 0; g < devices; g++) {
             long first, count;
-            rtlws_topo_info t;
-            char one[32];
-            const char* bus = NULL;
             rtlws_multi_partition(frames, k, devices, g, &first, &count);
-            if (bus_ids) {                 /* the g-th comma-separated entry */
-                const char* p = bus_ids;
-                int skip = g;
-                size_t n;
-                while (skip > 0 && (p = strchr(p, ',')) != NULL) { ++p; --skip; }
-                n = p ? strcspn(p, ",") : 0;
-                if (p && n > 0 && n < sizeof one) { memcpy(one, p, n); one[n] = 0; bus = one; }
-                else bus = "";
-            }
-            if (rtlws_topo_describe(bus ? -1 : g, bus, sysfs_root, &t) != 0) memset(&t, 0, sizeof t), t.numa_node = -1;
-            printf("%s{\"device\": %d, \"first_frame\": %ld, \"frames\": %ld, \"bus_id\": \"%s\", \"numa_node\": %d, "
-                   "\"cpus\": %d, \"cpulist\": \"%s\"}", g ? ", " : "", g, first, count, t.bus_id, t.numa_node, t.ncpus, t.cpulist);
+            printf("%s{\"device\": %d, \"first_frame\": %ld, \"frames\": %ld, ", g ? ", " : "", g, first, count);
+            print_device_topology(g, bus_ids, sysfs_root);
+            printf("}");
         }
         printf("]}\n");
         return 0;
@@ -135,7 +101,7 @@ int main(int argc, char** argv)
         const size_t fb = rtlws_multi_frame_bytes(m);
         host = (unsigned char*)malloc((size_t)frames * fb + 1);
         if (!host) return 3;
-        synth_iq(host, (long)((size_t)frames * fb / 2));
+        synth_iq(host, (long)((size_t)frames * fb / 2), 2463534242u, 0.1373);   /* tone + noise */
     }
     st = (rtlws_multi_shard_stats*)calloc((size_t)n, sizeof(*st));
     rc = rtlws_multi_upload(m, host);

@@ -25,6 +25,7 @@
 #include <time.h>
 
 #include "rtlws_stream.h"
+#include "driver_util.h"
 
 #define BUF_SAMPLES 131072
 
@@ -65,9 +66,7 @@ static void* producer_main(void* arg)
     struct producer* p = (struct producer*)arg;
     const long frames = (long)p->chunk_buffers * (BUF_SAMPLES / p->desc.n_fft);
     unsigned char* buf = (unsigned char*)malloc((size_t)2 * BUF_SAMPLES * (size_t)p->chunk_buffers);
-    unsigned x = 2463534242u + 977u * (unsigned)p->id;
     double t0, next;
-    long i;
     /* this thread feeds device p->device for the rest of its life: stay on that device's NUMA node, so the
      * buffer below is first touched there and every push's memcpy into a ring slot is node-local */
     {
@@ -75,16 +74,8 @@ static void* producer_main(void* arg)
         rtlws_topo_describe(p->device, NULL, NULL, &t);
         (void)rtlws_topo_pin_thread(&t);
     }
-    for (i = 0; i < (long)BUF_SAMPLES * p->chunk_buffers; i++) {      /* tone + noise, different per stream */
-        double ph = 2.0 * 3.14159265358979 * (0.05 + 0.1 * p->id) * (double)i;
-        double re, im;
-        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
-        re = 0.6 * cos(ph) + ((double)(x & 0xffff) / 65536.0 - 0.5) * 0.2;
-        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
-        im = 0.6 * sin(ph) + ((double)(x & 0xffff) / 65536.0 - 0.5) * 0.2;
-        buf[2 * i] = (unsigned char)fmin(255.0, fmax(0.0, floor(re * 128.0 + 128.5)));
-        buf[2 * i + 1] = (unsigned char)fmin(255.0, fmax(0.0, floor(im * 128.0 + 128.5)));
-    }
+    /* tone + noise, different per stream */
+    synth_iq(buf, (long)BUF_SAMPLES * p->chunk_buffers, 2463534242u + 977u * (unsigned)p->id, 0.05 + 0.1 * p->id);
     p->st = rtlws_stream_open_q(p->device, &p->desc, frames, 4, p->queues, on_rows, p);
     if (!p->st) { fprintf(stderr, "stream %d: open failed: %s\n", p->id, rtlws_last_error()); free(buf); return NULL; }
     rtlws_stream_topology(p->st, &p->topo, &p->cpus_pinned);
@@ -118,7 +109,7 @@ int main(int argc, char** argv)
     const char* precision = "f32";
     const char* bus_ids = NULL;
     const char* sysfs_root = NULL;
-    int flags = 0;
+    int f64 = 0, flags = 0;
     double seconds = 3.0, rate = 2400000.0;
     struct producer* ps;
     pthread_t* th;
@@ -139,17 +130,12 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) devices_override = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--precision") && i + 1 < argc) {
             precision = argv[++i];
-            if (!strcmp(precision, "f32")) flags = 0;
-            else if (!strcmp(precision, "f64")) flags = RTLWS_FLAG_F64;
-            else if (!strcmp(precision, "f64c_f32o")) flags = RTLWS_FLAG_F64 | RTLWS_FLAG_ROWS_F32;
-            else { fprintf(stderr, "--precision f32|f64|f64c_f32o\n"); return 2; }
+            if (parse_precision(precision, &f64, &flags)) return 2;
+            if (f64) flags |= RTLWS_FLAG_F64;         /* a stream's arithmetic is in its desc.flags (rtlws_stream.h) */
         }
         else if (!strcmp(argv[i], "--output") && i + 1 < argc) {
             output_name = argv[++i];
-            if (!strcmp(output_name, "f32")) output = RTLWS_OUT_POWER_SUM;
-            else if (!strcmp(output_name, "db")) output = RTLWS_OUT_MEAN_DB;
-            else if (!strcmp(output_name, "payload")) output = RTLWS_OUT_PAYLOAD_U8;
-            else { fprintf(stderr, "--output f32|db|payload\n"); return 2; }
+            if (parse_output(output_name, &output)) return 2;
         }
     }
     if (streams < 1 || chunk_buffers < 1) { fprintf(stderr, "bad --streams / --chunk-buffers\n"); return 2; }
@@ -159,21 +145,9 @@ int main(int argc, char** argv)
         for (i = 0; i < streams; i++) printf("%s%d", i ? ", " : "", rtlws_stream_device_for(i, devices_override));
         printf("], \"device_topology\": [");
         for (i = 0; i < devices_override; i++) {
-            rtlws_topo_info t;
-            char one[32];
-            const char* bus = NULL;
-            if (bus_ids) {                 /* the i-th comma-separated entry */
-                const char* p = bus_ids;
-                int skip = i;
-                size_t n;
-                while (skip > 0 && (p = strchr(p, ',')) != NULL) { ++p; --skip; }
-                n = p ? strcspn(p, ",") : 0;
-                if (p && n > 0 && n < sizeof one) { memcpy(one, p, n); one[n] = 0; bus = one; }
-                else bus = "";
-            }
-            if (rtlws_topo_describe(bus ? -1 : i, bus, sysfs_root, &t) != 0) { memset(&t, 0, sizeof t); t.numa_node = -1; }
-            printf("%s{\"device\": %d, \"bus_id\": \"%s\", \"numa_node\": %d, \"cpus\": %d, \"cpulist\": \"%s\"}",
-                   i ? ", " : "", i, t.bus_id, t.numa_node, t.ncpus, t.cpulist);
+            printf("%s{\"device\": %d, ", i ? ", " : "", i);
+            print_device_topology(i, bus_ids, sysfs_root);
+            printf("}");
         }
         printf("]}\n");
         return 0;

@@ -23,11 +23,8 @@
 struct spectrum {
     int N;
     rtlws_engine* eng;
-    void* d_in;       /* N * 8 bytes: large enough for cmplx_s32 (NULL in zero-copy mode) */
-    double* d_out;    /* N doubles (NULL in zero-copy mode) */
-    void* h_in;       /* pinned */
-    double* h_out;    /* pinned */
-    int zero_copy;
+    void* h_in;       /* pinned, N * 8 bytes: large enough for cmplx_s32 */
+    double* h_out;    /* pinned, N doubles */
 };
 
 struct spectrum* spectrum_alloc(int N)
@@ -50,17 +47,9 @@ struct spectrum* spectrum_alloc(int N)
         free(s);
         return NULL;
     }
-    {
-        const char* z = getenv("RTLWS_DROPIN_ZEROCOPY");
-        s->zero_copy = !(z && z[0] == '0');
-    }
-    if (!s->zero_copy) {             /* device staging exists only in the two-copies mode */
-        s->d_in = rtlws_dev_alloc(s->eng, (size_t)N * sizeof(cmplx_s32));
-        s->d_out = (double*)rtlws_dev_alloc(s->eng, (size_t)N * sizeof(double));
-    }
     s->h_in = rtlws_pinned_alloc((size_t)N * sizeof(cmplx_s32));
     s->h_out = (double*)rtlws_pinned_alloc((size_t)N * sizeof(double));
-    if ((!s->zero_copy && (!s->d_in || !s->d_out)) || !s->h_in || !s->h_out) {
+    if (!s->h_in || !s->h_out) {
         fprintf(stderr, "rtlws: spectrum_alloc: %s\n", rtlws_last_error());
         spectrum_free(s);
         return NULL;
@@ -89,13 +78,8 @@ static int add_frame(struct spectrum* s, const void* src, size_t sample_bytes, i
     memcpy(s->h_in, src, (size_t)N * sample_bytes);
     /* One frame per call: the kernel reads the frame from, and stores the row into, the pinned
      * (device-mapped) staging buffers itself -- one launch and one synchronisation per call
-     * instead of two copies around them (RTLWS_DROPIN_ZEROCOPY=0: the copies; A/B). */
-    if (s->zero_copy
-            ? (rtlws_spectra_batch_f64(s->eng, &d, s->h_in, 1, s->h_out, NULL) || rtlws_stream_sync(s->eng, NULL))
-            : (rtlws_copy_h2d(s->eng, s->d_in, s->h_in, (size_t)N * sample_bytes, NULL) ||
-               rtlws_spectra_batch_f64(s->eng, &d, s->d_in, 1, s->d_out, NULL) ||
-               rtlws_copy_d2h(s->eng, s->h_out, s->d_out, (size_t)N * sizeof(double), NULL) ||
-               rtlws_stream_sync(s->eng, NULL))) {
+     * instead of two copies around them. */
+    if (rtlws_spectra_batch_f64(s->eng, &d, s->h_in, 1, s->h_out, NULL) || rtlws_stream_sync(s->eng, NULL)) {
         fprintf(stderr, "rtlws: spectrum_add: device failure: %s\n", rtlws_last_error());
         return -3;
     }
@@ -130,10 +114,6 @@ int spectrum_add_real_f32(struct spectrum* s, const float* src, double* power_sp
 void spectrum_free(struct spectrum* s)
 {
     if (!s) return;
-    if (s->eng) {
-        rtlws_dev_free(s->eng, s->d_in);
-        rtlws_dev_free(s->eng, s->d_out);
-    }
     rtlws_pinned_free(s->h_in);
     rtlws_pinned_free(s->h_out);
     rtlws_engine_destroy(s->eng);

@@ -28,8 +28,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
 
+#include "host_util.h"
 #include "topology.h"
 
 enum { SLOT_FREE = 0, SLOT_IN_FLIGHT = 1 };
@@ -78,40 +78,13 @@ int rtlws_stream_device_for(int stream_index, int device_count)
     return stream_index % device_count;
 }
 
-static double now_ms(void)
-{
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (double)ts.tv_sec * 1e3 + (double)ts.tv_nsec * 1e-6;
-}
-
-static size_t sample_bytes(const rtlws_spectra_desc* d)
-{
-    const size_t r = d->cic_r > 1 ? (size_t)d->cic_r : 1u;
-    switch (d->input) {
-    case RTLWS_IN_CS32: return 8;
-    case RTLWS_IN_RF32: return 4;
-    default: return 2 * r;
-    }
-}
-
-/* bytes of one output value: payload bytes, f64 rows (RTLWS_FLAG_F64 without
- * RTLWS_FLAG_ROWS_F32), f32 rows otherwise */
-static size_t out_elem_bytes(const rtlws_spectra_desc* d)
-{
-    if (d->output == RTLWS_OUT_PAYLOAD_U8) return 1;
-    return ((d->flags & RTLWS_FLAG_F64) && !(d->flags & RTLWS_FLAG_ROWS_F32)) ? 8 : 4;
-}
-
 /* copy in, transform, copy out, mark: in program order on this slot's queue */
 static int enqueue_chunk(rtlws_stream* s, struct slot* sl)
 {
     const void* in = s->zero_copy_in ? sl->h_in : sl->d_in;
     void* out = s->zero_copy_out ? sl->h_out : sl->d_out;
     return (!s->zero_copy_in && rtlws_copy_h2d(s->eng, sl->d_in, sl->h_in, s->in_bytes, sl->q)) ||
-           ((s->desc.flags & RTLWS_FLAG_F64)      /* the reference's arithmetic (src/spectrum.c:54-60,21,28) */
-                ? rtlws_spectra_batch_f64(s->eng, &s->desc, in, s->frames_per_chunk, out, sl->q)
-                : rtlws_spectra_batch(s->eng, &s->desc, in, s->frames_per_chunk, out, sl->q)) ||
+           rtlws_launch_desc(s->eng, &s->desc, s->desc.flags & RTLWS_FLAG_F64, in, s->frames_per_chunk, out, sl->q) ||
            (!s->zero_copy_out && rtlws_copy_d2h(s->eng, sl->h_out, sl->d_out, s->out_bytes, sl->q)) ||
            rtlws_event_record(sl->done, s->eng, sl->q);
 }
@@ -176,30 +149,6 @@ rtlws_stream* rtlws_stream_open(int device, const rtlws_spectra_desc* desc, long
 
 static rtlws_stream* open_pinned(int device, const rtlws_spectra_desc* desc, long frames_per_chunk,
                                  int ring_slots, int queues, rtlws_stream_callback cb, void* user,
-                                 const rtlws_topo_info* topo, int cpus_pinned);
-
-rtlws_stream* rtlws_stream_open_q(int device, const rtlws_spectra_desc* desc, long frames_per_chunk,
-                                  int ring_slots, int queues, rtlws_stream_callback cb, void* user)
-{
-    rtlws_stream* s;
-    rtlws_topo_info topo;
-    cpu_set_t saved;
-    int have_saved = 0, pinned;
-    if (!desc || rtlws_spectra_kernel_kind(desc) == 0 || frames_per_chunk <= 0 ||
-        frames_per_chunk % desc->k_avg || ring_slots < 2 || queues < 1 || queues > 8 || queues > ring_slots)
-        return NULL;
-    /* everything below -- the pinned slots' allocation and first touch, the warm start, the worker thread's
-     * creation (a new thread inherits its creator's mask) -- happens next to the device; the caller gets its
-     * own mask back on every way out */
-    rtlws_topo_describe(device, NULL, NULL, &topo);
-    pinned = rtlws_topo_pin_save(&topo, &saved, &have_saved);
-    s = open_pinned(device, desc, frames_per_chunk, ring_slots, queues, cb, user, &topo, pinned > 0 ? pinned : 0);
-    rtlws_topo_restore(&saved, have_saved);
-    return s;
-}
-
-static rtlws_stream* open_pinned(int device, const rtlws_spectra_desc* desc, long frames_per_chunk,
-                                 int ring_slots, int queues, rtlws_stream_callback cb, void* user,
                                  const rtlws_topo_info* topo, int cpus_pinned)
 {
     rtlws_stream* s;
@@ -213,8 +162,8 @@ static rtlws_stream* open_pinned(int device, const rtlws_spectra_desc* desc, lon
     s->desc = *desc;
     s->frames_per_chunk = frames_per_chunk;
     s->rows_per_chunk = frames_per_chunk / desc->k_avg;
-    s->in_bytes = (size_t)frames_per_chunk * (size_t)desc->n_fft * sample_bytes(desc);
-    s->out_bytes = (size_t)s->rows_per_chunk * (size_t)desc->n_fft * out_elem_bytes(desc);
+    s->in_bytes = (size_t)frames_per_chunk * rtlws_frame_bytes(desc);
+    s->out_bytes = (size_t)s->rows_per_chunk * rtlws_row_bytes(desc, desc->flags & RTLWS_FLAG_F64);
     s->nslots = ring_slots;
     s->cb = cb;
     s->user = user;
@@ -287,6 +236,26 @@ static rtlws_stream* open_pinned(int device, const rtlws_spectra_desc* desc, lon
     pthread_mutex_lock(&s->mu);
     while (!s->worker_ready) pthread_cond_wait(&s->cv_free, &s->mu);
     pthread_mutex_unlock(&s->mu);
+    return s;
+}
+
+rtlws_stream* rtlws_stream_open_q(int device, const rtlws_spectra_desc* desc, long frames_per_chunk,
+                                  int ring_slots, int queues, rtlws_stream_callback cb, void* user)
+{
+    rtlws_stream* s;
+    rtlws_topo_info topo;
+    cpu_set_t saved;
+    int have_saved = 0, pinned;
+    if (!desc || rtlws_spectra_kernel_kind(desc) == 0 || frames_per_chunk <= 0 ||
+        frames_per_chunk % desc->k_avg || ring_slots < 2 || queues < 1 || queues > 8 || queues > ring_slots)
+        return NULL;
+    /* everything below -- the pinned slots' allocation and first touch, the warm start, the worker thread's
+     * creation (a new thread inherits its creator's mask) -- happens next to the device; the caller gets its
+     * own mask back on every way out */
+    rtlws_topo_describe(device, NULL, NULL, &topo);
+    pinned = rtlws_topo_pin_save(&topo, &saved, &have_saved);
+    s = open_pinned(device, desc, frames_per_chunk, ring_slots, queues, cb, user, &topo, pinned > 0 ? pinned : 0);
+    rtlws_topo_restore(&saved, have_saved);
     return s;
 }
 

@@ -183,7 +183,9 @@ def test_void_entry_points_do_not_kill_the_host_without_a_gpu(built):
 
 def _own_call_graph(lib):
     """{function: set(call targets)} of a shared library's own .text (objdump -d; direct calls and
-    tail jumps to named symbols; PLT stubs keep their `name@plt` spelling)."""
+    tail jumps to named symbols).  A call from one exported function to another goes through the PLT:
+    `name@plt` is resolved to `name` when the library itself defines it, so that such an edge is followed;
+    PLT stubs of other libraries' functions keep their `name@plt` spelling."""
     import subprocess
     txt = subprocess.run(["objdump", "-d", "--no-show-raw-insn", "-j", ".text", lib], capture_output=True, text=True,
                          check=True).stdout
@@ -199,6 +201,8 @@ def _own_call_graph(lib):
         m = re.search(r"\b(?:call|jmp|j[a-z]+)\s+[0-9a-f]+ <([^>+]+)(?:\+0x[0-9a-f]+)?>", line)
         if m and m.group(1) != cur:
             graph[cur].add(m.group(1))
+    for f, targets in graph.items():
+        graph[f] = {t[:-4] if t.endswith("@plt") and t[:-4] in graph else t for t in targets}
     return graph
 
 
