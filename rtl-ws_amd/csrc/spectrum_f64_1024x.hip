@@ -12,12 +12,20 @@
 // and does the radix-4 FIRST, where the data are still the 8-bit samples:
 //   pass 0  n = 256 a + m: lane t loads x[64 j + t], j < 16 (one 128-byte line per wave-instruction,
 //           as everywhere), i.e. a = j / 4 and m = 64 b + t with b = j % 4.  y_p[m] = sum_a x[256a+m]
-//           (-i)^(a p) is exact INTEGER arithmetic on packed int16 (re, im) pairs (|y| <= 1020):
-//           v_pk_add_i16 / v_pk_sub_i16, 11 instructions per b.
-//   cross-row transpose  the 256-point transform p wants m = c + 16 r on lane (p, c): the 4 x 4
-//           exchange (lane row t / 16  <->  index p) of ONE dword per value is two
-//           v_permlane16_swap + two v_permlane32_swap per b -- 16 VALU instructions per frame, no LDS.
-//           Lane (row p, column c) then holds y_p[c + 16 r], r = 4 b + g, r = 0 .. 15 in order.
+//           (-i)^(a p) is exact INTEGER arithmetic (|y| <= 1020), and
+//   cross-row transpose  the 256-point transform p wants m = c + 16 r on lane (p, c): a 4 x 4
+//           exchange (lane row t / 16  <->  index p).  Lane (row p, column c) then holds
+//           y_p[c + 16 r], r = 4 b + g, r = 0 .. 15 in order.
+//           K = 1 instantiations: both at once on the MATRIX pipe.  The coefficients (-i)^(a p) act on
+//           (re, im) as 0 / +-1, so the radix-4 is a 16 x 32 int8 matrix A (two constants per lane: real
+//           and imaginary parts) times the lane's own eight sample bytes of one b, and the operand /
+//           result lane maps of v_mfma_i32_16x16x32_i8 ARE the exchange: 8 v_perm_b32 (2-byte loads ->
+//           dwords) + 8 v_xor_b32 (offset-binary -> signed) + 8 MFMAs per frame, results int32 in pass
+//           A's registers and lanes, the offset 512 (1 + i) of y_0 put back through the C operand so that
+//           every integer is the vector form's (rows bit-identical: tests/test_f64_1024x_digest_gpu.py).
+//           K > 1 instantiations (256 VGPRs, no room for the result quads): on the vector pipe -- packed
+//           int16 (re, im) pairs, v_pk_add_u16 / v_pk_sub_i16, 11 instructions per b; two
+//           v_permlane16_swap + two v_permlane32_swap of ONE dword per value per b; 32 sign extensions.
 //   pass A  the twiddle owed, W_1024^(p m) = W_1024^(p c) (W_64^p)^r, is a lane constant times a
 //           geometric sequence in the register index: the radix-16 over r absorbs the sequence in
 //           fused-multiply-add form (fft_regs_impl.h "last pass": 8 (cos, tan) pairs per lane, 192
@@ -43,6 +51,22 @@ namespace rtlws {
 using namespace f64;
 
 typedef short pk_i16 __attribute__((ext_vector_type(2)));      // (re, im) of one integer point
+typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// Row p of the radix-4 as an int8 A operand: eight bytes, element 2 a + ri = the coefficient of x[a].re (ri = 0) /
+// x[a].im (ri = 1) in the real (im = false) or imaginary part of x[a] (-i)^(a p)
+constexpr long radix4_coef(int p, bool im)
+{
+    unsigned long v = 0;
+    for (int a = 0; a < 4; ++a) {
+        const int e = (a * p) & 3;                                          // (cr, ci) = (-i)^e
+        const int cr = e == 0 ? 1 : e == 2 ? -1 : 0, ci = e == 1 ? -1 : e == 3 ? 1 : 0;
+        v |= (unsigned long)(unsigned char)(im ? ci : cr) << (16 * a);
+        v |= (unsigned long)(unsigned char)(im ? cr : -ci) << (16 * a + 8);
+    }
+    return (long)v;
+}
 
 // V_PERMLANE16_SWAP: odd rows (16 lanes) of a <-> even rows of b; V_PERMLANE32_SWAP: upper half of a
 // <-> lower half of b (tools/permlane_probe.hip)
@@ -101,13 +125,44 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
         }
     };
 
-    unsigned raw[16];
+    // The front end (radix-4 + cross-row transpose) on the matrix pipe: the K = 1 instantiations.  The K-frame
+    // accumulators sit at 256 VGPRs and spill with it; they keep the vector-pipe form.
+    constexpr bool MFMA_FE = KONE;
+    // vector form: raw[j] = x[64 j + t].  Matrix form: raw[2 b + h] = the samples a = 2 h (low half) and 2 h + 1
+    // of j = 4 a + b: the lane's B operand of MFMA b is (raw[2 b], raw[2 b + 1]), bytes in order (a, re / im)
+    unsigned raw[MFMA_FE ? 8 : 16];
     auto load_raw = [&](long frame) {
         const uint16_t* src = reinterpret_cast<const uint16_t*>(p.in) + frame * N;
+        if constexpr (MFMA_FE) {
 #pragma unroll
-        for (int j = 0; j < 16; ++j) raw[j] = __builtin_nontemporal_load(src + 64 * j + t);
+            for (int b = 0; b < 4; ++b) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    pk_u16 w;
+                    w.x = __builtin_nontemporal_load(src + 64 * (8 * h + b) + t);
+                    w.y = __builtin_nontemporal_load(src + 64 * (8 * h + 4 + b) + t);
+                    raw[2 * b + h] = __builtin_bit_cast(unsigned, w);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) raw[j] = __builtin_nontemporal_load(src + 64 * j + t);
+        }
     };
     if (g < ngroups) load_raw(g * K);
+
+    // constant operands of the matrix form.  A (16 x 32, lane l holds row l & 15, k = 8 (l >> 4) + e): row 4 p + gg
+    // takes row p of the radix-4 from k-block gg alone, so lane (g, 4 p + gg) is zero unless g == gg.  C: the samples
+    // enter as signed bytes (x ^ 0x80); the 128 (1 + i) per sample the vector form carries -- it reaches X[0] only --
+    // is 512 (1 + i) in y_0 = result rows 0 .. 3 = lanes 0 .. 15: added back, every integer is the vector form's.
+    long a_re = 0, a_im = 0;
+    if ((t >> 4) == (t & 3)) {
+        const int pp = (t & 15) >> 2;
+        a_re = pp == 0 ? radix4_coef(0, false) : pp == 1 ? radix4_coef(1, false) : pp == 2 ? radix4_coef(2, false) : radix4_coef(3, false);
+        a_im = pp == 0 ? radix4_coef(0, true) : pp == 1 ? radix4_coef(1, true) : pp == 2 ? radix4_coef(2, true) : radix4_coef(3, true);
+    }
+    const int c_dc = t < 16 ? 512 : 0;
+    const v4i c_off = {c_dc, c_dc, c_dc, c_dc};
 
     // lane constants, resident for the life of the (persistent) workgroup
     f2 twA[8], twB[16];
@@ -132,48 +187,70 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
         for (int kf = 0; kf < K; ++kf) {
             const long frame = g * K + kf;
 
-            // ---- pass 0: radix-4 over a on packed int16 points.  The 128 offset of the samples
-            // only reaches y_0 -> bin 0 of every 256-point transform p = 0 -> bins k = 4 k' + 0 ...
-            // no: it reaches exactly X[0] (a constant sequence has a single non-zero bin), which is
-            // never output (src/spectrum.c:31); it is kept, as in the other kernels.
-            unsigned y[16];                     // y[4 b + pp]
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                pk_i16 x[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const unsigned r = raw[4 * a + b];
-                    // bytes (re, im) -> int16 pair (re | im << 16): one v_perm_b32
-                    x[a] = __builtin_bit_cast(pk_i16, __builtin_amdgcn_perm(r, r, 0x0c010c00u));
-                }
-                const pk_i16 s0 = x[0] + x[2], s1 = x[0] - x[2], s2 = x[1] + x[3], s3 = x[1] - x[3];
-                const pk_i16 rot = {s3.y, (short)-s3.x};                 // -i * s3
-                y[4 * b + 0] = __builtin_bit_cast(unsigned, (pk_i16)(s0 + s2));
-                y[4 * b + 1] = __builtin_bit_cast(unsigned, (pk_i16)(s1 + rot));
-                y[4 * b + 2] = __builtin_bit_cast(unsigned, (pk_i16)(s0 - s2));
-                y[4 * b + 3] = __builtin_bit_cast(unsigned, (pk_i16)(s1 - rot));
-            }
-            {
+            auto prefetch = [&]() {
                 long nf = frame + 1;
                 if (kf + 1 == K) nf = g_next * K;
                 if (nf >= ngroups * K) nf = frame;        // in bounds, result unused  (this form: the ternary
                                                           // spelling costs the K > 1 instantiations 12-15 spilled VGPRs)
                 load_raw(nf);
-            }
-
-            // ---- cross-row 4 x 4 transpose (lane row <-> p): afterwards lane (row p, column c)
-            // holds y_p[c + 16 (4 b + g)] in y[4 b + g]
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                swap_rows16(y[4 * b + 0], y[4 * b + 1]);
-                swap_rows16(y[4 * b + 2], y[4 * b + 3]);
-                swap_rows32(y[4 * b + 0], y[4 * b + 2]);
-                swap_rows32(y[4 * b + 1], y[4 * b + 3]);
-            }
+            };
             f2 v[16];
+            if constexpr (MFMA_FE) {
+                // ---- pass 0 and the cross-row transpose as eight v_mfma_i32_16x16x32_i8: D = A B + C with B
+                // (32 x 16, lane l holds column l & 15, k = 8 (l >> 4) + e) = this lane's four samples of
+                // m = 64 b + t, so column c, k-block t >> 4; D (lane l holds column l & 15, rows 4 (l >> 4) + i):
+                // lane (p, c), register i of MFMA b = Re | Im y_p[c + 16 (4 b + i)], as int32 -- pass A's layout.
+                v4i yre[4], yim[4];
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                v[r] = mk((double)(short)(y[r] & 0xffffu), (double)((int)y[r] >> 16));
+                for (int b = 0; b < 4; ++b) {
+                    const unsigned lo = raw[2 * b] ^ 0x80808080u, hi = raw[2 * b + 1] ^ 0x80808080u;
+                    const long xb = (long)(((unsigned long)hi << 32) | lo);
+                    yre[b] = __builtin_amdgcn_mfma_i32_16x16x32_i8(a_re, xb, c_off, 0, 0, 0);
+                    yim[b] = __builtin_amdgcn_mfma_i32_16x16x32_i8(a_im, xb, c_off, 0, 0, 0);
+                }
+                // the eight MFMAs back to back, the conversions behind the last one: left alone the scheduler
+                // converts each quad as it lands and waits (s_nop 5 .. 7) eight times a frame
+                __builtin_amdgcn_sched_barrier(0);
+                prefetch();
+#pragma unroll
+                for (int r = 0; r < 16; ++r) v[r] = mk((double)yre[r >> 2][r & 3], (double)yim[r >> 2][r & 3]);
+            } else {
+                // ---- pass 0: radix-4 over a on packed int16 points.  The 128 offset of the samples
+                // only reaches y_0 -> bin 0 of every 256-point transform p = 0 -> bins k = 4 k' + 0 ...
+                // no: it reaches exactly X[0] (a constant sequence has a single non-zero bin), which is
+                // never output (src/spectrum.c:31); it is kept, as in the other kernels.
+                unsigned y[16];                     // y[4 b + pp]
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    pk_i16 x[4];
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        const unsigned r = raw[4 * a + b];
+                        // bytes (re, im) -> int16 pair (re | im << 16): one v_perm_b32
+                        x[a] = __builtin_bit_cast(pk_i16, __builtin_amdgcn_perm(r, r, 0x0c010c00u));
+                    }
+                    const pk_i16 s0 = x[0] + x[2], s1 = x[0] - x[2], s2 = x[1] + x[3], s3 = x[1] - x[3];
+                    const pk_i16 rot = {s3.y, (short)-s3.x};                 // -i * s3
+                    y[4 * b + 0] = __builtin_bit_cast(unsigned, (pk_i16)(s0 + s2));
+                    y[4 * b + 1] = __builtin_bit_cast(unsigned, (pk_i16)(s1 + rot));
+                    y[4 * b + 2] = __builtin_bit_cast(unsigned, (pk_i16)(s0 - s2));
+                    y[4 * b + 3] = __builtin_bit_cast(unsigned, (pk_i16)(s1 - rot));
+                }
+                prefetch();
+
+                // ---- cross-row 4 x 4 transpose (lane row <-> p): afterwards lane (row p, column c)
+                // holds y_p[c + 16 (4 b + g)] in y[4 b + g]
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    swap_rows16(y[4 * b + 0], y[4 * b + 1]);
+                    swap_rows16(y[4 * b + 2], y[4 * b + 3]);
+                    swap_rows32(y[4 * b + 0], y[4 * b + 2]);
+                    swap_rows32(y[4 * b + 1], y[4 * b + 3]);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    v[r] = mk((double)(short)(y[r] & 0xffffu), (double)((int)y[r] >> 16));
+            }
 
             // ---- pass A: radix-16 over r with the geometric pre-twiddle (W_64^p)^r absorbed;
             // slot s holds index q = rev16(s)

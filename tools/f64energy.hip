@@ -109,9 +109,88 @@ DEF32(k_pkadd16, I16(PKADD16))
 DEF32(k_perm, I16(PERM))
 DEF32(k_mov32, I16(MOV32))
 DEF32(k_addu32, I16(ADDU32))
+#define XOR32(r)   "v_xor_b32_e32 " #r ", %16, " #r "\n"
+DEF32(k_xor32, I16(XOR32))
 #define SWAP32_8 "v_permlane32_swap_b32_e32 %0, %1\n v_permlane32_swap_b32_e32 %2, %3\n v_permlane32_swap_b32_e32 %4, %5\n v_permlane32_swap_b32_e32 %6, %7\n" \
                  "v_permlane16_swap_b32_e32 %8, %9\n v_permlane16_swap_b32_e32 %10, %11\n v_permlane16_swap_b32_e32 %12, %13\n v_permlane16_swap_b32_e32 %14, %15\n"
 DEF32(k_swap, SWAP32_8 SWAP32_8)
+
+// ---- matrix pipe: v_mfma_i32_16x16x32_i8 with the constant A operand of spectrum_f64_1024x.hip's front end (the
+// real part of the radix-4 coefficients: lane (g, row 4 p + gg) is zero unless g == gg, seven eighths zeros), B =
+// random bytes that move on every iteration, eight independent int32 accumulator quads
+typedef int v4i __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ long front_end_a_re(int t)
+{
+    const long re[4] = {0x0001000100010001L, (long)0xff0000ff01000001UL, 0x00ff000100ff0001L, 0x010000ffff000001L};
+    return (t >> 4) == (t & 3) ? re[(t & 15) >> 2] : 0L;
+}
+__device__ __forceinline__ unsigned hash32(unsigned x)
+{
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__global__ __launch_bounds__(64, 2) void k_mfma_i8(double* out, Stamp* st, int iters, double a, double b)
+{
+    PROLOGUE
+    const long va = front_end_a_re(threadIdx.x);
+    unsigned blo[8], bhi[8];
+    v4i acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        blo[k] = hash32(blockIdx.x * 1024 + threadIdx.x * 16 + 2 * k);
+        bhi[k] = hash32(blockIdx.x * 1024 + threadIdx.x * 16 + 2 * k + 1);
+        acc[k] = v4i{k, 0, 0, 0};
+    }
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int rep = 0; rep < 32; ++rep)
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                acc[k] = __builtin_amdgcn_mfma_i32_16x16x32_i8(va, (long)(((unsigned long)bhi[k] << 32) | blo[k]), acc[k], 0, 0, 0);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { blo[k] += 0x9e3779b9u; bhi[k] += 0x7f4a7c15u; }     // 16 of 272 instructions
+    }
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += acc[k][0] ^ acc[k][1] ^ acc[k][2] ^ acc[k][3];
+    out[blockIdx.x * 64 + threadIdx.x] = (double)s + a + b;
+    EPILOGUE
+}
+// the v_fma_f64 stream of k_fma64 with one such MFMA per 55 FMAs (the product kernel's 8 per 436): 8 x (55 + 1) per
+// iteration, counted as its 440 FMAs
+#define FMA55 D8(FMA64) D8(FMA64) D8(FMA64) D8(FMA64) D8(FMA64) D8(FMA64) FMA64(%0) FMA64(%1) FMA64(%2) FMA64(%3) FMA64(%4) FMA64(%5) FMA64(%6)
+__global__ __launch_bounds__(64, 2) void k_fma64_mfma(double* out, Stamp* st, int iters, double a, double b)
+{
+    PROLOGUE
+    double r0 = 1.0 + 1e-3 * threadIdx.x, r1 = r0 * 1.1, r2 = r0 * 1.2, r3 = r0 * 1.3, r4 = r0 * 1.4, r5 = r0 * 1.5, r6 = r0 * 1.6, r7 = r0 * 1.7;
+    double va = a + 1e-9 * threadIdx.x, vb = b - 1e-9 * threadIdx.x;
+    int vi = threadIdx.x;
+    const long ma = front_end_a_re(threadIdx.x);
+    unsigned blo[8], bhi[8];
+    v4i acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        blo[k] = hash32(blockIdx.x * 1024 + threadIdx.x * 16 + 2 * k);
+        bhi[k] = hash32(blockIdx.x * 1024 + threadIdx.x * 16 + 2 * k + 1);
+        acc[k] = v4i{k, 0, 0, 0};
+    }
+    for (int i = 0; i < iters; ++i) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            asm volatile(FMA55
+                : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "+v"(r4), "+v"(r5), "+v"(r6), "+v"(r7), "+v"(vi)
+                : "v"(va), "v"(vb), "s"(a), "s"(b));
+            acc[k] = __builtin_amdgcn_mfma_i32_16x16x32_i8(ma, (long)(((unsigned long)bhi[k] << 32) | blo[k]), acc[k], 0, 0, 0);
+            blo[k] += 0x9e3779b9u;
+            bhi[k] += 0x7f4a7c15u;
+        }
+    }
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += acc[k][0] ^ acc[k][1] ^ acc[k][2] ^ acc[k][3];
+    out[blockIdx.x * 64 + threadIdx.x] = r0 + r1 + r2 + r3 + r4 + r5 + r6 + r7 + vi + (double)s;
+    EPILOGUE
+}
 
 // ---- LDS: 16 x (ds_write_b128 + ds_read_b128) of a wavefront-private, conflict-free slice (rows of 17)
 __global__ __launch_bounds__(64, 2) void k_lds128(double* out, Stamp* st, int iters, double a, double b)
@@ -157,8 +236,9 @@ int main(int argc, char** argv)
         {"fma_f64_sgpr", k_fma64_s, 256, 0}, {"fma_f64_inline", k_fma64_lit, 256, 0}, {"fmac_f64", k_fmac64, 256, 0},
         {"cvt_f64_i32", k_cvt64, 256, 0}, {"mov_b64", k_mov64, 256, 0}, {"mix_5fma_2add_1mul", k_mix64, 256, 0},
         {"fma_f32", k_fma32, 256, 0}, {"add_f32", k_add32, 256, 0}, {"pk_add_u16", k_pkadd16, 256, 0},
-        {"perm_b32", k_perm, 256, 0}, {"mov_b32", k_mov32, 256, 0}, {"add_u32", k_addu32, 256, 0},
+        {"perm_b32", k_perm, 256, 0}, {"mov_b32", k_mov32, 256, 0}, {"add_u32", k_addu32, 256, 0}, {"xor_b32", k_xor32, 256, 0},
         {"permlane_swap", k_swap, 256, 0}, {"lds_w128_r128", k_lds128, 256, 16 * 17 * 64},
+        {"mfma_i8_sparse", k_mfma_i8, 256, 0}, {"fma_f64_with_mfma", k_fma64_mfma, 440, 0},
     };
     if (rsmi_init(0) != RSMI_STATUS_SUCCESS) { printf("rsmi_init failed\n"); return 2; }
     const int blocks = 2048, iters = 400;
@@ -167,11 +247,19 @@ int main(int argc, char** argv)
     CHECK(hipMalloc(&st, blocks * sizeof(Stamp)));
     std::vector<Stamp> hst(blocks);
     hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
-    printf("%-20s %10s %8s %8s %9s %10s %12s\n", "mode", "Ginstr/s", "sclk", "watts", "W(smi)", "nJ/instr", "cyc/instr/SIMD");
-    for (const Mode& m : modes) {
-        bool want = argc <= 2;
-        for (int i = 2; i < argc; ++i) want = want || !strcmp(argv[i], m.name);
-        if (!want) continue;
+    printf("%-20s %10s %8s %8s %9s %10s %10s %12s\n", "mode", "Ginstr/s", "sclk", "watts", "W(smi)", "nJ/instr", "above nop", "cyc/instr/SIMD");
+    // the modes in the order the command line names them (a name may repeat: run-to-run spread), else all of them
+    std::vector<const Mode*> order;
+    for (int i = 2; i < argc; ++i) {
+        const Mode* found = nullptr;
+        for (const Mode& m : modes) if (!strcmp(argv[i], m.name)) found = &m;
+        if (!found) { printf("unknown mode %s\n", argv[i]); return 2; }
+        order.push_back(found);
+    }
+    if (order.empty()) for (const Mode& m : modes) order.push_back(&m);
+    double nop_watts = 0.0;          // of this run's "nop" mode, once it has run
+    for (const Mode* mp : order) {
+        const Mode& m = *mp;
         auto launch = [&]() { hipLaunchKernelGGL(m.k, dim3(blocks), dim3(64), m.lds, 0, out, st, iters, 0.99999904632568359375, 1.0e-6); };
         // settle the governor
         const double tw = now_s();
@@ -200,8 +288,11 @@ int main(int argc, char** argv)
         const double watts = joules / (t1 - t0);
         // the device was busy gpu_ms of the wall interval; energy per instruction from the busy share
         const double busy = gpu_ms * 1e-3 / (t1 - t0);
-        printf("%-20s %10.2f %8.3f %8.0f %9.0f %10.3f %12.2f   (busy %.3f)\n", m.name, instr / (gpu_ms * 1e-3) * 1e-9, sclk, watts,
-               wn ? wsum / wn : 0.0, joules / instr * 1e9, sclk * 1e9 * (gpu_ms * 1e-3) * 1024.0 / instr, busy);
+        if (!strcmp(m.name, "nop")) nop_watts = watts;
+        const double rate = instr / (gpu_ms * 1e-3);                // wave64 instructions per second
+        printf("%-20s %10.2f %8.3f %8.0f %9.0f %10.3f %10.3f %12.2f   (busy %.3f)\n", m.name, rate * 1e-9, sclk, watts,
+               wn ? wsum / wn : 0.0, joules / instr * 1e9, nop_watts > 0 ? (watts - nop_watts) / rate * 1e9 : 0.0,
+               sclk * 1e9 * (gpu_ms * 1e-3) * 1024.0 / instr, busy);
         fflush(stdout);
     }
     return 0;

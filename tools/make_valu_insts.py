@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def pmc(workload):
     """the newest committed counter file of the workload (the kernel a line is priced with)"""
-    for tag in ("r05", "r04", "r03"):
+    for tag in ("mfma_fe", "r05", "r04", "r03"):
         f = os.path.join(ROOT, "profiles", "%s_%s_pmc.json" % (tag, workload))
         if os.path.exists(f):
             return json.load(open(f))["counters"]
@@ -52,15 +52,19 @@ def main():
                                            "spectra_fused<1024, u8, rect, sum, K=1>: 32 byte conversions per frame at 4 "
                                            "cycles; in-kernel clock 2.007 GHz median (p10-p90 1.936-2.078; another box's "
                                            "rocm-smi: 1.884-1.892 GHz at 1 394-1 402 W, the cap)"),
-        # round 4, spectrum_f64_1024x.hip (one wavefront per frame): 436 f64 add / mul / fma + 32 v_cvt_f64_i32 at 4
-        # cycles (+ 16 v_cvt_f32_f64 with f32 rows); the ~115 integer / cross-lane / address instructions at 2
+        # spectrum_f64_1024x.hip (one wavefront per frame): 436 f64 add / mul / fma + 32 v_cvt_f64_i32 at 4 cycles
+        # (+ 16 v_cvt_f32_f64 with f32 rows); the integer / address instructions at 2.  Since the integer front end
+        # moved to the matrix pipe (profiles/mfma_fe_*_pmc.json): 536 / 522 instead of 615 / 601 SQ_INSTS_VALU per frame,
+        # and 8 v_mfma_i32_16x16x32_i8 per frame (SQ_INSTS_VALU_MFMA_I8) that issue on the matrix pipe
         "batched_1024pt_64k_frames_f64": entry("batched_1024pt_64k_frames_f64", 65536, 436 + 32, 2.03,
                                                "spectra_f64_1024x<sum, K=1, f64 rows>: 436 f64 add / mul / fma + 32 "
-                                               "v_cvt_f64_i32 per frame at 4 cycles; rocm-smi sclk 2.02-2.05 GHz at "
+                                               "v_cvt_f64_i32 per frame at 4 cycles, 8 int8 MFMAs per frame beside "
+                                               "them on the matrix pipe; rocm-smi sclk 2.02-2.05 GHz at "
                                                "1 375-1 382 W (bench.py measures its own run's clock: roofline.sclk_ghz)"),
         "batched_1024pt_64k_frames_f64c_f32o": entry("batched_1024pt_64k_frames_f64c_f32o", 65536, 436 + 32 + 16, 2.01,
                                                      "spectra_f64_1024x<sum, K=1, f32 rows>: 436 f64 add / mul / fma + 32 "
-                                                     "v_cvt_f64_i32 + 16 v_cvt_f32_f64 per frame at 4 cycles; rocm-smi "
+                                                     "v_cvt_f64_i32 + 16 v_cvt_f32_f64 per frame at 4 cycles, 8 int8 MFMAs "
+                                                     "per frame beside them on the matrix pipe; rocm-smi "
                                                      "sclk 2.00-2.02 GHz at 1 380-1 386 W (profiles/r04_power_clocks.txt)"),
     }
     json.dump(out, open(sys.argv[1], "w"), indent=1, sort_keys=True)
