@@ -97,7 +97,7 @@ struct SpectraParamsF64 {
     int rows_f32;            // RTLWS_FLAG_ROWS_F32: f64 arithmetic, rows rounded once to f32 on the store
     // spectrum_f64_1024x.hip (1024 = 4 x 16 x 16, one LDS transposition)
     const double2* twxa;     // [4][8] (cos, tan) pairs of pass A's geometric pre-twiddle alpha = W_64^p
-    const double2* twxb;     // [64][16] W_1024^(c (4 q + p)) / 128, lane 16 p + c, slot s: q = rev16(s)
+    const double2* twxb;     // [16][64] W_1024^(c (4 q + p)) / 128, slot s: q = rev16(s), lane 16 p + c (the host table transposed)
 };
 
 // which f64 descriptors take the fused throughput kernel (the rest: spectrum_f64.hip): the three

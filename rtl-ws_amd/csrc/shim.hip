@@ -144,12 +144,16 @@ const Tables* get_tables(rtlws_engine* e, Prec prec, int n_fft)
     if (it != e->tables.end()) return &it->second;
     HIP_TRY(hipSetDevice(e->device), nullptr);
     const rtlws::HostTables h = prec == Prec::F64 ? rtlws::tables_f64(n_fft) : rtlws::tables_f32(n_fft);
+    // spectrum_f64_1024x.hip reads its inner twiddles [slot][lane]: a wave-instruction then covers 1 KiB contiguous
+    // (eight 128-byte lines), where the host table's [lane][slot] puts its 64 lanes on 64 different lines
+    std::vector<rtlws::D2> twxb_t(h.twxb_64.size());
+    for (size_t i = 0; i < twxb_t.size(); ++i) twxb_t[(i % 16) * (twxb_t.size() / 16) + i / 16] = h.twxb_64[i];
     Tables tb;
     if (!upload(tb, h.tw1, &tb.tw1) || !upload(tb, h.tw1_128, &tb.tw1_128) || !upload(tb, h.tw2, &tb.tw2) ||
         !upload(tb, h.hann_cs, &tb.hann_cs) || !upload(tb, h.hann, &tb.hann) || !upload(tb, h.tw64, &tb.tw64) ||
         !upload(tb, h.hann64, &tb.hann64) || !upload(tb, h.tw1_64, &tb.tw1_64) || !upload(tb, h.tw1u_64, &tb.tw1u_64) ||
         !upload(tb, h.tw2_64, &tb.tw2_64) || !upload(tb, h.hann_cs64, &tb.hann_cs64) ||
-        !upload(tb, h.twxa_64, &tb.twxa_64) || !upload(tb, h.twxb_64, &tb.twxb_64))
+        !upload(tb, h.twxa_64, &tb.twxa_64) || !upload(tb, twxb_t, &tb.twxb_64))
         return nullptr;
     return &(e->tables[key] = std::move(tb));
 }

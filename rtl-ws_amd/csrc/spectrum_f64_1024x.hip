@@ -53,6 +53,7 @@ using namespace f64;
 typedef short pk_i16 __attribute__((ext_vector_type(2)));      // (re, im) of one integer point
 typedef unsigned short pk_u16 __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
+#define RTLWS_GLOBAL __attribute__((address_space(1)))          // a pointer the compiler need not prove global
 
 // Row p of the radix-4 as an int8 A operand: eight bytes, element 2 a + ri = the coefficient of x[a].re (ri = 0) /
 // x[a].im (ri = 1) in the real (im = false) or imaginary part of x[a] (-i)^(a p)
@@ -83,6 +84,11 @@ __device__ __forceinline__ void swap_rows32(unsigned& a, unsigned& b)
     b = r[1];
 }
 
+// V_WRITELANE_B32 as the compiler's own intrinsic (hipcc 7.2 has the readlane builtin but not this one): lane `lane`
+// of `old` replaced by the scalar `src`.  Not inline assembly: a VALU-written SGPR needs wait states before a VALU
+// reads it, which the compiler inserts around its own instructions only.
+extern "C" __device__ int rtlws_writelane(int src, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+
 // WAVES = 1: one wavefront per workgroup, output rows dealt statically (row = workgroup + i * grid) -- small
 // batches and the drop-in calls.  WAVES > 1: ONE workgroup of WAVES wavefronts per CU (WAVES / 4 per SIMD),
 // the workgroup's rows (b + i * grid) handed to its wavefronts one at a time through a counter in LDS.  Why
@@ -106,22 +112,30 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
 
     const int t = threadIdx.x & 63;
     const int K = KONE ? 1 : p.k_avg;
-    const long ngroups = p.ngroups;
-    // this workgroup's output rows: blockIdx.x + i * gridDim.x; the first WAVES indices i are dealt statically
-    long g = (long)blockIdx.x + (WAVES == 1 ? 0L : (long)(threadIdx.x >> 6) * gridDim.x);
+    // rows and frames are counted in 32 bits (2^31 frames are 4 TiB of samples): the scalar unit compares 32-bit
+    // integers, a 64-bit signed compare goes to the vector pipe.  Addresses are 64-bit scalar arithmetic.
+    const int ngroups = (int)p.ngroups;
+    // this workgroup's output rows: blockIdx.x + i * gridDim.x; the first WAVES indices i are dealt statically.
+    // The row index is wave-uniform and is carried on the scalar unit (readfirstlane: the wavefront's number is
+    // uniform, which the compiler cannot see), so every frame, prefetch and row address below is scalar arithmetic
+    // and the loads and stores take the form scalar base + per-lane byte offset + immediate.
+    int g = blockIdx.x;
     if constexpr (WAVES > 1) {
+        g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x + (threadIdx.x >> 6) * gridDim.x));
         if (threadIdx.x == 0) *row_counter = WAVES;
-        __syncthreads();                                        // the only barrier of the kernel
     }
     // the row after `cur`: WAVES = 1 strides, WAVES > 1 takes the workgroup's next undone row (lane 0's LDS
-    // atomic, broadcast); >= ngroups: none left
-    auto next_row = [&](long cur) -> long {
+    // atomic, broadcast); >= ngroups: none left.  The atomic is spelt as an increment that wraps at 2^32 - 1
+    // (ds_inc_rtn_u32), which is a fetch-and-add of one for every count a launch can reach: around a fetch_add the
+    // compiler's atomic optimiser puts a v_mbcnt / popcount / v_readfirstlane wrapper, nine vector instructions
+    // per row for an atomic that one lane issues anyway.
+    auto next_row = [&](int cur) -> int {
         if constexpr (WAVES == 1) {
-            return cur + gridDim.x;
+            return cur + (int)gridDim.x;
         } else {
             unsigned v = 0;
-            if (t == 0) v = __hip_atomic_fetch_add(row_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            return (long)blockIdx.x + (long)(unsigned)__builtin_amdgcn_readfirstlane((int)v) * gridDim.x;
+            if (t == 0) v = __builtin_amdgcn_atomic_inc32(row_counter, 0xffffffffu, __ATOMIC_RELAXED, "workgroup");
+            return (int)(blockIdx.x + (unsigned)__builtin_amdgcn_readfirstlane((int)v) * gridDim.x);
         }
     };
 
@@ -131,26 +145,29 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
     // vector form: raw[j] = x[64 j + t].  Matrix form: raw[2 b + h] = the samples a = 2 h (low half) and 2 h + 1
     // of j = 4 a + b: the lane's B operand of MFMA b is (raw[2 b], raw[2 b + 1]), bytes in order (a, re / im)
     unsigned raw[MFMA_FE ? 8 : 16];
-    auto load_raw = [&](long frame) {
-        const uint16_t* src = reinterpret_cast<const uint16_t*>(p.in) + frame * N;
+    unsigned lane_in = 2u * t;                    // the lane's byte offset in a frame's 128-byte lines
+    auto load_raw = [&](int frame) {
+        const char* base = reinterpret_cast<const char*>(p.in) + (long)frame * (2 * N);          // uniform
+        // kept whole, the base in a scalar pair and the lane's offset in 32 bits (passed through in place, so no copy):
+        // else p.in + lane is hoisted as a 64-bit vector value and the frame added to it per lane (v_lshl_add_u64)
+        asm("" : "+s"(base), "+v"(lane_in));
+        const RTLWS_GLOBAL uint16_t* const src = (const RTLWS_GLOBAL uint16_t*)(base + lane_in);
         if constexpr (MFMA_FE) {
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     pk_u16 w;
-                    w.x = __builtin_nontemporal_load(src + 64 * (8 * h + b) + t);
-                    w.y = __builtin_nontemporal_load(src + 64 * (8 * h + 4 + b) + t);
+                    w.x = __builtin_nontemporal_load(src + 64 * (8 * h + b));
+                    w.y = __builtin_nontemporal_load(src + 64 * (8 * h + 4 + b));
                     raw[2 * b + h] = __builtin_bit_cast(unsigned, w);
                 }
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) raw[j] = __builtin_nontemporal_load(src + 64 * j + t);
+            for (int j = 0; j < 16; ++j) raw[j] = __builtin_nontemporal_load(src + 64 * j);
         }
     };
-    if (g < ngroups) load_raw(g * K);
-
     // constant operands of the matrix form.  A (16 x 32, lane l holds row l & 15, k = 8 (l >> 4) + e): row 4 p + gg
     // takes row p of the radix-4 from k-block gg alone, so lane (g, 4 p + gg) is zero unless g == gg.  C: the samples
     // enter as signed bytes (x ^ 0x80); the 128 (1 + i) per sample the vector form carries -- it reaches X[0] only --
@@ -164,31 +181,37 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
     const int c_dc = t < 16 ? 512 : 0;
     const v4i c_off = {c_dc, c_dc, c_dc, c_dc};
 
-    // lane constants, resident for the life of the (persistent) workgroup
+    // lane constants, resident for the life of the (persistent) workgroup.  The 24 table loads and the first
+    // frame's samples are issued together, ahead of the barrier: one memory round trip in the head of a launch, not
+    // two.  twxb is [slot][lane] on the device: a wave-instruction reads 1 KiB contiguous.
     f2 twA[8], twB[16];
 #pragma unroll
     for (int m = 0; m < 8; ++m) twA[m] = p.twxa[(t >> 4) * 8 + m];
 #pragma unroll
-    for (int s = 0; s < 16; ++s) twB[s] = p.twxb[t * 16 + s];
+    for (int s = 0; s < 16; ++s) twB[s] = p.twxb[s * 64 + t];
+    if (g < ngroups) load_raw(g * K);
+    if constexpr (WAVES > 1) __syncthreads();                  // the only barrier of the kernel (the row counter)
 #pragma unroll
     for (int m = 0; m < 8; ++m) asm volatile("" ::"v"(twA[m].x), "v"(twA[m].y));      // retired before the loop
 #pragma unroll
     for (int s = 0; s < 16; ++s) asm volatile("" ::"v"(twB[s].x), "v"(twB[s].y));
 
     const int wp = t >> 4, wc = t & 15;         // writer side of the transposition: lane (p, c)
+    unsigned lane_out = (OUT == OUT_PAYLOAD ? 1u : ROWF32 ? 4u : 8u) * t;     // the lane's byte offset in a row's 64 outputs
 
     while (g < ngroups) {
-        const long g_next = next_row(g);
+        const int g_next = next_row(g);
         double acc[16];
         double wdc = 0.0;
 #pragma unroll
         for (int u = 0; u < 16; ++u) acc[u] = 0.0;
 
+#pragma nounroll      // (left alone the compiler unrolls the 32-bit frame loop by two: twice the code, nothing gained)
         for (int kf = 0; kf < K; ++kf) {
-            const long frame = g * K + kf;
+            const int frame = g * K + kf;
 
             auto prefetch = [&]() {
-                long nf = frame + 1;
+                int nf = frame + 1;
                 if (kf + 1 == K) nf = g_next * K;
                 if (nf >= ngroups * K) nf = frame;        // in bounds, result unused  (this form: the ternary
                                                           // spelling costs the K > 1 instantiations 12-15 spilled VGPRs)
@@ -293,8 +316,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
 
         // ---- DC-slot rule (src/spectrum.c:25-33): slot N/2 (bin 0: lane 0, u = 0) takes
         // sum_k (K-k) * P_k[N-1] (bin N-1: lane 63, u = 15)
-        const double dcv = lane63(wdc);
-        if (t == 0) acc[0] = dcv;
+        // (two v_readlane + two v_writelane: lane 0's halves of acc[0] replaced in place)
+        {
+            const unsigned long long w = __builtin_bit_cast(unsigned long long, wdc);
+            const unsigned long long a0 = __builtin_bit_cast(unsigned long long, acc[0]);
+            const unsigned lo = rtlws_writelane(__builtin_amdgcn_readlane((int)(unsigned)w, 63), 0, (int)(unsigned)a0);
+            const unsigned hi = rtlws_writelane(__builtin_amdgcn_readlane((int)(unsigned)(w >> 32), 63), 0, (int)(unsigned)(a0 >> 32));
+            acc[0] = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+        }
 
         // ---- epilogue + store: slot u holds bin 64 q' + t, q' = rev16(u); fft-shift = flip the top
         // bit of the bin index = q' ^ 8.
@@ -302,16 +331,23 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 2 : WAVES / 4) void spectr
         // the row staged through the idle transposition buffer so that a lane stores 16 bytes -- 111.2 us
         // against 109.3 for these 4-byte-per-lane stores; profiles/r04_x1024_store_ab.txt.)
         {
+            constexpr unsigned ELEM = OUT == OUT_PAYLOAD ? 1 : ROWF32 ? 4 : 8;             // bytes per output
+            char* base = reinterpret_cast<char*>(p.out) + g * (long)(N * ELEM);        // uniform (as in load_raw)
+            char* base_hi = base + 4096;            // f64 rows are 8 KiB and a store's immediate ends at 4 095: a second base
+            asm("" : "+s"(base), "+s"(base_hi), "+v"(lane_out));
+            RTLWS_GLOBAL char* const row = (RTLWS_GLOBAL char*)(base + lane_out);
+            RTLWS_GLOBAL char* const row_hi = (RTLWS_GLOBAL char*)(base_hi + lane_out);
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
-                const long i = g * N + 64 * (rev16(u) ^ 8) + t;
+                const unsigned off = 64 * ELEM * (rev16(u) ^ 8);           // a constant once unrolled
+                RTLWS_GLOBAL char* const dst = (off < 4096 ? row : row_hi) + (off & 4095);
                 const double a = acc[u];
                 if constexpr (OUT == OUT_PAYLOAD) {
-                    reinterpret_cast<uint8_t*>(p.out)[i] = (uint8_t)payload_f64(p.lin_gain * a, p.count);
+                    *(RTLWS_GLOBAL uint8_t*)dst = (uint8_t)payload_f64(p.lin_gain * a, p.count);
                 } else {
                     const double o = (OUT == OUT_DB) ? db_f64(a, p.count) : a;
-                    if constexpr (ROWF32) __builtin_nontemporal_store((float)o, reinterpret_cast<float*>(p.out) + i);
-                    else __builtin_nontemporal_store(o, reinterpret_cast<double*>(p.out) + i);
+                    if constexpr (ROWF32) __builtin_nontemporal_store((float)o, (RTLWS_GLOBAL float*)dst);
+                    else __builtin_nontemporal_store(o, (RTLWS_GLOBAL double*)dst);
                 }
             }
         }

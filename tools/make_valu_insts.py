@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def pmc(workload):
     """the newest committed counter file of the workload (the kernel a line is priced with)"""
-    for tag in ("mfma_fe", "r05", "r04", "r03"):
+    for tag in ("saddr", "mfma_fe", "r05", "r04", "r03"):
         f = os.path.join(ROOT, "profiles", "%s_%s_pmc.json" % (tag, workload))
         if os.path.exists(f):
             return json.load(open(f))["counters"]
@@ -55,7 +55,8 @@ def main():
         # spectrum_f64_1024x.hip (one wavefront per frame): 436 f64 add / mul / fma + 32 v_cvt_f64_i32 at 4 cycles
         # (+ 16 v_cvt_f32_f64 with f32 rows); the integer / address instructions at 2.  Since the integer front end
         # moved to the matrix pipe (profiles/mfma_fe_*_pmc.json): 536 / 522 instead of 615 / 601 SQ_INSTS_VALU per frame,
-        # and 8 v_mfma_i32_16x16x32_i8 per frame (SQ_INSTS_VALU_MFMA_I8) that issue on the matrix pipe
+        # and 8 v_mfma_i32_16x16x32_i8 per frame (SQ_INSTS_VALU_MFMA_I8) that issue on the matrix pipe.  Since the
+        # wave-uniform address / row-counter / DC-slot work left the vector pipe (profiles/saddr_*_pmc.json): 517 / 501
         "batched_1024pt_64k_frames_f64": entry("batched_1024pt_64k_frames_f64", 65536, 436 + 32, 2.03,
                                                "spectra_f64_1024x<sum, K=1, f64 rows>: 436 f64 add / mul / fma + 32 "
                                                "v_cvt_f64_i32 per frame at 4 cycles, 8 int8 MFMAs per frame beside "
