@@ -76,6 +76,9 @@ int rtlws_device_pci_bus_id(int device, char* buf, int len);
 rtlws_engine* rtlws_engine_create(int device);
 void rtlws_engine_destroy(rtlws_engine* e);
 int rtlws_engine_device(const rtlws_engine* e);
+/* The engine's own stream as a hipStream_t -- what RTLWS_STREAM_ENGINE (NULL) stands for in every call here: for
+ * libraries layered on an engine (rtlws_long.h) that launch on it themselves.  NULL for a null engine. */
+void* rtlws_engine_stream(const rtlws_engine* e);
 
 /* Kernel-selection switches, for experiments and A/B tests.  Each is read from the environment
  * ONCE, when the engine is created (the variable in brackets), and can be changed afterwards only
@@ -109,7 +112,7 @@ int rtlws_engine_get_option(const rtlws_engine* e, const char* name);
  * therefore not legal inside a hipGraph capture).  After this, batch launches
  * for that size only enqueue a kernel and may be captured.  0 / -1 / -3. */
 int rtlws_engine_prepare(rtlws_engine* e, int n_fft);
-/* The same for rtlws_spectra_batch_f64's tables (2 <= n_fft <= 8192); it also raises the dynamic-LDS limit of
+/* The same for rtlws_spectra_batch_f64's tables (2 <= n_fft <= 8192; longer frames: rtlws_long.h); it also raises the dynamic-LDS limit of
  * every instantiation of that size that needs more than 64 KiB (hipFuncSetAttribute, once per instantiation
  * and device), which the first launch of such an instantiation would otherwise do. */
 int rtlws_engine_prepare_f64(rtlws_engine* e, int n_fft);
@@ -235,7 +238,8 @@ int rtlws_payload_from_sums(rtlws_engine* e, const float* d_sums, int n, int cou
  * reference-API paths -- spectrum_add_* (spectrum.h) and cbb_main.h -- move
  * one to six frames per call, so they go through this entry point: same
  * descriptor, same semantics and frame layout as rtlws_spectra_batch, f64
- * arithmetic, any 2 <= n_fft <= 8192.  1024- / 2048- / 4096-point frames of any input
+ * arithmetic, any 2 <= n_fft <= 8192 (power-of-two frames of 2^14 .. 2^20 points have entry points of their own:
+ * rtlws_long.h).  1024- / 2048- / 4096-point frames of any input
  * kind, and cmplx_u8 through the CIC-fused input stage for cic_r = 8, 10, 12, run the
  * fused throughput kernel (spectrum_f64_fused.hip; needs d_out -- and d_in when cic_r > 1
  * -- 16-byte aligned, else the general kernel is used); everything else one workgroup per

@@ -24,7 +24,10 @@
  * Differences, stated so a maintainer is not surprised:
  *   - 2 <= N <= 8192 (a frame lives in the 160 KiB LDS of one compute unit as
  *     complex doubles): the fused radix-16 kernel at N = 1024 / 2048 / 4096, radix-2
- *     for the other powers of two, a direct O(N^2) sum for any other N.  There is no CPU path: if no HIP device is usable, or N is out of
+ *     for the other powers of two, a direct O(N^2) sum for any other N.  Above that, the powers of two
+ *     N = 2^14 .. 2^20: a four-step transform through device memory (rtlws_long.h, librtlws_long.so; one plan per
+ *     input kind, opened on the first spectrum_add_* of that kind).  Any other N above 8192 is not served (the
+ *     reference plans any length).  There is no CPU path: if no HIP device is usable, or N is out of
  *     range, spectrum_alloc returns NULL (the reference never reports failure).
  *   - Arithmetic is f64 on the device, like the reference (f64 via FFTW):
  *     increments agree with an f64 FFT to <= 1e-10 relative per bin under the

@@ -356,6 +356,8 @@ void rtlws_engine_destroy(rtlws_engine* e)
 
 int rtlws_engine_device(const rtlws_engine* e) { return e ? e->device : -1; }
 
+void* rtlws_engine_stream(const rtlws_engine* e) { return e ? e->stream : nullptr; }
+
 int rtlws_engine_set_option(rtlws_engine* e, const char* name, int value)
 {
     g_err.clear();

@@ -10,6 +10,12 @@
  * host memory.  One frame per call is launch- and PCIe-bound whatever the
  * arithmetic costs, so nothing is gained by computing it in f32; the f32 fused
  * kernel is the batch API's (rtlws_hip.h).
+ *
+ * Frames above 8192 points (powers of two up to 2^20) go through rtlws_long.h's plans instead, one per input
+ * kind, opened on first use for one frame, K = 1, power sums.  That needs librtlws_long.so, which only the product
+ * build links: it compiles this file with -DRTLWS_LONG_FRAMES (rtl-ws_amd/Makefile).  Without the switch -- a host
+ * program built against a shim that lacks the library -- this file refers to none of its symbols and refuses those
+ * sizes as it always did.
  */
 #include "spectrum.h"
 
@@ -19,13 +25,57 @@
 
 #include "host_ctx.h"
 #include "rtlws_hip.h"
+#ifdef RTLWS_LONG_FRAMES
+#include "rtlws_long.h"
+#endif
+
+#define SHORT_MAX 8192    /* rtlws_spectra_batch_f64's largest frame */
 
 struct spectrum {
     int N;
     rtlws_engine* eng;
     void* h_in;       /* pinned, N * 8 bytes: large enough for cmplx_s32 */
     double* h_out;    /* pinned, N doubles */
+#ifdef RTLWS_LONG_FRAMES
+    rtlws_long_plan* plan[3];    /* N > SHORT_MAX: by enum rtlws_input, opened on first use */
+#endif
 };
+
+/* whether frames of N > SHORT_MAX points are served (powers of two up to 2^20, product build only) */
+static int long_size_ok(int N)
+{
+#ifdef RTLWS_LONG_FRAMES
+    rtlws_spectra_desc d;
+    memset(&d, 0, sizeof d);
+    d.n_fft = N;
+    d.k_avg = 1;
+    return rtlws_long_supported(&d);
+#else
+    (void)N;
+    return 0;
+#endif
+}
+
+/* one frame from h_in to h_out on the engine's stream; 0 or the failing call's code (its text: *why) */
+static int run_frame(struct spectrum* s, const rtlws_spectra_desc* d, const char** why)
+{
+    int rc;
+#ifdef RTLWS_LONG_FRAMES
+    if (s->N > SHORT_MAX) {
+        rtlws_long_plan** p = &s->plan[d->input];
+        *why = NULL;
+        if (!*p) *p = rtlws_long_open(s->eng, d, 1);
+        rc = *p ? rtlws_long_run(*p, s->h_in, 1, s->h_out, NULL) : -3;
+        if (rc) *why = rtlws_long_last_error();
+        if (!rc && (rc = rtlws_stream_sync(s->eng, NULL)) != 0) *why = rtlws_last_error();
+        return rc;
+    }
+#endif
+    rc = rtlws_spectra_batch_f64(s->eng, d, s->h_in, 1, s->h_out, NULL);
+    if (!rc) rc = rtlws_stream_sync(s->eng, NULL);
+    *why = rtlws_last_error();
+    return rc;
+}
 
 struct spectrum* spectrum_alloc(int N)
 {
@@ -34,7 +84,7 @@ struct spectrum* spectrum_alloc(int N)
     memset(&probe, 0, sizeof probe);
     probe.n_fft = N;
     probe.k_avg = 1;
-    if (rtlws_spectra_kernel_kind(&probe) == 0 || N > 8192) {
+    if (N > SHORT_MAX ? !long_size_ok(N) : rtlws_spectra_kernel_kind(&probe) == 0) {
         fprintf(stderr, "rtlws: spectrum_alloc(%d): size not supported by the device engine\n", N);
         return NULL;
     }
@@ -64,6 +114,7 @@ static int add_frame(struct spectrum* s, const void* src, size_t sample_bytes, i
     rtlws_spectra_desc d;
     const int N = s->N;
     const int offset = N / 2;
+    const char* why;
     int i;
 
     if (len != N) return -1;                      /* reference src/spectrum.c:51-52 */
@@ -79,8 +130,8 @@ static int add_frame(struct spectrum* s, const void* src, size_t sample_bytes, i
     /* One frame per call: the kernel reads the frame from, and stores the row into, the pinned
      * (device-mapped) staging buffers itself -- one launch and one synchronisation per call
      * instead of two copies around them. */
-    if (rtlws_spectra_batch_f64(s->eng, &d, s->h_in, 1, s->h_out, NULL) || rtlws_stream_sync(s->eng, NULL)) {
-        fprintf(stderr, "rtlws: spectrum_add: device failure: %s\n", rtlws_last_error());
+    if (run_frame(s, &d, &why)) {
+        fprintf(stderr, "rtlws: spectrum_add: device failure: %s\n", why);
         return -3;
     }
 
@@ -114,6 +165,9 @@ int spectrum_add_real_f32(struct spectrum* s, const float* src, double* power_sp
 void spectrum_free(struct spectrum* s)
 {
     if (!s) return;
+#ifdef RTLWS_LONG_FRAMES
+    for (int k = 0; k < 3; k++) rtlws_long_close(s->plan[k]);
+#endif
     rtlws_pinned_free(s->h_in);
     rtlws_pinned_free(s->h_out);
     rtlws_engine_destroy(s->eng);

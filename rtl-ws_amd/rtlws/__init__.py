@@ -6,6 +6,7 @@ behind it -- if the libraries are missing or no HIP device is usable, calls
 fail loudly.
 
   Engine ............ include/rtlws_hip.h (batch API on device buffers)
+  LongPlan .......... include/rtlws_long.h (f64 spectra of 2^14 .. 2^20-point frames)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -24,6 +25,7 @@ LIB_DIR = os.path.join(ROOT, "lib")
 HIP_LIB = os.environ.get("RTLWS_HIP_LIB") or os.path.join(LIB_DIR, "librtlws_hip.so")
 # RTLWS_AMD_LIB: an instrumented build of the C host layer (tests/tools/asan_host_cpu.sh)
 AMD_LIB = os.environ.get("RTLWS_AMD_LIB") or os.path.join(LIB_DIR, "librtlws_amd.so")
+LONG_LIB = os.path.join(LIB_DIR, "librtlws_long.so")     # include/rtlws_long.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -67,6 +69,7 @@ class CicDelayLine(C.Structure):
 # every symbol include/*.h declares, by library (tests check the exports)
 HIP_SYMBOLS = [
     "rtlws_device_count", "rtlws_device_pci_bus_id", "rtlws_engine_create", "rtlws_engine_destroy", "rtlws_engine_device",
+    "rtlws_engine_stream",
     "rtlws_engine_prepare", "rtlws_engine_prepare_f64", "rtlws_engine_set_option", "rtlws_engine_get_option",
     "rtlws_last_error", "rtlws_dev_alloc", "rtlws_dev_free", "rtlws_pinned_alloc",
     "rtlws_pinned_free", "rtlws_copy_h2d", "rtlws_copy_d2h", "rtlws_memset_dev",
@@ -78,6 +81,8 @@ HIP_SYMBOLS = [
     "rtlws_queue_create", "rtlws_queue_destroy", "rtlws_queue_wait_event", "rtlws_event_create_blocking",
     "rtlws_clock_stamp",
 ]
+LONG_SYMBOLS = ["rtlws_long_supported", "rtlws_long_open", "rtlws_long_workspace_bytes", "rtlws_long_run",
+                "rtlws_long_close", "rtlws_long_last_error"]
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -109,6 +114,7 @@ SYNTH_SYMBOLS = ["rtl_init", "rtl_set_frequency", "rtl_set_sample_rate", "rtl_se
                  "signal_source_remove_callbacks", "signal_source_stop"]
 
 _hip = None
+_long = None
 _amd = None
 _cbb = None
 
@@ -141,6 +147,8 @@ def hip_lib():
         L.rtlws_engine_create.restype = vp
         L.rtlws_engine_destroy.argtypes = [vp]
         L.rtlws_engine_device.argtypes = [vp]
+        L.rtlws_engine_stream.argtypes = [vp]
+        L.rtlws_engine_stream.restype = vp
         L.rtlws_engine_prepare.argtypes = [vp, i]
         L.rtlws_engine_prepare_f64.argtypes = [vp, i]
         L.rtlws_engine_set_option.argtypes = [vp, C.c_char_p, i]
@@ -185,10 +193,32 @@ def hip_lib():
     return _hip
 
 
+def long_lib():
+    """librtlws_long.so (include/rtlws_long.h); it needs librtlws_hip.so's engine."""
+    global _long
+    if _long is None:
+        hip_lib()
+        _need(LONG_LIB)
+        L = C.CDLL(LONG_LIB, mode=C.RTLD_GLOBAL)
+        vp, l = C.c_void_p, C.c_long
+        L.rtlws_long_supported.argtypes = [C.POINTER(SpectraDesc)]
+        L.rtlws_long_open.argtypes = [vp, C.POINTER(SpectraDesc), l]
+        L.rtlws_long_open.restype = vp
+        L.rtlws_long_workspace_bytes.argtypes = [vp]
+        L.rtlws_long_workspace_bytes.restype = C.c_size_t
+        L.rtlws_long_run.argtypes = [vp, vp, l, vp, vp]
+        L.rtlws_long_close.argtypes = [vp]
+        L.rtlws_long_close.restype = None
+        L.rtlws_long_last_error.restype = C.c_char_p
+        _long = L
+    return _long
+
+
 def amd_lib():
     global _amd
     if _amd is None:
         hip_lib()
+        long_lib()
         _need(AMD_LIB)
         L = C.CDLL(AMD_LIB)
         vp, i = C.c_void_p, C.c_int
@@ -243,6 +273,10 @@ def last_error():
     return hip_lib().rtlws_last_error().decode()
 
 
+def long_last_error():
+    return long_lib().rtlws_long_last_error().decode()
+
+
 def host_error():
     """(count, first message) of include/rtlws_host.h's sticky failure record."""
     L = amd_lib()
@@ -295,6 +329,43 @@ class DevBuf:
             self.free()
         except Exception:
             pass
+
+
+class LongPlan:
+    """rtlws_long_plan* of include/rtlws_long.h: one descriptor, tables and workspace for up to max_frames frames
+    per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+
+    def __init__(self, eng, desc, max_frames=1):
+        self.eng, self.desc = eng, desc
+        self.h = long_lib().rtlws_long_open(eng.h if eng is not None else None, C.byref(desc), int(max_frames))
+        if not self.h:
+            raise RuntimeError("rtlws_long_open failed: %s" % long_last_error())
+
+    @property
+    def workspace_bytes(self):
+        return long_lib().rtlws_long_workspace_bytes(self.h)
+
+    def run(self, d_in, nframes, d_out, stream=None, check=True):
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = long_lib().rtlws_long_run(self.h, ptr(d_in), int(nframes), ptr(d_out), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_long_run failed (rc=%d): %s" % (rc, long_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            long_lib().rtlws_long_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def long_supported(desc):
+    return long_lib().rtlws_long_supported(C.byref(desc))
 
 
 class Engine:
@@ -445,6 +516,31 @@ class Engine:
         res = self.download(d_out, out_dtype, (rows, n_fft))
         d_in.free()
         d_out.free()
+        return res
+
+
+    def spectra_long(self, data, n_fft, k_avg=1, input="cu8", output="power_sum", gain_db=0, rows_f32=False,
+                     max_frames=None):
+        """Engine.spectra for 2^14 .. 2^20-point frames (include/rtlws_long.h): host arrays in, f64 rows out
+        (rows_f32=True: the same arithmetic, rows rounded once to f32).  max_frames: the plan's group size
+        (default: the whole batch)."""
+        desc = make_desc(n_fft, k_avg, input, "rect", output, 0, gain_db, FLAG_ROWS_F32 if rows_f32 else 0)
+        data = np.ascontiguousarray(data)
+        per_sample = {"cu8": 2, "cs32": 8, "rf32": 4}[input]
+        nframes = data.nbytes // (per_sample * n_fft)
+        assert nframes * per_sample * n_fft == data.nbytes
+        rows = nframes // k_avg
+        out_dtype = np.uint8 if output == "payload_u8" else (np.float32 if rows_f32 else np.float64)
+        plan = LongPlan(self, desc, nframes if max_frames is None else max_frames)
+        d_in = self.upload(data)
+        d_out = self.alloc(max(rows, 1) * n_fft * np.dtype(out_dtype).itemsize)
+        try:
+            plan.run(d_in, nframes, d_out)
+            res = self.download(d_out, out_dtype, (rows, n_fft))
+        finally:
+            plan.close()
+            d_in.free()
+            d_out.free()
         return res
 
 
