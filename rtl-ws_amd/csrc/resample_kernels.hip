@@ -14,6 +14,7 @@
 
 #include "rtlws_internal.h"
 #include "cic_lds.h"
+#include "fm_math.h"
 
 namespace rtlws {
 
@@ -127,33 +128,6 @@ hipError_t launch_cic_block_sums(int R, const void* d_src, long dst_len, void* d
     return hipGetLastError();
 }
 
-// atan2_approx of reference src/common_sp.h:40-76, evaluated as the C source
-// reads under IEEE rules: f32 divide/multiply/add without contraction (this
-// file is built with -ffp-contract=off), and the +-M_PI corrections as a
-// double-precision add rounded back to f32.
-__device__ __forceinline__ float atan2_approx_dev(float y, float x)
-{
-    const float pi_by_2 = (float)(3.14159265358979323846 / 2);
-    const double pi_d = 3.14159265358979323846;
-    if (x == 0.0f) {
-        if (y > 0.0f) return pi_by_2;
-        if (y == 0.0f) return 0.0f;
-        return -pi_by_2;
-    }
-    const float z = __fdiv_rn(y, x);
-    if (fabsf(z) < 1.0f) {
-        const float at = __fdiv_rn(z, __fadd_rn(1.0f, __fmul_rn(__fmul_rn(0.28f, z), z)));
-        if (x < 0.0f) {
-            if (y < 0.0f) return (float)((double)at - pi_d);
-            return (float)((double)at + pi_d);
-        }
-        return at;
-    }
-    const float at = __fsub_rn(pi_by_2, __fdiv_rn(z, __fadd_rn(__fmul_rn(z, z), 0.28f)));
-    if (y < 0.0f) return (float)((double)at - pi_d);
-    return at;
-}
-
 // reference src/audio_main.c:110-131: phase, first difference, hard limit.
 // Each thread recomputes its left neighbour's phase (elementwise, no scan).
 __global__ __launch_bounds__(256) void fm_demod_kernel(const int2* __restrict__ iq, long n,
@@ -172,10 +146,7 @@ __global__ __launch_bounds__(256) void fm_demod_kernel(const int2* __restrict__ 
             const int2 q = iq[i - 1];
             pp = atan2_approx_dev((float)q.y, (float)q.x);
         }
-        float d = __fsub_rn(ph, pp);
-        if (d > 1.0f) d = 1.0f;
-        else if (d < -1.0f) d = -1.0f;
-        out[i] = d;
+        out[i] = fm_limit_dev(ph, pp);
         if (i == n - 1) *prev_out = ph;
     }
 }
@@ -197,21 +168,11 @@ hipError_t launch_fm_demod(const void* d_iq, long len, const float* d_prev_in, f
 __global__ __launch_bounds__(256) void halfband_kernel(const float* __restrict__ xbuf,
                                                        float* __restrict__ y, long n)
 {
-    // This file is compiled with -ffp-contract=off (Makefile): mul then add, never
-    // fma, for bit parity with an IEEE evaluation of the C expression.
-    const float h0 = 0.01824f, h2 = -0.11614f, h4 = 0.34790f, h5 = 0.5f;   // src/resample.c:4
     const float* x = xbuf + 10;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float* c = x + 2 * i;
-        float acc = __fmul_rn(h5, c[-5]);                    // src/resample.c:57
-        acc = __fadd_rn(acc, __fmul_rn(h0, c[0]));           // k = 0   src/resample.c:60-64
-        acc = __fadd_rn(acc, __fmul_rn(h2, c[-2]));          // k = 2
-        acc = __fadd_rn(acc, __fmul_rn(h4, c[-4]));          // k = 4
-        acc = __fadd_rn(acc, __fmul_rn(h4, c[-6]));          // k = 6
-        acc = __fadd_rn(acc, __fmul_rn(h2, c[-8]));          // k = 8
-        acc = __fadd_rn(acc, __fmul_rn(h0, c[-10]));         // k = 10
-        y[i] = acc;
+        y[i] = halfband_dev(c[-5], c[0], c[-2], c[-4], c[-6], c[-8], c[-10]);   // fm_math.h: mul then add, never fma
     }
 }
 

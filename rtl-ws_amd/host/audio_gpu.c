@@ -1,7 +1,8 @@
 /* audio_gpu.c -- audio_main.h over the HIP shim (replaces reference
- * src/audio_main.c:1-161).  Per decimator block: H2D, fm_demod kernel,
- * half-band, half-band, D2H of len/4 floats; the phase carry and the two
- * 10-sample delay lines stay on the device between calls.
+ * src/audio_main.c:1-161).  Per decimator block: H2D, ONE launch of the fused
+ * chain (rtlws_fm.h: demodulator and both half-bands), D2H of len/4 floats; the
+ * phase carry and the two 10-sample delay lines are the chain's 21-float state,
+ * two buffers on the device, swapped each call.
  */
 #include "audio_main.h"
 
@@ -12,20 +13,19 @@
 
 #include "host_ctx.h"
 #include "resample.h"
+#include "rtlws_fm.h"
 #include "rtlws_hip.h"
 
 #define AUDIO_BUFFER_POOL 50          /* reference src/audio_main.c:11 */
-#define HIST (HALF_BAND_N - 1)
+#define STATE_STRIDE 24               /* floats between the two states (RTLWS_FM_STATE_FLOATS = 21, padded) */
 
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;
 static rtlws_engine* g_eng = NULL;
 static int g_len = 0;                 /* block length the device buffers are sized for */
 static void* g_d_iq = NULL;
-static float* g_d_demod = NULL;       /* HIST history + len samples   */
-static float* g_d_work = NULL;        /* HIST history + len/2 samples */
 static float* g_d_audio = NULL;       /* len/4 samples                */
-static float* g_d_phase = NULL;       /* two floats: carry in / out, swapped each call */
-static int g_phase_idx = 0;
+static float* g_d_state = NULL;       /* two states: in / out, swapped each call; independent of the block length */
+static int g_state_idx = 0;
 static cmplx_s32* g_h_iq = NULL;      /* pinned */
 static float* g_h_audio = NULL;       /* pinned */
 
@@ -37,8 +37,6 @@ static void free_device(void)
 {
     if (!g_eng) return;
     rtlws_dev_free(g_eng, g_d_iq); g_d_iq = NULL;
-    rtlws_dev_free(g_eng, g_d_demod); g_d_demod = NULL;
-    rtlws_dev_free(g_eng, g_d_work); g_d_work = NULL;
     rtlws_dev_free(g_eng, g_d_audio); g_d_audio = NULL;
     rtlws_pinned_free(g_h_iq); g_h_iq = NULL;
     rtlws_pinned_free(g_h_audio); g_h_audio = NULL;
@@ -52,11 +50,23 @@ void audio_init(void)
         if (!g_eng) {                 /* no CPU path; inert audio side, failure recorded (rtlws_host.h) */
             rtlws_host_fail("audio_init", rtlws_last_error());
         } else {
-            g_d_phase = (float*)rtlws_dev_alloc(g_eng, 2 * sizeof(float));
-            rtlws_memset_dev(g_eng, g_d_phase, 0, 2 * sizeof(float), NULL);
-            rtlws_stream_sync(g_eng, NULL);
+            /* zeroed state is the reference's start (src/audio_main.c:77-79) */
+            g_d_state = (float*)rtlws_dev_alloc(g_eng, 2 * STATE_STRIDE * sizeof(float));
+            const char* why = NULL;
+            if (!g_d_state || rtlws_memset_dev(g_eng, g_d_state, 0, 2 * STATE_STRIDE * sizeof(float), NULL) ||
+                rtlws_stream_sync(g_eng, NULL))
+                why = rtlws_last_error();
+            else if (rtlws_fm_prepare(g_eng))
+                why = rtlws_fm_last_error();
+            if (why) {
+                rtlws_host_fail("audio_init", why);
+                rtlws_dev_free(g_eng, g_d_state);
+                g_d_state = NULL;
+                rtlws_engine_destroy(g_eng);
+                g_eng = NULL;
+            }
             g_len = 0;
-            g_phase_idx = 0;
+            g_state_idx = 0;
         }
     }
     /* a second audio_init without audio_close only restarts the queue: the phase
@@ -103,16 +113,12 @@ static int resize_for(int len)
     free_device();
     g_len = len;
     g_d_iq = rtlws_dev_alloc(g_eng, (size_t)len * sizeof(cmplx_s32));
-    g_d_demod = (float*)rtlws_dev_alloc(g_eng, (size_t)(HIST + len) * sizeof(float));
-    g_d_work = (float*)rtlws_dev_alloc(g_eng, (size_t)(HIST + len / 2) * sizeof(float));
     g_d_audio = (float*)rtlws_dev_alloc(g_eng, (size_t)(len / 4 + 1) * sizeof(float));
     g_h_iq = (cmplx_s32*)rtlws_pinned_alloc((size_t)len * sizeof(cmplx_s32));
     g_h_audio = (float*)rtlws_pinned_alloc((size_t)(len / 4 + 1) * sizeof(float));
-    if (!g_d_iq || !g_d_demod || !g_d_work || !g_d_audio || !g_h_iq || !g_h_audio) return -3;
+    if (!g_d_iq || !g_d_audio || !g_h_iq || !g_h_audio) return -3;
     /* reference src/audio_main.c:82-104: a new block length restarts the queue
-     * (delay lines and phase carry are function statics there and survive) */
-    rtlws_memset_dev(g_eng, g_d_demod, 0, HIST * sizeof(float), NULL);
-    rtlws_memset_dev(g_eng, g_d_work, 0, HIST * sizeof(float), NULL);
+     * (delay lines and phase carry are function statics there and survive: g_d_state is not touched) */
     g_audio_len = (len / 2) / 2;
     for (i = 0; i < AUDIO_BUFFER_POOL; i++) {
         free(g_pool[i]);
@@ -124,7 +130,7 @@ static int resize_for(int len)
 
 void audio_fm_demodulator(const cmplx_s32* signal, int len)
 {
-    const int half = len / 2, quarter = half / 2;
+    const int quarter = (len / 2) / 2;
     int rc = 0, have_buf;
     if (len <= 0) return;
     pthread_mutex_lock(&g_mu);
@@ -133,44 +139,31 @@ void audio_fm_demodulator(const cmplx_s32* signal, int len)
         rtlws_host_fail("audio_fm_demodulator", "no engine (audio_init not called, or no usable HIP device)");
         return;
     }
-    if (g_len != len) {
-        float hist1[HIST], hist2[HIST];
-        int have = g_len > 0;
-        /* carry the delay lines over a change of block length, as the
-         * reference's statics do */
-        if (have) {
-            rtlws_copy_d2h(g_eng, hist1, g_d_demod, sizeof hist1, NULL);
-            rtlws_copy_d2h(g_eng, hist2, g_d_work, sizeof hist2, NULL);
-            rtlws_stream_sync(g_eng, NULL);
-        }
-        rc = resize_for(len);
-        if (!rc && have) {
-            rtlws_copy_h2d(g_eng, g_d_demod, hist1, sizeof hist1, NULL);
-            rtlws_copy_h2d(g_eng, g_d_work, hist2, sizeof hist2, NULL);
-            rtlws_stream_sync(g_eng, NULL);
-        }
-    }
+    if (g_len != len) rc = resize_for(len);
     /* reference src/audio_main.c:137-142: the second half-band runs -- and its delay
      * line advances -- only when a pool buffer is free to take its output; a
      * block that meets an exhausted pool leaves delay line 2 untouched */
     have_buf = g_q_count < AUDIO_BUFFER_POOL;
     if (!rc) {
-        float* prev_in = g_d_phase + g_phase_idx;
-        float* prev_out = g_d_phase + (1 - g_phase_idx);
+        const float* st_in = g_d_state + g_state_idx * STATE_STRIDE;
+        float* st_out = g_d_state + (1 - g_state_idx) * STATE_STRIDE;
+        const char* why = NULL;
         memcpy(g_h_iq, signal, (size_t)len * sizeof(cmplx_s32));
-        if (rtlws_copy_h2d(g_eng, g_d_iq, g_h_iq, (size_t)len * sizeof(cmplx_s32), NULL) ||
-            rtlws_fm_demod(g_eng, g_d_iq, len, prev_in, prev_out, g_d_demod + HIST, NULL) ||
-            rtlws_halfband(g_eng, g_d_demod, g_d_work + HIST, half, NULL) ||              /* :133 */
-            /* delay line 1 <- last 10 inputs of the stage (src/resample.c:66) */
-            rtlws_copy_d2d(g_eng, g_d_demod, g_d_demod + 2 * half, HIST * sizeof(float), NULL) ||
-            (have_buf &&
-             (rtlws_halfband(g_eng, g_d_work, g_d_audio, quarter, NULL) ||               /* :139 */
-              rtlws_copy_d2d(g_eng, g_d_work, g_d_work + 2 * quarter, HIST * sizeof(float), NULL) ||
-              rtlws_copy_d2h(g_eng, g_h_audio, g_d_audio, (size_t)quarter * sizeof(float), NULL))) ||
-            rtlws_stream_sync(g_eng, NULL))
+        if (rtlws_copy_h2d(g_eng, g_d_iq, g_h_iq, (size_t)len * sizeof(cmplx_s32), NULL))
+            rc = -3;
+        /* :110-142 in one launch; have_buf == 0 leaves delay line 2 as it is */
+        else if ((rc = rtlws_fm_audio_blocks(g_eng, g_d_iq, len, 1, st_in, st_out, have_buf, g_d_audio, NULL)) != 0)
+            why = rtlws_fm_last_error();
+        else if ((have_buf && rtlws_copy_d2h(g_eng, g_h_audio, g_d_audio, (size_t)quarter * sizeof(float), NULL)) ||
+                 rtlws_stream_sync(g_eng, NULL))
             rc = -3;
         else
-            g_phase_idx = 1 - g_phase_idx;
+            g_state_idx = 1 - g_state_idx;
+        if (why) {
+            pthread_mutex_unlock(&g_mu);
+            rtlws_host_fail("audio_fm_demodulator", why);
+            return;
+        }
     }
     if (rc) {                         /* void signature: the block yields no audio, the failure is recorded */
         pthread_mutex_unlock(&g_mu);
@@ -191,8 +184,8 @@ void audio_close(void)
     pthread_mutex_lock(&g_mu);
     free_device();
     if (g_eng) {
-        rtlws_dev_free(g_eng, g_d_phase);
-        g_d_phase = NULL;
+        rtlws_dev_free(g_eng, g_d_state);
+        g_d_state = NULL;
         rtlws_engine_destroy(g_eng);
         g_eng = NULL;
     }

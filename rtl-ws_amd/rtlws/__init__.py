@@ -7,6 +7,7 @@ fail loudly.
 
   Engine ............ include/rtlws_hip.h (batch API on device buffers)
   LongPlan .......... include/rtlws_long.h (f64 spectra of 2^14 .. 2^20-point frames)
+  Engine.fm_audio_blocks[_cu8]  include/rtlws_fm.h (the FM receive chain in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -26,6 +27,7 @@ HIP_LIB = os.environ.get("RTLWS_HIP_LIB") or os.path.join(LIB_DIR, "librtlws_hip
 # RTLWS_AMD_LIB: an instrumented build of the C host layer (tests/tools/asan_host_cpu.sh)
 AMD_LIB = os.environ.get("RTLWS_AMD_LIB") or os.path.join(LIB_DIR, "librtlws_amd.so")
 LONG_LIB = os.path.join(LIB_DIR, "librtlws_long.so")     # include/rtlws_long.h
+FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -83,6 +85,9 @@ HIP_SYMBOLS = [
 ]
 LONG_SYMBOLS = ["rtlws_long_supported", "rtlws_long_open", "rtlws_long_workspace_bytes", "rtlws_long_run",
                 "rtlws_long_close", "rtlws_long_last_error"]
+FM_SYMBOLS = ["rtlws_fm_supported", "rtlws_fm_grid", "rtlws_fm_prepare", "rtlws_fm_audio_blocks",
+              "rtlws_fm_audio_blocks_cu8", "rtlws_fm_last_error"]
+FM_STATE_FLOATS = 21       # rtlws_fm.h: phase carry, delay line 1, delay line 2
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -115,6 +120,7 @@ SYNTH_SYMBOLS = ["rtl_init", "rtl_set_frequency", "rtl_set_sample_rate", "rtl_se
 
 _hip = None
 _long = None
+_fm = None
 _amd = None
 _cbb = None
 
@@ -214,11 +220,30 @@ def long_lib():
     return _long
 
 
+def fm_lib():
+    """librtlws_fm.so (include/rtlws_fm.h); it needs librtlws_hip.so's engine."""
+    global _fm
+    if _fm is None:
+        hip_lib()
+        _need(FM_LIB)
+        L = C.CDLL(FM_LIB, mode=C.RTLD_GLOBAL)
+        vp, i, l, ip = C.c_void_p, C.c_int, C.c_long, C.POINTER(C.c_int)
+        L.rtlws_fm_supported.argtypes = [i, l, i]
+        L.rtlws_fm_grid.argtypes = [i, l, i, ip, ip, ip, ip]
+        L.rtlws_fm_prepare.argtypes = [vp]
+        L.rtlws_fm_audio_blocks.argtypes = [vp, vp, i, l, vp, vp, i, vp, vp]
+        L.rtlws_fm_audio_blocks_cu8.argtypes = [vp, i, vp, i, l, vp, vp, i, vp, vp, vp]
+        L.rtlws_fm_last_error.restype = C.c_char_p
+        _fm = L
+    return _fm
+
+
 def amd_lib():
     global _amd
     if _amd is None:
         hip_lib()
         long_lib()
+        fm_lib()
         _need(AMD_LIB)
         L = C.CDLL(AMD_LIB)
         vp, i = C.c_void_p, C.c_int
@@ -275,6 +300,21 @@ def last_error():
 
 def long_last_error():
     return long_lib().rtlws_long_last_error().decode()
+
+
+def fm_last_error():
+    return fm_lib().rtlws_fm_last_error().decode()
+
+
+def fm_supported(block_len, nblocks=1, cic_r=0):
+    return fm_lib().rtlws_fm_supported(int(block_len), int(nblocks), int(cic_r))
+
+
+def fm_grid(block_len, nblocks, cic_r=0):
+    """rtlws_fm_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
+    b, t, s, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = fm_lib().rtlws_fm_grid(int(block_len), int(nblocks), int(cic_r), C.byref(b), C.byref(t), C.byref(s), C.byref(a))
+    return rc, b.value, t.value, s.value, a.value
 
 
 def host_error():
@@ -496,6 +536,46 @@ class Engine:
         rc = hip_lib().rtlws_spectra_grid(self.h, C.byref(desc), int(nframes), C.byref(b),
                                           C.byref(t), C.byref(l))
         return rc, b.value, t.value, l.value
+
+    # -- include/rtlws_fm.h: host arrays in, (audio, new state[, decimated samples]) out ----
+    def _fm_run(self, call, src, nsamples, block_len, state, run_stage2, want_dec):
+        nblocks = nsamples // block_len if block_len > 0 else 0
+        assert block_len <= 0 or nblocks * block_len == nsamples
+        state = np.ascontiguousarray(state, dtype=np.float32)
+        assert state.size == FM_STATE_FLOATS
+        naudio = max(nblocks * (block_len // 4), 0)
+        d_src = self.upload(src) if src.nbytes else self.alloc(16)
+        d_st = self.upload(np.concatenate([state, np.zeros(3, np.float32), np.zeros(FM_STATE_FLOATS, np.float32)]))
+        d_audio = self.alloc(max(naudio, 1) * 4)
+        d_dec = self.alloc(max(nsamples, 1) * 8) if want_dec else None
+        try:
+            rc = call(d_src.ptr, nblocks, d_st.ptr, d_st.ptr + 96, d_audio.ptr, d_dec.ptr if d_dec else None)
+            if rc != 0:
+                raise RuntimeError("rtlws_fm_audio_blocks failed (rc=%d): %s" % (rc, fm_last_error()))
+            audio = self.download(d_audio, np.float32, (naudio,)) if run_stage2 and naudio else np.zeros(0, np.float32)
+            new_state = self.download(d_st, np.float32, (24 + FM_STATE_FLOATS,))[24:]
+            dec = self.download(d_dec, np.int32, (nsamples, 2)) if d_dec and nsamples else None
+        finally:
+            for b in (d_src, d_st, d_audio, d_dec):
+                if b:
+                    b.free()
+        return (audio, new_state, dec) if want_dec else (audio, new_state)
+
+    def fm_audio_blocks(self, iq, block_len, state, run_stage2=True):
+        """rtlws_fm_audio_blocks: iq int32 [nblocks * block_len, 2], state f32[21] -> (audio f32, new state)."""
+        iq = np.ascontiguousarray(iq, dtype=np.int32).reshape(-1, 2)
+        return self._fm_run(lambda s, nb, si, so, a, d: fm_lib().rtlws_fm_audio_blocks(
+            self.h, s, int(block_len), nb, si, so, int(bool(run_stage2)), a, None),
+            iq, iq.shape[0], int(block_len), state, run_stage2, False)
+
+    def fm_audio_blocks_cu8(self, iq, cic_r, block_len, state, run_stage2=True, want_dec=False):
+        """rtlws_fm_audio_blocks_cu8: iq uint8 [nblocks * block_len * cic_r, 2] -> (audio, new state[, decimated int32])."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        n = iq.shape[0] // cic_r if cic_r > 0 else 0
+        assert cic_r <= 0 or n * cic_r == iq.shape[0]
+        return self._fm_run(lambda s, nb, si, so, a, d: fm_lib().rtlws_fm_audio_blocks_cu8(
+            self.h, int(cic_r), s, int(block_len), nb, si, so, int(bool(run_stage2)), a, d, None),
+            iq, n, int(block_len), state, run_stage2, want_dec)
 
     # -- convenience: host arrays in, host arrays out ------------------------
     def spectra(self, data, n_fft, k_avg=1, input="cu8", window="rect", output="power_sum",
