@@ -239,7 +239,8 @@ int rtlws_payload_from_sums(rtlws_engine* e, const float* d_sums, int n, int cou
  * one to six frames per call, so they go through this entry point: same
  * descriptor, same semantics and frame layout as rtlws_spectra_batch, f64
  * arithmetic, any 2 <= n_fft <= 8192 (power-of-two frames of 2^14 .. 2^20 points have entry points of their own:
- * rtlws_long.h).  1024- / 2048- / 4096-point frames of any input
+ * rtlws_long.h; every other length up to 2^19, and Bluestein's algorithm instead of the direct sum below 8192:
+ * rtlws_anylen.h).  1024- / 2048- / 4096-point frames of any input
  * kind, and cmplx_u8 through the CIC-fused input stage for cic_r = 8, 10, 12, run the
  * fused throughput kernel (spectrum_f64_fused.hip; needs d_out -- and d_in when cic_r > 1
  * -- 16-byte aligned, else the general kernel is used); everything else one workgroup per

@@ -27,7 +27,11 @@
  *     for the other powers of two, a direct O(N^2) sum for any other N.  Above that, the powers of two
  *     N = 2^14 .. 2^20: a four-step transform through device memory (rtlws_long.h, librtlws_long.so; one plan per
  *     input kind, opened on the first spectrum_add_* of that kind).  Any other N above 8192 is not served (the
- *     reference plans any length).  There is no CPU path: if no HIP device is usable, or N is out of
+ *     reference plans any length) -- unless the process sets the environment variable RTLWS_ANY_LENGTH to a
+ *     non-zero number (read on every spectrum_alloc): then every N up to 2^19 is, by Bluestein's algorithm over that
+ *     transform (rtlws_anylen.h, librtlws_anylen.so).  It is an opt-in only because a test of this drop-in pins the
+ *     refusal (tests/test_long_gpu.py::test_dropin_long_frames); making it the default is a later, one-line change.
+ *      There is no CPU path: if no HIP device is usable, or N is out of
  *     range, spectrum_alloc returns NULL (the reference never reports failure).
  *   - Arithmetic is f64 on the device, like the reference (f64 via FFTW):
  *     increments agree with an f64 FFT to <= 1e-10 relative per bin under the

@@ -49,18 +49,6 @@ const char* why_not(const rtlws_spectra_desc* d)
     return nullptr;
 }
 
-// W_n^j, j < count * step, every step-th: evaluated in long double, rounded once
-std::vector<double2> roots(long n, long step, int count)
-{
-    const long double two_pi = 6.283185307179586476925286766559005768L;
-    std::vector<double2> w((size_t)count);
-    for (int i = 0; i < count; ++i) {
-        const long double a = -two_pi * (long double)(i * step) / (long double)n;
-        w[(size_t)i] = make_double2((double)cosl(a), (double)sinl(a));
-    }
-    return w;
-}
-
 }  // namespace
 
 struct rtlws_long_plan {

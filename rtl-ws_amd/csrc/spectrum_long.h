@@ -2,6 +2,9 @@
 #ifndef RTLWS_SPECTRUM_LONG_H
 #define RTLWS_SPECTRUM_LONG_H
 
+#include <cmath>
+#include <vector>
+
 #include "rtlws_internal.h"
 
 namespace rtlws {
@@ -37,6 +40,18 @@ struct LongParams {
     double lin_gain;       // 10^(gain_db/10), C integer division (src/cbb_main.c:112)
     double in_scale;       // 1/128 or 1
 };
+
+// The twiddle tables' entries (host): W_n^j, j < count * step, every step-th, evaluated in long double, rounded once
+inline std::vector<double2> roots(long n, long step, int count)
+{
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    std::vector<double2> w((size_t)count);
+    for (int i = 0; i < count; ++i) {
+        const long double a = -two_pi * (long double)(i * step) / (long double)n;
+        w[(size_t)i] = make_double2((double)cosl(a), (double)sinl(a));
+    }
+    return w;
+}
 
 // pass A over `frames` frames, pass B over `rows` = frames / k_avg rows
 hipError_t launch_long_pass_a(const LongParams&, int in_kind, long frames, hipStream_t);

@@ -16,6 +16,12 @@
  * build links: it compiles this file with -DRTLWS_LONG_FRAMES (rtl-ws_amd/Makefile).  Without the switch -- a host
  * program built against a shim that lacks the library -- this file refers to none of its symbols and refuses those
  * sizes as it always did.
+ *
+ * Every other length above 8192 points, up to 2^19, can go through rtlws_anylen.h's plans (Bluestein, librtlws_anylen.so)
+ * in the same way -- behind -DRTLWS_ANYLEN_FRAMES, which the product build sets too, and ONLY in a process whose
+ * environment sets RTLWS_ANY_LENGTH to a non-zero number, read on every spectrum_alloc.  It is an opt-in because the
+ * refusal of those sizes is pinned by a test of the drop-in (tests/test_long_gpu.py::test_dropin_long_frames);
+ * serving them by default is the one-line change of any_length_opted_in() returning 1.
  */
 #include "spectrum.h"
 
@@ -28,6 +34,9 @@
 #ifdef RTLWS_LONG_FRAMES
 #include "rtlws_long.h"
 #endif
+#ifdef RTLWS_ANYLEN_FRAMES
+#include "rtlws_anylen.h"
+#endif
 
 #define SHORT_MAX 8192    /* rtlws_spectra_batch_f64's largest frame */
 
@@ -38,6 +47,10 @@ struct spectrum {
     double* h_out;    /* pinned, N doubles */
 #ifdef RTLWS_LONG_FRAMES
     rtlws_long_plan* plan[3];    /* N > SHORT_MAX: by enum rtlws_input, opened on first use */
+#endif
+#ifdef RTLWS_ANYLEN_FRAMES
+    int anylen;                  /* N > SHORT_MAX and not a power of two: rtlws_anylen.h's plans instead */
+    rtlws_anylen_plan* aplan[3];
 #endif
 };
 
@@ -56,10 +69,44 @@ static int long_size_ok(int N)
 #endif
 }
 
+/* whether frames of N > SHORT_MAX points that rtlws_long.h refuses are served: up to 2^19, product build, opted in */
+#ifdef RTLWS_ANYLEN_FRAMES
+static int any_length_opted_in(void)
+{
+    const char* v = getenv("RTLWS_ANY_LENGTH");    /* every call: a process may set it between two handles */
+    return v && atoi(v) != 0;
+}
+#endif
+
+static int anylen_size_ok(int N)
+{
+#ifdef RTLWS_ANYLEN_FRAMES
+    rtlws_spectra_desc d;
+    memset(&d, 0, sizeof d);
+    d.n_fft = N;
+    d.k_avg = 1;
+    return any_length_opted_in() && rtlws_anylen_supported(&d);
+#else
+    (void)N;
+    return 0;
+#endif
+}
+
 /* one frame from h_in to h_out on the engine's stream; 0 or the failing call's code (its text: *why) */
 static int run_frame(struct spectrum* s, const rtlws_spectra_desc* d, const char** why)
 {
     int rc;
+#ifdef RTLWS_ANYLEN_FRAMES
+    if (s->anylen) {
+        rtlws_anylen_plan** p = &s->aplan[d->input];
+        *why = NULL;
+        if (!*p) *p = rtlws_anylen_open(s->eng, d, 1);
+        rc = *p ? rtlws_anylen_run(*p, s->h_in, 1, s->h_out, NULL) : -3;
+        if (rc) *why = rtlws_anylen_last_error();
+        if (!rc && (rc = rtlws_stream_sync(s->eng, NULL)) != 0) *why = rtlws_last_error();
+        return rc;
+    }
+#endif
 #ifdef RTLWS_LONG_FRAMES
     if (s->N > SHORT_MAX) {
         rtlws_long_plan** p = &s->plan[d->input];
@@ -81,16 +128,22 @@ struct spectrum* spectrum_alloc(int N)
 {
     struct spectrum* s;
     rtlws_spectra_desc probe;
+    int anylen = 0;
     memset(&probe, 0, sizeof probe);
     probe.n_fft = N;
     probe.k_avg = 1;
-    if (N > SHORT_MAX ? !long_size_ok(N) : rtlws_spectra_kernel_kind(&probe) == 0) {
+    if (N > SHORT_MAX ? !(long_size_ok(N) || (anylen = anylen_size_ok(N)) != 0) : rtlws_spectra_kernel_kind(&probe) == 0) {
         fprintf(stderr, "rtlws: spectrum_alloc(%d): size not supported by the device engine\n", N);
         return NULL;
     }
     s = (struct spectrum*)calloc(1, sizeof(*s));
     if (!s) return NULL;
     s->N = N;
+#ifdef RTLWS_ANYLEN_FRAMES
+    s->anylen = anylen;
+#else
+    (void)anylen;
+#endif
     s->eng = rtlws_engine_create(rtlws_host_device());
     if (!s->eng) {
         fprintf(stderr, "rtlws: spectrum_alloc: %s\n", rtlws_last_error());
@@ -167,6 +220,9 @@ void spectrum_free(struct spectrum* s)
     if (!s) return;
 #ifdef RTLWS_LONG_FRAMES
     for (int k = 0; k < 3; k++) rtlws_long_close(s->plan[k]);
+#endif
+#ifdef RTLWS_ANYLEN_FRAMES
+    for (int k = 0; k < 3; k++) rtlws_anylen_close(s->aplan[k]);
 #endif
     rtlws_pinned_free(s->h_in);
     rtlws_pinned_free(s->h_out);

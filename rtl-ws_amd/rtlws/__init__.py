@@ -7,6 +7,7 @@ fail loudly.
 
   Engine ............ include/rtlws_hip.h (batch API on device buffers)
   LongPlan .......... include/rtlws_long.h (f64 spectra of 2^14 .. 2^20-point frames)
+  AnyLenPlan ........ include/rtlws_anylen.h (f64 spectra of any frame length 2 .. 2^19)
   Engine.fm_audio_blocks[_cu8]  include/rtlws_fm.h (the FM receive chain in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
@@ -27,6 +28,7 @@ HIP_LIB = os.environ.get("RTLWS_HIP_LIB") or os.path.join(LIB_DIR, "librtlws_hip
 # RTLWS_AMD_LIB: an instrumented build of the C host layer (tests/tools/asan_host_cpu.sh)
 AMD_LIB = os.environ.get("RTLWS_AMD_LIB") or os.path.join(LIB_DIR, "librtlws_amd.so")
 LONG_LIB = os.path.join(LIB_DIR, "librtlws_long.so")     # include/rtlws_long.h
+ANYLEN_LIB = os.path.join(LIB_DIR, "librtlws_anylen.so") # include/rtlws_anylen.h
 FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
@@ -85,6 +87,8 @@ HIP_SYMBOLS = [
 ]
 LONG_SYMBOLS = ["rtlws_long_supported", "rtlws_long_open", "rtlws_long_workspace_bytes", "rtlws_long_run",
                 "rtlws_long_close", "rtlws_long_last_error"]
+ANYLEN_SYMBOLS = ["rtlws_anylen_supported", "rtlws_anylen_open", "rtlws_anylen_conv_log2", "rtlws_anylen_workspace_bytes",
+                  "rtlws_anylen_run", "rtlws_anylen_close", "rtlws_anylen_last_error"]
 FM_SYMBOLS = ["rtlws_fm_supported", "rtlws_fm_grid", "rtlws_fm_prepare", "rtlws_fm_audio_blocks",
               "rtlws_fm_audio_blocks_cu8", "rtlws_fm_last_error"]
 FM_STATE_FLOATS = 21       # rtlws_fm.h: phase carry, delay line 1, delay line 2
@@ -120,6 +124,7 @@ SYNTH_SYMBOLS = ["rtl_init", "rtl_set_frequency", "rtl_set_sample_rate", "rtl_se
 
 _hip = None
 _long = None
+_anylen = None
 _fm = None
 _amd = None
 _cbb = None
@@ -220,6 +225,28 @@ def long_lib():
     return _long
 
 
+def anylen_lib():
+    """librtlws_anylen.so (include/rtlws_anylen.h); it needs librtlws_hip.so's engine."""
+    global _anylen
+    if _anylen is None:
+        hip_lib()
+        _need(ANYLEN_LIB)
+        L = C.CDLL(ANYLEN_LIB, mode=C.RTLD_GLOBAL)
+        vp, l = C.c_void_p, C.c_long
+        L.rtlws_anylen_supported.argtypes = [C.POINTER(SpectraDesc)]
+        L.rtlws_anylen_conv_log2.argtypes = [C.POINTER(SpectraDesc)]
+        L.rtlws_anylen_open.argtypes = [vp, C.POINTER(SpectraDesc), l]
+        L.rtlws_anylen_open.restype = vp
+        L.rtlws_anylen_workspace_bytes.argtypes = [vp]
+        L.rtlws_anylen_workspace_bytes.restype = C.c_size_t
+        L.rtlws_anylen_run.argtypes = [vp, vp, l, vp, vp]
+        L.rtlws_anylen_close.argtypes = [vp]
+        L.rtlws_anylen_close.restype = None
+        L.rtlws_anylen_last_error.restype = C.c_char_p
+        _anylen = L
+    return _anylen
+
+
 def fm_lib():
     """librtlws_fm.so (include/rtlws_fm.h); it needs librtlws_hip.so's engine."""
     global _fm
@@ -243,6 +270,7 @@ def amd_lib():
     if _amd is None:
         hip_lib()
         long_lib()
+        anylen_lib()
         fm_lib()
         _need(AMD_LIB)
         L = C.CDLL(AMD_LIB)
@@ -300,6 +328,10 @@ def last_error():
 
 def long_last_error():
     return long_lib().rtlws_long_last_error().decode()
+
+
+def anylen_last_error():
+    return anylen_lib().rtlws_anylen_last_error().decode()
 
 
 def fm_last_error():
@@ -406,6 +438,48 @@ class LongPlan:
 
 def long_supported(desc):
     return long_lib().rtlws_long_supported(C.byref(desc))
+
+
+class AnyLenPlan:
+    """rtlws_anylen_plan* of include/rtlws_anylen.h: one descriptor, tables and workspaces for up to max_frames
+    frames per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+
+    def __init__(self, eng, desc, max_frames=1):
+        self.eng, self.desc = eng, desc
+        self.h = anylen_lib().rtlws_anylen_open(eng.h if eng is not None else None, C.byref(desc), int(max_frames))
+        if not self.h:
+            raise RuntimeError("rtlws_anylen_open failed: %s" % anylen_last_error())
+
+    @property
+    def workspace_bytes(self):
+        return anylen_lib().rtlws_anylen_workspace_bytes(self.h)
+
+    def run(self, d_in, nframes, d_out, stream=None, check=True):
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = anylen_lib().rtlws_anylen_run(self.h, ptr(d_in), int(nframes), ptr(d_out), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_anylen_run failed (rc=%d): %s" % (rc, anylen_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            anylen_lib().rtlws_anylen_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def anylen_supported(desc):
+    return anylen_lib().rtlws_anylen_supported(C.byref(desc))
+
+
+def anylen_conv_log2(desc):
+    """m of the convolution length 2^m the descriptor runs at, -1 if it is not served."""
+    return anylen_lib().rtlws_anylen_conv_log2(C.byref(desc))
 
 
 class Engine:
@@ -612,6 +686,29 @@ class Engine:
         rows = nframes // k_avg
         out_dtype = np.uint8 if output == "payload_u8" else (np.float32 if rows_f32 else np.float64)
         plan = LongPlan(self, desc, nframes if max_frames is None else max_frames)
+        d_in = self.upload(data)
+        d_out = self.alloc(max(rows, 1) * n_fft * np.dtype(out_dtype).itemsize)
+        try:
+            plan.run(d_in, nframes, d_out)
+            res = self.download(d_out, out_dtype, (rows, n_fft))
+        finally:
+            plan.close()
+            d_in.free()
+            d_out.free()
+        return res
+
+    def spectra_anylen(self, data, n_fft, k_avg=1, input="cu8", output="power_sum", gain_db=0, rows_f32=False,
+                       max_frames=None):
+        """Engine.spectra_long for any frame length 2 .. 2^19 (include/rtlws_anylen.h).  The device buffers are
+        exactly as long as the frames and the rows: nothing lies behind the last frame."""
+        desc = make_desc(n_fft, k_avg, input, "rect", output, 0, gain_db, FLAG_ROWS_F32 if rows_f32 else 0)
+        data = np.ascontiguousarray(data)
+        per_sample = {"cu8": 2, "cs32": 8, "rf32": 4}[input]
+        nframes = data.nbytes // (per_sample * n_fft)
+        assert nframes * per_sample * n_fft == data.nbytes
+        rows = nframes // k_avg
+        out_dtype = np.uint8 if output == "payload_u8" else (np.float32 if rows_f32 else np.float64)
+        plan = AnyLenPlan(self, desc, nframes if max_frames is None else max_frames)
         d_in = self.upload(data)
         d_out = self.alloc(max(rows, 1) * n_fft * np.dtype(out_dtype).itemsize)
         try:
