@@ -1,0 +1,235 @@
+// ddc_bank.hip -- a bank of digital down-converters in ONE pass over a cmplx_u8 capture (include/rtlws_ddc.h):
+// every channel c mixes the capture with exp(-2 pi i k_c n / P) and block-sums R samples, all in integers.
+// 2 R bytes in and 8 C bytes out per decimated sample, the capture read once whatever C is.
+//
+// The arithmetic (P = 2^16, T[j] = rint(2^14 (cos, sin)(2 pi j / P)) as int16 pairs):
+//   U[c][m]   = sum_{n<R} (x[m R + n] - 128 (1 + i)) * conj(T[k_c n mod P])            int32, inside the block
+//   out[c][m] = (U[c][m] * conj(T[k_c R g mod P]) + 2^27 (1 + i)) >> 28,  g = first + m  int64, one per output
+// The inner sum is a dense int8 contraction on the matrix pipe.  D = A B with v_mfma_i32_16x16x32_i8:
+//   B (32 x 16)  column j = decimated sample m0 + j, k = byte of its block of 2 R bytes (re, im interleaved) with
+//                the offset binary taken off by ^ 0x80: lane l holds column l & 15, bytes 8 (l >> 4) .. + 7 --
+//                its own eight consecutive bytes of the capture, straight from the load;
+//   A (16 x 32)  row 2 c' = Re, 2 c' + 1 = Im of channel c' of a column tile of eight channels: (c_n, s_n) and
+//                (-s_n, c_n) at the bytes of sample n.  An int16 phasor is w = 256 wh + wl with wl in -128 .. 127
+//                and wh in -64 .. 64: two int8 operands, D = 256 (A_h B) + A_l B exactly;
+//   D            lane l holds column l & 15 (the sample) and rows 4 (l >> 4) + i: Re and Im of TWO channels --
+//                a complex value stays on its lane, and the 16 lanes of a row group store 128 consecutive bytes
+//                of one channel's stream.
+// R <= 16 is one K step; the generic kernel takes ceil(R / 16) steps into the same accumulators.  A wavefront
+// derives its phasor operands from T itself (R = 8, 10, 12: in registers; any R: the workgroup's, in LDS), so
+// a retune is nothing but other kernel arguments.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ddc_bank.h"
+
+namespace rtlws {
+namespace ddc {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int nt_i2 __attribute__((ext_vector_type(2)));
+typedef unsigned nt_u2 __attribute__((ext_vector_type(2)));
+
+// T[phase mod P] as (cos, sin)
+__device__ __forceinline__ int2 phasor(const uint32_t* __restrict__ table, unsigned phase)
+{
+    const uint32_t e = table[phase & (unsigned)(P - 1)];
+    return make_int2((int)(int16_t)(e & 0xffffu), (int)e >> 16);
+}
+
+// The A operands of lane `lane` for column tile ct and K step ks: {high bytes (2 dwords), low bytes (2 dwords)}
+// of the phasors of samples n = 16 ks + 4 (lane >> 4) + t, t < 4, on row lane & 15.  Zero beyond R and beyond C.
+__device__ __forceinline__ uint4 phasor_operand(const BankParams& p, int ct, int ks, int lane)
+{
+    const int r = lane & 15, q = lane >> 4;
+    const int c = 8 * ct + (r >> 1);
+    const bool im_row = r & 1;
+    const int k = p.words[c & (MAX_CH - 1)];
+    unsigned hi[2] = {0u, 0u}, lo[2] = {0u, 0u};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int n = 16 * ks + 4 * q + t;
+        int w_re = 0, w_im = 0;                          // what multiplies the sample's re byte and its im byte
+        if (c < p.nch && n < p.cic_r) {
+            const int2 e = phasor(p.table, (unsigned)(k * n));
+            w_re = im_row ? -e.y : e.x;
+            w_im = im_row ? e.x : e.y;
+        }
+        const int re_l = (int8_t)w_re, im_l = (int8_t)w_im;
+        const unsigned pair_l = ((unsigned)re_l & 0xffu) | (((unsigned)im_l & 0xffu) << 8);
+        const unsigned pair_h = ((unsigned)((w_re - re_l) >> 8) & 0xffu) | (((unsigned)((w_im - im_l) >> 8) & 0xffu) << 8);
+        lo[t >> 1] |= pair_l << (16 * (t & 1));
+        hi[t >> 1] |= pair_h << (16 * (t & 1));
+    }
+    return make_uint4(hi[0], hi[1], lo[0], lo[1]);
+}
+
+__device__ __forceinline__ long pack(unsigned lo, unsigned hi) { return (long)(((unsigned long)hi << 32) | lo); }
+
+// Bytes 8 q .. 8 q + 7 of the block of decimated sample m (zero behind the block).  Streamed once: nontemporal.
+template <int RT>
+__device__ __forceinline__ long load_block(const void* src, long m, int q)
+{
+    if constexpr (RT == 8) {                             // 16 bytes: two lanes of eight
+        if (q >= 2) return 0;
+        const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2*>(src) + m * 2 + q);
+        return pack(v.x, v.y);
+    } else if constexpr (RT == 12) {                     // 24 bytes, 8-byte aligned: three lanes of eight
+        if (q >= 3) return 0;
+        const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2*>(src) + m * 3 + q);
+        return pack(v.x, v.y);
+    } else {                                             // R = 10: 20 bytes, 4-byte aligned: dwords 2 q, 2 q + 1 of five
+        static_assert(RT == 10, "compile-time factors: 8, 10, 12");
+        if (q >= 3) return 0;
+        const unsigned* w = reinterpret_cast<const unsigned*>(src) + m * 5 + 2 * q;
+        const unsigned lo = __builtin_nontemporal_load(w);
+        const unsigned hi = q < 2 ? __builtin_nontemporal_load(w + 1) : 0u;
+        return pack(lo, hi);
+    }
+}
+
+// any factor: samples n0 .. n0 + 3 of the block of decimated sample m, two bytes each (zero from sample R on)
+__device__ __forceinline__ long load_any(const void* src, long m, int R, int n0)
+{
+    const uint16_t* s = reinterpret_cast<const uint16_t*>(src) + m * R;
+    unsigned v[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = n0 + t < R ? (unsigned)s[n0 + t] : 0u;
+    return pack(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+}
+
+// The block phasor and the store: this lane's two channels c0, c0 + 1 of decimated sample m.
+__device__ __forceinline__ void emit(const BankParams& p, v4i hi, v4i lo, int c0, unsigned kr0, unsigned kr1, long m)
+{
+    const unsigned g16 = ((unsigned)p.first + (unsigned)m) & 0xffffu;      // only the low 16 bits of k R g matter
+    nt_i2* out = reinterpret_cast<nt_i2*>(p.out);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (c0 + h >= p.nch) continue;
+        const int ur = (int)(((unsigned)hi[2 * h] << 8) + (unsigned)lo[2 * h]);
+        const int ui = (int)(((unsigned)hi[2 * h + 1] << 8) + (unsigned)lo[2 * h + 1]);
+        const int2 e = phasor(p.table, (h ? kr1 : kr0) * g16);
+        const long vr = (long)ur * e.x + (long)ui * e.y + (1L << 27);
+        const long vi = (long)ui * e.x - (long)ur * e.y + (1L << 27);
+        const nt_i2 o = {(int)(vr >> 28), (int)(vi >> 28)};
+        out[(long)(c0 + h) * p.out_stride + m] = o;
+    }
+}
+
+// RT = 8, 10, 12: that factor, one K step, the phasor operands in registers.  RT = 0: any factor 1 .. 128.
+template <int RT>
+__global__ __launch_bounds__(THREADS) void ddc_bank_kernel(const BankParams p)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 15, q = lane >> 4;
+    const int nct = (p.nch + 7) >> 3;
+    const int R = RT ? RT : p.cic_r;
+    const long tile0 = (long)blockIdx.x * TILE_DEC;
+
+    // k_c R mod P of the channels this lane stores
+    unsigned kr[COL_TILES][2];
+#pragma unroll
+    for (int ct = 0; ct < COL_TILES; ++ct)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) kr[ct][h] = (unsigned)(p.words[(8 * ct + 2 * q + h) & (MAX_CH - 1)] * R) & 0xffffu;
+
+    if constexpr (RT != 0) {
+        uint4 a[COL_TILES];
+#pragma unroll
+        for (int ct = 0; ct < COL_TILES; ++ct) a[ct] = ct < nct ? phasor_operand(p, ct, 0, lane) : make_uint4(0, 0, 0, 0);
+
+#pragma unroll 1
+        for (int gi = 0; gi < ROW_TILES / (4 * GROUP); ++gi) {
+            const long m_base = tile0 + (long)((gi * 4 + wave) * GROUP * ROWS);
+            if (m_base >= p.dec_len) break;
+            long b[GROUP];                               // every load of the group in flight
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) {
+                const long m = m_base + i * ROWS + j;
+                b[i] = m < p.dec_len ? load_block<RT>(p.src, m, q) : 0;
+            }
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) {
+                const long m = m_base + i * ROWS + j;
+                if (m_base + i * ROWS < p.dec_len) {
+                    const long x = b[i] ^ (long)0x8080808080808080UL;
+                    const v4i zero = {0, 0, 0, 0};
+#pragma unroll
+                    for (int ct = 0; ct < COL_TILES; ++ct) {
+                        if (ct < nct) {
+                            const v4i hi = __builtin_amdgcn_mfma_i32_16x16x32_i8(pack(a[ct].x, a[ct].y), x, zero, 0, 0, 0);
+                            const v4i lo = __builtin_amdgcn_mfma_i32_16x16x32_i8(pack(a[ct].z, a[ct].w), x, zero, 0, 0, 0);
+                            if (m < p.dec_len) emit(p, hi, lo, 8 * ct + 2 * q, kr[ct][0], kr[ct][1], m);
+                        }
+                    }
+                }
+            }
+        }
+    } else {
+        __shared__ uint4 ops[COL_TILES * K_STEPS * 64];
+        const int nks = (R + 15) >> 4;
+        for (int e = tid; e < nct * nks * 64; e += THREADS) {
+            const int ks = (e >> 6) % nks, ct = (e >> 6) / nks;
+            ops[(ct * K_STEPS + ks) * 64 + (e & 63)] = phasor_operand(p, ct, ks, e & 63);
+        }
+        __syncthreads();
+
+#pragma unroll 1
+        for (int rt = 0; rt < ROW_TILES / 4; ++rt) {
+            const long m0 = tile0 + (long)(((rt / GROUP) * 4 + wave) * GROUP + rt % GROUP) * ROWS;
+            if (m0 >= p.dec_len) continue;
+            const long m = m0 + j;
+            const bool valid = m < p.dec_len;
+            v4i hi[COL_TILES], lo[COL_TILES];
+#pragma unroll
+            for (int ct = 0; ct < COL_TILES; ++ct) hi[ct] = lo[ct] = v4i{0, 0, 0, 0};
+#pragma unroll 1
+            for (int ks = 0; ks < nks; ++ks) {
+                const long x = (valid ? load_any(p.src, m, R, 16 * ks + 4 * q) : 0) ^ (long)0x8080808080808080UL;
+#pragma unroll
+                for (int ct = 0; ct < COL_TILES; ++ct) {
+                    if (ct < nct) {
+                        const uint4 a = ops[(ct * K_STEPS + ks) * 64 + lane];
+                        hi[ct] = __builtin_amdgcn_mfma_i32_16x16x32_i8(pack(a.x, a.y), x, hi[ct], 0, 0, 0);
+                        lo[ct] = __builtin_amdgcn_mfma_i32_16x16x32_i8(pack(a.z, a.w), x, lo[ct], 0, 0, 0);
+                    }
+                }
+            }
+            if (valid) {
+#pragma unroll
+                for (int ct = 0; ct < COL_TILES; ++ct)
+                    if (ct < nct) emit(p, hi[ct], lo[ct], 8 * ct + 2 * q, kr[ct][0], kr[ct][1], m);
+            }
+        }
+    }
+}
+
+template <int RT>
+static hipError_t launch_rt(const BankParams& p, hipStream_t st)
+{
+    const long blocks = (p.dec_len + TILE_DEC - 1) / TILE_DEC;
+    hipLaunchKernelGGL((ddc_bank_kernel<RT>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_bank(const BankParams& p, hipStream_t st)
+{
+    if (p.cic_r == 8) return launch_rt<8>(p, st);
+    if (p.cic_r == 10) return launch_rt<10>(p, st);
+    if (p.cic_r == 12) return launch_rt<12>(p, st);
+    return launch_rt<0>(p, st);
+}
+
+// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call
+hipError_t prepare_bank()
+{
+    hipFuncAttributes a;
+    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<0>));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<8>));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<10>));
+    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<12>));
+    return e;
+}
+
+}  // namespace ddc
+}  // namespace rtlws

@@ -9,6 +9,7 @@ fail loudly.
   LongPlan .......... include/rtlws_long.h (f64 spectra of 2^14 .. 2^20-point frames)
   AnyLenPlan ........ include/rtlws_anylen.h (f64 spectra of any frame length 2 .. 2^19)
   Engine.fm_audio_blocks[_cu8]  include/rtlws_fm.h (the FM receive chain in one launch)
+  DdcPlan, Engine.ddc  include/rtlws_ddc.h (tuned channels from one capture: integer mixer + CIC in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -30,6 +31,7 @@ AMD_LIB = os.environ.get("RTLWS_AMD_LIB") or os.path.join(LIB_DIR, "librtlws_amd
 LONG_LIB = os.path.join(LIB_DIR, "librtlws_long.so")     # include/rtlws_long.h
 ANYLEN_LIB = os.path.join(LIB_DIR, "librtlws_anylen.so") # include/rtlws_anylen.h
 FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
+DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -92,6 +94,10 @@ ANYLEN_SYMBOLS = ["rtlws_anylen_supported", "rtlws_anylen_open", "rtlws_anylen_c
 FM_SYMBOLS = ["rtlws_fm_supported", "rtlws_fm_grid", "rtlws_fm_prepare", "rtlws_fm_audio_blocks",
               "rtlws_fm_audio_blocks_cu8", "rtlws_fm_last_error"]
 FM_STATE_FLOATS = 21       # rtlws_fm.h: phase carry, delay line 1, delay line 2
+DDC_SYMBOLS = ["rtlws_ddc_supported", "rtlws_ddc_table", "rtlws_ddc_tuning_word", "rtlws_ddc_open", "rtlws_ddc_grid",
+               "rtlws_ddc_run", "rtlws_ddc_close", "rtlws_ddc_last_error"]
+DDC_LOG2_PERIOD = 16       # rtlws_ddc.h: the phase period P = 2^16
+DDC_MAX_CHANNELS = 32
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -126,6 +132,7 @@ _hip = None
 _long = None
 _anylen = None
 _fm = None
+_ddc = None
 _amd = None
 _cbb = None
 
@@ -265,6 +272,28 @@ def fm_lib():
     return _fm
 
 
+def ddc_lib():
+    """librtlws_ddc.so (include/rtlws_ddc.h); it needs librtlws_hip.so's engine."""
+    global _ddc
+    if _ddc is None:
+        hip_lib()
+        _need(DDC_LIB)
+        L = C.CDLL(DDC_LIB, mode=C.RTLD_GLOBAL)
+        vp, i, l, ip = C.c_void_p, C.c_int, C.c_long, C.POINTER(C.c_int)
+        L.rtlws_ddc_supported.argtypes = [i, i]
+        L.rtlws_ddc_table.argtypes = [vp]
+        L.rtlws_ddc_tuning_word.argtypes = [C.c_double, C.c_double, ip]
+        L.rtlws_ddc_open.argtypes = [vp]
+        L.rtlws_ddc_open.restype = vp
+        L.rtlws_ddc_grid.argtypes = [i, i, l, ip, ip, ip, ip]
+        L.rtlws_ddc_run.argtypes = [vp, i, vp, l, l, i, vp, vp, l, vp]
+        L.rtlws_ddc_close.argtypes = [vp]
+        L.rtlws_ddc_close.restype = None
+        L.rtlws_ddc_last_error.restype = C.c_char_p
+        _ddc = L
+    return _ddc
+
+
 def amd_lib():
     global _amd
     if _amd is None:
@@ -347,6 +376,37 @@ def fm_grid(block_len, nblocks, cic_r=0):
     b, t, s, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     rc = fm_lib().rtlws_fm_grid(int(block_len), int(nblocks), int(cic_r), C.byref(b), C.byref(t), C.byref(s), C.byref(a))
     return rc, b.value, t.value, s.value, a.value
+
+
+def ddc_last_error():
+    return ddc_lib().rtlws_ddc_last_error().decode()
+
+
+def ddc_supported(cic_r, nchannels=1):
+    return ddc_lib().rtlws_ddc_supported(int(cic_r), int(nchannels))
+
+
+def ddc_table():
+    """rtlws_ddc_table: the phasor table as the library builds it, int16 [P, 2] = (cos, sin).  No GPU needed."""
+    t = np.empty((1 << DDC_LOG2_PERIOD, 2), dtype=np.int16)
+    rc = ddc_lib().rtlws_ddc_table(_p(t))
+    if rc != 0:
+        raise RuntimeError("rtlws_ddc_table failed (rc=%d): %s" % (rc, ddc_last_error()))
+    return t
+
+
+def ddc_tuning_word(offset_hz, sample_rate_hz):
+    """rtlws_ddc_tuning_word: (rc, word).  No GPU needed."""
+    w = C.c_int(0)
+    rc = ddc_lib().rtlws_ddc_tuning_word(float(offset_hz), float(sample_rate_hz), C.byref(w))
+    return rc, w.value
+
+
+def ddc_grid(cic_r, nchannels, dec_len):
+    """rtlws_ddc_grid: (rc, workgroups, threads, LDS bytes, decimated samples per tile).  No GPU needed."""
+    b, t, s, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = ddc_lib().rtlws_ddc_grid(int(cic_r), int(nchannels), int(dec_len), C.byref(b), C.byref(t), C.byref(s), C.byref(d))
+    return rc, b.value, t.value, s.value, d.value
 
 
 def host_error():
@@ -464,6 +524,42 @@ class AnyLenPlan:
     def close(self):
         if self.h:
             anylen_lib().rtlws_anylen_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DdcPlan:
+    """rtlws_ddc_plan* of include/rtlws_ddc.h: the phasor table on the engine's device, the kernels loaded.  eng may
+    be None (as a C caller's NULL engine): open then fails with the library's text."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.h = ddc_lib().rtlws_ddc_open(eng.h if eng is not None else None)
+        if not self.h:
+            raise RuntimeError("rtlws_ddc_open failed: %s" % ddc_last_error())
+
+    @classmethod
+    def open(cls, eng):
+        return cls(eng)
+
+    def run(self, cic_r, d_iq, dec_len, tuning_words, d_out, out_stride=None, first_dec_index=0, stream=None, check=True):
+        """One launch: channel c of the bank is the cmplx_s32 stream at d_out + c * out_stride samples."""
+        words = (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = ddc_lib().rtlws_ddc_run(self.h, int(cic_r), ptr(d_iq), int(dec_len), int(first_dec_index), len(tuning_words),
+                                     words, ptr(d_out), int(dec_len if out_stride is None else out_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_ddc_run failed (rc=%d): %s" % (rc, ddc_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            ddc_lib().rtlws_ddc_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -650,6 +746,26 @@ class Engine:
         return self._fm_run(lambda s, nb, si, so, a, d: fm_lib().rtlws_fm_audio_blocks_cu8(
             self.h, int(cic_r), s, int(block_len), nb, si, so, int(bool(run_stage2)), a, d, None),
             iq, n, int(block_len), state, run_stage2, want_dec)
+
+    # -- include/rtlws_ddc.h: host arrays in, the bank's streams out ----
+    def ddc(self, iq, cic_r, tuning_words, first_dec_index=0):
+        """rtlws_ddc_run: iq uint8 [dec_len * cic_r, 2], one tuning word per channel -> int32 [C, dec_len, 2]."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        dec_len = iq.shape[0] // cic_r if cic_r > 0 else 0
+        assert cic_r <= 0 or dec_len * cic_r == iq.shape[0]
+        nch = len(tuning_words)
+        plan = DdcPlan(self)
+        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
+        d_out = self.alloc(max(nch * dec_len, 1) * 8)
+        try:
+            plan.run(cic_r, d_iq, dec_len, tuning_words, d_out, dec_len, first_dec_index)
+            self.sync()
+            out = self.download(d_out, np.int32, (nch, dec_len, 2)) if nch * dec_len else np.zeros((nch, 0, 2), np.int32)
+        finally:
+            plan.close()
+            d_iq.free()
+            d_out.free()
+        return out
 
     # -- convenience: host arrays in, host arrays out ------------------------
     def spectra(self, data, n_fft, k_avg=1, input="cu8", window="rect", output="power_sum",
