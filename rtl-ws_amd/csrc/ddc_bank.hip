@@ -22,81 +22,10 @@
 #include <stdint.h>
 
 #include "ddc_bank.h"
+#include "ddc_ops.h"
 
 namespace rtlws {
 namespace ddc {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int nt_i2 __attribute__((ext_vector_type(2)));
-typedef unsigned nt_u2 __attribute__((ext_vector_type(2)));
-
-// T[phase mod P] as (cos, sin)
-__device__ __forceinline__ int2 phasor(const uint32_t* __restrict__ table, unsigned phase)
-{
-    const uint32_t e = table[phase & (unsigned)(P - 1)];
-    return make_int2((int)(int16_t)(e & 0xffffu), (int)e >> 16);
-}
-
-// The A operands of lane `lane` for column tile ct and K step ks: {high bytes (2 dwords), low bytes (2 dwords)}
-// of the phasors of samples n = 16 ks + 4 (lane >> 4) + t, t < 4, on row lane & 15.  Zero beyond R and beyond C.
-__device__ __forceinline__ uint4 phasor_operand(const BankParams& p, int ct, int ks, int lane)
-{
-    const int r = lane & 15, q = lane >> 4;
-    const int c = 8 * ct + (r >> 1);
-    const bool im_row = r & 1;
-    const int k = p.words[c & (MAX_CH - 1)];
-    unsigned hi[2] = {0u, 0u}, lo[2] = {0u, 0u};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int n = 16 * ks + 4 * q + t;
-        int w_re = 0, w_im = 0;                          // what multiplies the sample's re byte and its im byte
-        if (c < p.nch && n < p.cic_r) {
-            const int2 e = phasor(p.table, (unsigned)(k * n));
-            w_re = im_row ? -e.y : e.x;
-            w_im = im_row ? e.x : e.y;
-        }
-        const int re_l = (int8_t)w_re, im_l = (int8_t)w_im;
-        const unsigned pair_l = ((unsigned)re_l & 0xffu) | (((unsigned)im_l & 0xffu) << 8);
-        const unsigned pair_h = ((unsigned)((w_re - re_l) >> 8) & 0xffu) | (((unsigned)((w_im - im_l) >> 8) & 0xffu) << 8);
-        lo[t >> 1] |= pair_l << (16 * (t & 1));
-        hi[t >> 1] |= pair_h << (16 * (t & 1));
-    }
-    return make_uint4(hi[0], hi[1], lo[0], lo[1]);
-}
-
-__device__ __forceinline__ long pack(unsigned lo, unsigned hi) { return (long)(((unsigned long)hi << 32) | lo); }
-
-// Bytes 8 q .. 8 q + 7 of the block of decimated sample m (zero behind the block).  Streamed once: nontemporal.
-template <int RT>
-__device__ __forceinline__ long load_block(const void* src, long m, int q)
-{
-    if constexpr (RT == 8) {                             // 16 bytes: two lanes of eight
-        if (q >= 2) return 0;
-        const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2*>(src) + m * 2 + q);
-        return pack(v.x, v.y);
-    } else if constexpr (RT == 12) {                     // 24 bytes, 8-byte aligned: three lanes of eight
-        if (q >= 3) return 0;
-        const nt_u2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_u2*>(src) + m * 3 + q);
-        return pack(v.x, v.y);
-    } else {                                             // R = 10: 20 bytes, 4-byte aligned: dwords 2 q, 2 q + 1 of five
-        static_assert(RT == 10, "compile-time factors: 8, 10, 12");
-        if (q >= 3) return 0;
-        const unsigned* w = reinterpret_cast<const unsigned*>(src) + m * 5 + 2 * q;
-        const unsigned lo = __builtin_nontemporal_load(w);
-        const unsigned hi = q < 2 ? __builtin_nontemporal_load(w + 1) : 0u;
-        return pack(lo, hi);
-    }
-}
-
-// any factor: samples n0 .. n0 + 3 of the block of decimated sample m, two bytes each (zero from sample R on)
-__device__ __forceinline__ long load_any(const void* src, long m, int R, int n0)
-{
-    const uint16_t* s = reinterpret_cast<const uint16_t*>(src) + m * R;
-    unsigned v[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[t] = n0 + t < R ? (unsigned)s[n0 + t] : 0u;
-    return pack(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-}
 
 // The block phasor and the store: this lane's two channels c0, c0 + 1 of decimated sample m.
 __device__ __forceinline__ void emit(const BankParams& p, v4i hi, v4i lo, int c0, unsigned kr0, unsigned kr1, long m)
@@ -106,12 +35,9 @@ __device__ __forceinline__ void emit(const BankParams& p, v4i hi, v4i lo, int c0
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if (c0 + h >= p.nch) continue;
-        const int ur = (int)(((unsigned)hi[2 * h] << 8) + (unsigned)lo[2 * h]);
-        const int ui = (int)(((unsigned)hi[2 * h + 1] << 8) + (unsigned)lo[2 * h + 1]);
-        const int2 e = phasor(p.table, (h ? kr1 : kr0) * g16);
-        const long vr = (long)ur * e.x + (long)ui * e.y + (1L << 27);
-        const long vi = (long)ui * e.x - (long)ur * e.y + (1L << 27);
-        const nt_i2 o = {(int)(vr >> 28), (int)(vi >> 28)};
+        const int2 v = rotate(inner_sum(hi[2 * h], lo[2 * h]), inner_sum(hi[2 * h + 1], lo[2 * h + 1]),
+                              phasor(p.table, (h ? kr1 : kr0) * g16));
+        const nt_i2 o = {v.x, v.y};
         out[(long)(c0 + h) * p.out_stride + m] = o;
     }
 }

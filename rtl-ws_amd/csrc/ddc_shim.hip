@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ddc_bank.h"
+#include "ddc_table.h"
 #include "rtlws_ddc.h"
 
 struct rtlws_ddc_plan {
@@ -39,23 +40,6 @@ int fail_hip(const char* fn, const char* what, hipError_t e)
     snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
     g_err = buf;
     return -3;
-}
-
-// T[j] = rint(2^14 (cos, sin)(2 pi j / P)) from the exact integer phase j, the axis values exact (as
-// twiddle_tables.cpp's W()); no entry lies closer than 8.7e-7 to a rounding tie, a double's cos and sin are 1e-12 off
-void build_table(int16_t* t)
-{
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int j = 0; j < P; ++j) {
-        double c, s;
-        if (j == 0) c = 1, s = 0;
-        else if (j == P / 4) c = 0, s = 1;
-        else if (j == P / 2) c = -1, s = 0;
-        else if (j == 3 * (P / 4)) c = 0, s = -1;
-        else c = std::cos(two_pi * j / P), s = std::sin(two_pi * j / P);
-        t[2 * j] = (int16_t)std::lrint(16384.0 * c);
-        t[2 * j + 1] = (int16_t)std::lrint(16384.0 * s);
-    }
 }
 
 long tiles_of(long dec_len) { return (dec_len + TILE_DEC - 1) / TILE_DEC; }
@@ -88,7 +72,7 @@ int rtlws_ddc_table(int16_t* cos_sin)
 {
     g_err.clear();
     if (!cos_sin) return fail("rtlws_ddc_table", "null pointer", -1);
-    build_table(cos_sin);
+    build_table(cos_sin, P);
     return 0;
 }
 
@@ -133,7 +117,7 @@ rtlws_ddc_plan* rtlws_ddc_open(rtlws_engine* e)
         return nullptr;
     }
     std::vector<int16_t> host(2 * (size_t)P);
-    build_table(host.data());
+    build_table(host.data(), P);
     uint32_t* d_table = nullptr;
     err = hipMalloc(reinterpret_cast<void**>(&d_table), host.size() * sizeof(int16_t));
     if (err == hipSuccess) err = hipMemcpy(d_table, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice);

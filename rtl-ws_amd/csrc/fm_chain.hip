@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "fm_chain.h"
+#include "fm_maps.h"
 #include "fm_math.h"
 
 namespace rtlws {
@@ -28,81 +29,6 @@ namespace fm {
 typedef unsigned nt_u4 __attribute__((ext_vector_type(4)));
 typedef unsigned nt_u2 __attribute__((ext_vector_type(2)));
 typedef int nt_i2 __attribute__((ext_vector_type(2)));
-
-// the two index maps, stream position -> position in the stream it is cut from
-struct Maps {
-    int L, half, L1, L2;      // L1 = 2 half, L2 = 2 quarter
-    long nblocks;
-    __device__ long s2_to_w(long s2) const
-    {
-        if (L2 == half) return s2;
-        const long b = s2 / L2;
-        return b * half + (s2 - b * L2);
-    }
-    __device__ long s1_to_g(long s1) const
-    {
-        if (L1 == L) return s1;
-        const long b = s1 / L1;
-        return b * L + (s1 - b * L1);
-    }
-};
-
-// The same map for positions at or after `from`, with the one 64-bit division done once per workgroup: a tile spans
-// fewer than 2^12 positions and a block fewer than 2^31, so the offset from the block that holds `from` fits 32 bits.
-struct TileMap {
-    long src0, dst0;
-    unsigned n_src, n_dst;
-    __device__ TileMap(long from, int src_per_block, int dst_per_block)
-        : n_src((unsigned)src_per_block), n_dst((unsigned)dst_per_block)
-    {
-        const long b = from / src_per_block;
-        src0 = b * src_per_block;
-        dst0 = b * dst_per_block;
-    }
-    __device__ long operator()(long s) const
-    {
-        if (n_src == n_dst) return s;
-        const unsigned off = (unsigned)(s - src0);
-        const unsigned b = off / n_src;
-        return dst0 + (long)b * n_dst + (off - b * n_src);
-    }
-};
-
-__device__ __forceinline__ Maps make_maps(const ChainParams& p)
-{
-    Maps m;
-    m.L = p.block_len;
-    m.half = m.L / 2;
-    m.L1 = 2 * m.half;
-    m.L2 = 2 * (m.half / 2);
-    m.nblocks = p.nblocks;
-    return m;
-}
-
-// what tile t needs of every stream (all bounds inclusive)
-struct TileRange {
-    long a0, s2lo, wlo, whi, s1lo, glo, ghi;
-    int na, n2, n1, np;
-};
-
-__device__ __forceinline__ TileRange tile_range(const Maps& m, long t)
-{
-    TileRange r;
-    const long total_audio = m.nblocks * (m.L2 / 2);
-    r.a0 = t * TILE;
-    r.na = (int)(total_audio - r.a0 < TILE ? total_audio - r.a0 : TILE);
-    r.s2lo = 2 * r.a0 - 10;                              // the delay line of the first output
-    const long s2hi = 2 * (r.a0 + r.na - 1);
-    r.n2 = (int)(s2hi - r.s2lo) + 1;
-    r.wlo = m.s2_to_w(r.s2lo < 0 ? 0 : r.s2lo);
-    r.whi = m.s2_to_w(s2hi);
-    r.s1lo = 2 * r.wlo - 10;
-    r.n1 = 2 * (int)(r.whi - r.wlo) + 11;
-    r.glo = m.s1_to_g(r.s1lo < 0 ? 0 : r.s1lo);
-    r.ghi = m.s1_to_g(2 * r.whi);
-    r.np = (int)(r.ghi - r.glo) + 2;                     // phases glo - 1 .. ghi
-    return r;
-}
 
 // Decimated sample g.  cmplx_u8 sources: the sum over R consecutive samples of (x - 128) per component
 // (reference src/resample.c:21-40 without its delay lines), an integer sum in any order.  Streamed once: nontemporal.
@@ -200,7 +126,7 @@ __device__ __forceinline__ void write_tails(const ChainParams& p, const Maps& m)
         p.state_out[0] = phase_at<SRC>(p, m.nblocks * m.L - 1);
     } else if (tid >= 192 && p.dec) {
         nt_i2* dec = reinterpret_cast<nt_i2*>(p.dec);
-        for (long g = tile_range(m, p.ntiles - 1).ghi + 1 + (tid - 192); g < m.nblocks * m.L; g += 64) {
+        for (long g = tile_range<TILE>(m, p.ntiles - 1).ghi + 1 + (tid - 192); g < m.nblocks * m.L; g += 64) {
             const int2 s = load_sample<SRC>(p.src, g, p.cic_r);
             const nt_i2 o = {s.x, s.y};
             dec[g] = o;
@@ -212,17 +138,17 @@ template <int SRC, bool RUN2>
 __global__ __launch_bounds__(THREADS) void fm_chain_kernel(const ChainParams p)
 {
     __shared__ float lds[LDS_FLOATS];
-    const Maps m = make_maps(p);
+    const Maps m = make_maps(p.block_len, p.nblocks);
     const long t = blockIdx.x;
     if (t == p.ntiles) {
         write_tails<SRC, RUN2>(p, m);
         return;
     }
     const int tid = threadIdx.x;
-    const TileRange r = tile_range(m, t);
+    const TileRange r = tile_range<TILE>(m, t);
     // decimated samples this tile stores: from its own first to the next tile's first
     const long own_lo = t == 0 ? 0 : r.glo;
-    const long own_hi = t + 1 == p.ntiles ? r.ghi + 1 : tile_range(m, t + 1).glo;
+    const long own_hi = t + 1 == p.ntiles ? r.ghi + 1 : tile_range<TILE>(m, t + 1).glo;
     nt_i2* dec = reinterpret_cast<nt_i2*>(p.dec);
 
     if constexpr (!RUN2) {                               // exhausted pool: the tiles only deliver the decimated samples

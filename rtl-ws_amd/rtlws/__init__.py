@@ -10,6 +10,7 @@ fail loudly.
   AnyLenPlan ........ include/rtlws_anylen.h (f64 spectra of any frame length 2 .. 2^19)
   Engine.fm_audio_blocks[_cu8]  include/rtlws_fm.h (the FM receive chain in one launch)
   DdcPlan, Engine.ddc  include/rtlws_ddc.h (tuned channels from one capture: integer mixer + CIC in one launch)
+  FmBankPlan, Engine.fm_bank  include/rtlws_fmbank.h (up to 32 FM stations from one capture in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -32,6 +33,7 @@ LONG_LIB = os.path.join(LIB_DIR, "librtlws_long.so")     # include/rtlws_long.h
 ANYLEN_LIB = os.path.join(LIB_DIR, "librtlws_anylen.so") # include/rtlws_anylen.h
 FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
+FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -98,6 +100,9 @@ DDC_SYMBOLS = ["rtlws_ddc_supported", "rtlws_ddc_table", "rtlws_ddc_tuning_word"
                "rtlws_ddc_run", "rtlws_ddc_close", "rtlws_ddc_last_error"]
 DDC_LOG2_PERIOD = 16       # rtlws_ddc.h: the phase period P = 2^16
 DDC_MAX_CHANNELS = 32
+FMBANK_SYMBOLS = ["rtlws_fmbank_supported", "rtlws_fmbank_grid", "rtlws_fmbank_open", "rtlws_fmbank_run",
+                  "rtlws_fmbank_close", "rtlws_fmbank_last_error"]
+FMBANK_MAX_CHANNELS = 32
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -133,6 +138,7 @@ _long = None
 _anylen = None
 _fm = None
 _ddc = None
+_fmbank = None
 _amd = None
 _cbb = None
 
@@ -294,6 +300,26 @@ def ddc_lib():
     return _ddc
 
 
+def fmbank_lib():
+    """librtlws_fmbank.so (include/rtlws_fmbank.h); it needs librtlws_hip.so's engine."""
+    global _fmbank
+    if _fmbank is None:
+        hip_lib()
+        _need(FMBANK_LIB)
+        L = C.CDLL(FMBANK_LIB, mode=C.RTLD_GLOBAL)
+        vp, i, l, ip = C.c_void_p, C.c_int, C.c_long, C.POINTER(C.c_int)
+        L.rtlws_fmbank_supported.argtypes = [i, i, i, l]
+        L.rtlws_fmbank_grid.argtypes = [i, i, i, l, ip, ip, ip, ip]
+        L.rtlws_fmbank_open.argtypes = [vp]
+        L.rtlws_fmbank_open.restype = vp
+        L.rtlws_fmbank_run.argtypes = [vp, i, vp, i, l, l, i, vp, vp, vp, vp, l, vp]
+        L.rtlws_fmbank_close.argtypes = [vp]
+        L.rtlws_fmbank_close.restype = None
+        L.rtlws_fmbank_last_error.restype = C.c_char_p
+        _fmbank = L
+    return _fmbank
+
+
 def amd_lib():
     global _amd
     if _amd is None:
@@ -407,6 +433,22 @@ def ddc_grid(cic_r, nchannels, dec_len):
     b, t, s, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
     rc = ddc_lib().rtlws_ddc_grid(int(cic_r), int(nchannels), int(dec_len), C.byref(b), C.byref(t), C.byref(s), C.byref(d))
     return rc, b.value, t.value, s.value, d.value
+
+
+def fmbank_last_error():
+    return fmbank_lib().rtlws_fmbank_last_error().decode()
+
+
+def fmbank_supported(cic_r, nchannels=1, block_len=20, nblocks=1):
+    return fmbank_lib().rtlws_fmbank_supported(int(cic_r), int(nchannels), int(block_len), int(nblocks))
+
+
+def fmbank_grid(cic_r, nchannels, block_len, nblocks):
+    """rtlws_fmbank_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
+    b, t, s, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = fmbank_lib().rtlws_fmbank_grid(int(cic_r), int(nchannels), int(block_len), int(nblocks), C.byref(b), C.byref(t),
+                                        C.byref(s), C.byref(a))
+    return rc, b.value, t.value, s.value, a.value
 
 
 def host_error():
@@ -560,6 +602,45 @@ class DdcPlan:
     def close(self):
         if self.h:
             ddc_lib().rtlws_ddc_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FmBankPlan:
+    """rtlws_fmbank_plan* of include/rtlws_fmbank.h: the phasor table on the engine's device, the kernels loaded.  eng
+    may be None (as a C caller's NULL engine): open then fails with the library's text."""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.h = fmbank_lib().rtlws_fmbank_open(eng.h if eng is not None else None)
+        if not self.h:
+            raise RuntimeError("rtlws_fmbank_open failed: %s" % fmbank_last_error())
+
+    @classmethod
+    def open(cls, eng):
+        return cls(eng)
+
+    def run(self, cic_r, d_iq, block_len, nblocks, tuning_words, d_state_in, d_state_out, d_audio, audio_stride=None,
+            first_dec_index=0, stream=None, check=True):
+        """One launch: audio of channel c at d_audio + c * audio_stride floats, states channel-major [C, 21]."""
+        words = (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        stride = int(nblocks) * (int(block_len) // 4) if audio_stride is None else int(audio_stride)
+        rc = fmbank_lib().rtlws_fmbank_run(self.h, int(cic_r), ptr(d_iq), int(block_len), int(nblocks), int(first_dec_index),
+                                           len(tuning_words), words, ptr(d_state_in), ptr(d_state_out), ptr(d_audio),
+                                           stride, stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_fmbank_run failed (rc=%d): %s" % (rc, fmbank_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            fmbank_lib().rtlws_fmbank_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -766,6 +847,33 @@ class Engine:
             d_iq.free()
             d_out.free()
         return out
+
+    # -- include/rtlws_fmbank.h: host arrays in, (audio, new states) out ----
+    def fm_bank(self, iq, cic_r, tuning_words, block_len, states, first_dec_index=0):
+        """rtlws_fmbank_run: iq uint8 [nblocks * block_len * cic_r, 2], one tuning word and one state f32[21] per
+        channel -> (audio f32 [C, nblocks * quarter], new states f32 [C, 21])."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        nch = len(tuning_words)
+        states = np.ascontiguousarray(states, dtype=np.float32).reshape(nch, FM_STATE_FLOATS)
+        per_block = int(block_len) * int(cic_r)
+        nblocks = iq.shape[0] // per_block if per_block > 0 else 0
+        assert per_block <= 0 or nblocks * per_block == iq.shape[0]
+        n = max(nblocks * (int(block_len) // 4), 0)
+        plan = FmBankPlan(self)
+        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
+        d_in = self.upload(states)
+        d_out = self.alloc(states.nbytes)
+        d_audio = self.alloc(max(nch * n, 1) * 4)
+        try:
+            plan.run(cic_r, d_iq, block_len, nblocks, tuning_words, d_in, d_out, d_audio, n, first_dec_index)
+            self.sync()
+            audio = self.download(d_audio, np.float32, (nch, n)) if nch * n else np.zeros((nch, 0), np.float32)
+            new_states = self.download(d_out, np.float32, (nch, FM_STATE_FLOATS))
+        finally:
+            plan.close()
+            for b in (d_iq, d_in, d_out, d_audio):
+                b.free()
+        return audio, new_states
 
     # -- convenience: host arrays in, host arrays out ------------------------
     def spectra(self, data, n_fft, k_avg=1, input="cu8", window="rect", output="power_sum",
