@@ -11,6 +11,11 @@ SPECIAL_WORDS = (0, 1, -1, -32768, 32767)
 # (8, 10, 12, generic), one and four column tiles
 BANKS = [(1, 1), (7, 9), (8, 8), (8, 32), (10, 1), (12, 9), (16, 8), (17, 2), (128, 32)]
 
+# the banks of the multi-tile suite (fm_ref.tile_cases): every case at a compile-time factor with two column tiles of
+# which the second holds one channel; the cases whose stage-1 map skips also at the other instantiations
+TILE_BANK = (8, 9)
+SKIP_BANKS = [(10, 2), (12, 8), (7, 9)]
+
 _cache = {}
 
 
@@ -48,6 +53,22 @@ def expected(oracle, iq, R, words, L, states, first=0, key=None):
     if key is not None:
         _cache[key] = res
     return res
+
+
+def case_inputs(case, R, C):
+    """(capture, tuning words, carried states) of an fm_ref.tile_cases case at a bank of C channels and factor R: the
+    last channel is the first one's station, word and state."""
+    seed = 1000 * case.block_len + 10 * R + C
+    words = words_for(C, seed)
+    states = states_for(C, seed + 1)
+    states[C - 1] = states[0]
+    return ddc_ref.random_iq(case.nblocks * case.block_len * R, seed + 2), words, states
+
+
+def tile_bank_runs(t):
+    """(case, R, C) of every launch of the multi-tile suite"""
+    cases = fm_ref.tile_cases(t)
+    return [(c,) + TILE_BANK for c in cases] + [(c, R, C) for R, C in SKIP_BANKS for c in cases if c.residue in (1, 3)]
 
 
 def matrix_shape(t):

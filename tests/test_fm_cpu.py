@@ -133,14 +133,8 @@ def test_stream_maps_equal_the_per_block_chain(oracle, block_len):
         assert np.array_equal(got_st, want_st), (kind, np.nonzero(got_st != want_st))
 
 
-def test_tile_ranges_fit_the_lds_capacities(built):
-    """What a tile reads of each stream (tile_range() of fm_chain.hip, restated in fm_ref.tile_range) stays inside
-    the capacities of fm_chain.h for every block shape -- the worst is block_len = 23 -- and every tile index."""
-    hdr = open(os.path.join(ROOT, "rtl-ws_amd", "csrc", "fm_chain.h")).read()
-    const = lambda n: int(re.search(r"constexpr int %s = (\d+);" % n, hdr).group(1))
-    tile, phase_cap, s1_half, s2_half = const("TILE"), const("PHASE_CAP"), const("S1_HALF"), const("S2_HALF")
-    assert built.fm_grid(20, 1, 0)[4] == tile
-    assert s1_half % 32 == 16 and s2_half % 32 == 16               # even / odd halves 16 banks apart
+def _worst_tile_ranges(tile):
+    """the largest (n2, n1, np) over every block shape and every tile index"""
     worst = [0, 0, 0]
     for L in list(range(20, 120)) + [1023, 1026, 4102, 19200]:
         quarter = L // 4
@@ -149,7 +143,89 @@ def test_tile_ranges_fit_the_lds_capacities(built):
         for t in range(ntiles):
             r = fm_ref.tile_range(t, L, nb, tile)
             worst = [max(a, b) for a, b in zip(worst, r)]
-    n2, n1, np_ = worst
+    return worst
+
+
+def _capacities():
+    hdr = open(os.path.join(ROOT, "rtl-ws_amd", "csrc", "fm_chain.h")).read()
+    const = lambda n: int(re.search(r"constexpr int %s = (\d+);" % n, hdr).group(1))
+    return const("TILE"), const("PHASE_CAP"), const("S1_HALF"), const("S2_HALF")
+
+
+def test_tile_ranges_fit_the_lds_capacities(built):
+    """What a tile reads of each stream (tile_range() of fm_chain.hip, restated in fm_ref.tile_range) stays inside
+    the capacities of fm_chain.h for every block shape -- the worst is block_len = 23 -- and every tile index."""
+    tile, phase_cap, s1_half, s2_half = _capacities()
+    assert built.fm_grid(20, 1, 0)[4] == tile
+    assert s1_half % 32 == 16 and s2_half % 32 == 16               # even / odd halves 16 banks apart
+    n2, n1, np_ = _worst_tile_ranges(tile)
     print("worst n2 %d, n1 %d, phases %d" % (n2, n1, np_))
     assert (n2 + 1) // 2 <= s2_half and 2 * s2_half <= phase_cap
     assert (n1 + 1) // 2 <= s1_half and np_ <= phase_cap
+
+
+# ---- the block shapes tests/test_fm_gpu.py launches over several tiles (fm_ref.tile_cases) -----------------------
+
+def test_multi_tile_cases_meet_their_conditions(built):
+    """From the model alone, with the library's own tile: every case has four tiles or more and a partial last one;
+    where a map skips, some tile behind the first has its map's origin in a later block and a block border inside
+    what it reads; regime b's borders lie in the halos of tiles 1, 2 (stage 2) and 3 (stage 1); the block_len = 23
+    case reaches the largest ranges any block shape reaches, so its launch fills LDS as far as any can."""
+    tile = built.fm_grid(20, 1, 0)[4]
+    _, phase_cap, s1_half, _ = _capacities()
+    for line in fm_ref.case_report(tile, _worst_tile_ranges(tile)):
+        print(line)
+    n2, n1, nph = _worst_tile_ranges(tile)
+    print("tile %d, block_len 23 fills %d of %d phase slots, %d of %d per stage-1 half" % (tile, nph, phase_cap, (n1 + 1) // 2, s1_half))
+    for c in fm_ref.tile_cases(tile):
+        rc, blocks, _, _, t = built.fm_grid(c.block_len, c.nblocks, 0)
+        assert rc == 0 and t == tile and blocks == c.ntiles(tile) + 1, c.id
+
+
+@pytest.mark.parametrize("kind", ["A", "B"])
+def test_multi_tile_inputs_reach_both_sides_of_the_limiter(oracle, built, kind):
+    """On the oracle alone: in every case of tests/test_fm_gpu.py's multi-tile suite between 10 % and 90 % of the
+    demodulator's outputs are clamped."""
+    make = {"A": fm_ref.input_a, "B": fm_ref.input_b}[kind]
+    for c in fm_ref.tile_cases(built.fm_grid(20, 1, 0)[4]):
+        iq, st = fm_ref.case_input(make, c)
+        clamped = np.mean(np.abs(oracle.fm_demod(iq, prev_phase=float(st[0]))[0]) == 1.0)
+        print("input %s, case %s: %.1f %% of %d samples clamped" % (kind, c.id, 100 * clamped, iq.shape[0]))
+        assert 0.10 <= clamped <= 0.90, c.id
+
+
+@pytest.fixture(scope="module")
+def host_maps(built, tmp_path_factory):
+    cc = fm_ref.host_compiler()
+    if cc is None:
+        pytest.skip("no C++ compiler for the host")
+    tile = built.fm_grid(20, 1, 0)[4]
+    return fm_ref.HostMaps(cc, os.path.join(ROOT, "rtl-ws_amd", "csrc"), tmp_path_factory.mktemp("maps"), tile)
+
+
+def test_the_kernels_build_their_tile_maps_as_the_host_check_does():
+    for f in ("fm_chain.hip", "fm_bank.hip"):
+        txt = open(os.path.join(ROOT, "rtl-ws_amd", "csrc", f)).read().replace("fm::", "")
+        for line in fm_ref.TILE_MAP_TEXT:
+            assert txt.count(line) == 1, (f, line)
+
+
+def test_tile_map_equals_maps_in_the_product_text(host_maps):
+    """fm_maps.h compiled for the host: for every block_len 20 .. 4200, over enough blocks for four tiles, TileMap as
+    the kernels build it equals Maps at every position every tile reads, for both maps, and both equal fm_ref's numpy
+    restatements; tile_range() equals fm_ref.tile_bounds."""
+    print("tile %d: %d positions" % (host_maps.tile, fm_ref.sweep_host_maps(host_maps)))
+
+
+@pytest.mark.parametrize("residue", [0, 1, 2, 3])
+def test_tile_map_beyond_32_bits(host_maps, residue):
+    """The 64/32-bit split: tiles whose stream positions lie on both sides of 2^31, 2^32 and 2^33 and at the end of
+    a capture of more than 2^34 decimated samples, for tiny, tile-sized, long and the longest blocks."""
+    fm_ref.check_host_maps_beyond_32_bits(host_maps, residue)
+
+
+def test_wrong_tile_maps_pass_the_earlier_shapes_and_fail_the_new_ones(built):
+    """The gap and its closure, on the CPU: a TileMap with dst0 counted in source blocks, one with src0 = 0 and one that
+    maps nothing agree with Maps at every stage-1 position of every multi-tile launch the GPU suites made before, and
+    disagree inside a tile of the new cases wherever block_len is not a multiple of 4."""
+    fm_ref.check_wrong_tile_maps(built.fm_grid(20, 1, 0)[4])

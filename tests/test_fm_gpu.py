@@ -1,5 +1,6 @@
 """GPU suite of include/rtlws_fm.h: the FM receive chain in one launch (CIC block sums, demodulator, both
-half-bands) against the reference-object-code golden and a loop of the oracle's per-block chain.  Every
+half-bands) against the reference-object-code golden and a loop of the oracle's per-block chain, at single-tile
+shapes and at every block_len mod 4 over several tiles (fm_ref.tile_cases).  Every
 comparison is np.array_equal: the fused path is held to equality, not to a tolerance."""
 import ctypes as C
 
@@ -86,6 +87,77 @@ def test_tiles_with_block_borders_inside(engine, fm, oracle, built):
         got, got_st = engine.fm_audio_blocks(iq, L, st)
         assert np.array_equal(got, want), kind
         assert np.array_equal(got_st, want_st), kind
+
+
+# ---- every block shape over several tiles (fm_ref.tile_cases; tests/test_fm_cpu.py checks what the cases reach) ----
+
+CASES = [(regime, residue) for regime in "abc" for residue in range(4)]
+ODD_BLOCKS = [(regime, residue) for regime in "abc" for residue in (1, 3)]       # the stage-1 map skips
+
+
+def _tile_case(built, regime, residue):
+    """the case of the library's own tile, and its grid: one workgroup per tile and the one of the state"""
+    tile = built.fm_grid(20, 1, 0)[4]
+    case = {(c.regime, c.residue): c for c in fm_ref.tile_cases(tile)}[regime, residue]
+    ntiles = case.ntiles(tile)
+    for R in (0, 7, 8, 10, 12):
+        rc, blocks, _, _, t = built.fm_grid(case.block_len, case.nblocks, R)
+        assert rc == 0 and t == tile and blocks == ntiles + 1 >= 5, (case.id, R)
+    return case
+
+
+def _cu8_case(case, R):
+    seed = 100 * case.block_len + R
+    u8 = np.random.default_rng(seed).integers(0, 256, size=(case.block_len * case.nblocks * R, 2), dtype=np.uint8)
+    return u8, fm_ref.random_state(seed + 1)
+
+
+@pytest.mark.parametrize("regime,residue", CASES)
+def test_tile_cases_equal_the_oracle_loop(engine, fm, oracle, built, regime, residue):
+    """Dozens of tiny blocks per tile, borders just in front of tiles, long blocks: every block_len mod 4 over four
+    tiles or more, from a carried state, against the loop of the reference's per-block chain."""
+    case = _tile_case(built, regime, residue)
+    for kind, make in INPUTS.items():
+        iq, st = fm_ref.case_input(make, case)
+        want, want_st = fm_ref.oracle_chain(oracle, iq, case.block_len, st)
+        got, got_st = engine.fm_audio_blocks(iq, case.block_len, st)
+        assert got.size == case.nblocks * (case.block_len // 4)
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, (case.id, kind, bad.size, bad[:8])
+        assert np.array_equal(got_st, want_st), (case.id, kind, np.nonzero(got_st != want_st))
+
+
+@pytest.mark.parametrize("R,regime,residue", [(8,) + c for c in CASES] + [(R,) + c for R in (10, 12, 7) for c in ODD_BLOCKS])
+def test_tile_cases_with_the_cic_in_front(engine, fm, oracle, built, R, regime, residue):
+    """The cu8 form at every loader: audio, state and every decimated sample -- those an odd block skips and those
+    behind the last tile's range included."""
+    case = _tile_case(built, regime, residue)
+    u8, st = _cu8_case(case, R)
+    rc, dec, _ = oracle.cic_decimate(R, u8)
+    assert rc == 0 and dec.shape == (case.nblocks * case.block_len, 2)
+    want, want_st = fm_ref.oracle_chain(oracle, dec, case.block_len, st)
+    got, got_st, got_dec = engine.fm_audio_blocks_cu8(u8, R, case.block_len, st, want_dec=True)
+    bad = np.nonzero(np.any(got_dec != dec, axis=1))[0]
+    assert bad.size == 0, (case.id, "dec", bad.size, bad[:8])
+    bad = np.nonzero(got != want)[0]
+    assert got.size == want.size and bad.size == 0, (case.id, "audio", bad.size, bad[:8])
+    assert np.array_equal(got_st, want_st), (case.id, np.nonzero(got_st != want_st))
+
+
+@pytest.mark.parametrize("R", [8, 7])
+def test_stage_2_off_over_tiles_with_skipping_maps(engine, fm, oracle, built, R):
+    """run_stage2 = 0 where both maps skip and the borders lie in front of the tiles: every decimated sample is
+    delivered by the tiles and the last workgroup, the state is the exhausted pool's."""
+    case = _tile_case(built, "b", 3)
+    u8, st = _cu8_case(case, R)
+    rc, dec, _ = oracle.cic_decimate(R, u8)
+    assert rc == 0
+    _, want_st = fm_ref.oracle_chain(oracle, dec, case.block_len, st, run_stage2=False)
+    none, got_st, got_dec = engine.fm_audio_blocks_cu8(u8, R, case.block_len, st, run_stage2=False, want_dec=True)
+    assert none.size == 0
+    assert np.array_equal(got_dec, dec), np.nonzero(np.any(got_dec != dec, axis=1))[0][:8]
+    assert np.array_equal(got_st[11:21], st[11:21])
+    assert np.array_equal(got_st, want_st), np.nonzero(got_st != want_st)
 
 
 @pytest.mark.parametrize("L", [23, 1024])

@@ -145,13 +145,8 @@ def _constants():
     return val
 
 
-def test_capacities_hold_for_every_block_shape(built):
-    """With the library's own tile, what a tile reads of each stream (tests/fm_ref.py's tile_range) stays within
-    fm_bank.h's capacities for every block_len 20 .. 4200, over enough blocks for three tiles."""
-    k = _constants()
-    rc, _, threads, lds, tile = built.fmbank_grid(8, 8, 20, 1)
-    assert rc == 0 and tile == k["TILE"] and threads == k["THREADS"]
-    assert lds == k["COL_CH"] * (k["PHASE_CAP"] + 2 * k["S1_HALF"]) * 4
+def _worst_tile_ranges(tile):
+    """the largest (n2, n1, np) over every block_len 20 .. 4200 and every tile of enough blocks for three tiles"""
     worst = [0, 0, 0]
     for L in range(20, 4201):
         quarter = L // 4
@@ -159,12 +154,80 @@ def test_capacities_hold_for_every_block_shape(built):
         for t in range(-(-nb * quarter // tile)):
             r = fm_ref.tile_range(t, L, nb, tile)
             worst = [max(a, b) for a, b in zip(worst, r)]
-    n2, n1, nph = worst
+    return worst
+
+
+def test_capacities_hold_for_every_block_shape(built):
+    """With the library's own tile, what a tile reads of each stream (tests/fm_ref.py's tile_range) stays within
+    fm_bank.h's capacities for every block_len 20 .. 4200, over enough blocks for three tiles."""
+    k = _constants()
+    rc, _, threads, lds, tile = built.fmbank_grid(8, 8, 20, 1)
+    assert rc == 0 and tile == k["TILE"] and threads == k["THREADS"]
+    assert lds == k["COL_CH"] * (k["PHASE_CAP"] + 2 * k["S1_HALF"]) * 4
+    n2, n1, nph = _worst_tile_ranges(tile)
     print("tile %d: n2 <= %d, n1 <= %d, phases <= %d" % (tile, n2, n1, nph))
     assert n2 == 2 * tile + 9
     assert (n2 + 1) // 2 <= k["S2_HALF"] and k["S2_HALF"] + n2 // 2 <= k["PHASE_CAP"]
     assert (n1 + 1) // 2 <= k["S1_HALF"]
     assert nph <= k["PHASE_CAP"]
+
+
+# ---- the block shapes tests/test_fmbank_gpu.py launches over several tiles (fm_ref.tile_cases) -------------------
+
+def _tile(built):
+    rc, _, _, _, tile = built.fmbank_grid(8, 1, 20, 1)
+    assert rc == 0
+    return tile
+
+
+def test_multi_tile_cases_meet_their_conditions(built):
+    """tests/test_fm_cpu.py's test of the same name with this library's tile: four tiles or more and a partial last
+    one, a map origin in a later block with a border behind it wherever a map skips, regime b's borders in the halos,
+    and the block_len = 23 case at the largest ranges any block shape reaches."""
+    k = _constants()
+    tile = _tile(built)
+    worst = _worst_tile_ranges(tile)
+    for line in fm_ref.case_report(tile, worst):
+        print(line)
+    print("tile %d, block_len 23 fills %d of %d phase slots, %d of %d per stage-1 half"
+          % (tile, worst[2], k["PHASE_CAP"], (worst[1] + 1) // 2, k["S1_HALF"]))
+    for c, R, C in fmbank_ref.tile_bank_runs(tile):
+        rc, blocks, _, _, t = built.fmbank_grid(R, C, c.block_len, c.nblocks)
+        assert rc == 0 and t == tile and blocks == (c.ntiles(tile) + 1) * -(-C // 8), (c.id, R, C)
+
+
+def test_multi_tile_inputs_reach_both_sides_of_the_limiter(oracle, built):
+    """On the reference alone: in every launch of the multi-tile suite every channel's demodulator output holds clamped
+    and unclamped samples."""
+    for c, R, C in fmbank_ref.tile_bank_runs(_tile(built)):
+        iq, words, states = fmbank_ref.case_inputs(c, R, C)
+        streams = ddc_ref.ddc_ref(iq, R, words)
+        for ch in range(C):
+            d = oracle.fm_demod(streams[ch], prev_phase=float(states[ch][0]))[0]
+            assert np.any(np.abs(d) == 1.0) and np.any(np.abs(d) < 1.0), (c.id, R, C, ch)
+
+
+@pytest.fixture(scope="module")
+def host_maps(built, tmp_path_factory):
+    cc = fm_ref.host_compiler()
+    if cc is None:
+        pytest.skip("no C++ compiler for the host")
+    return fm_ref.HostMaps(cc, CSRC, tmp_path_factory.mktemp("maps"), _tile(built))
+
+
+def test_tile_map_equals_maps_in_the_product_text(host_maps):
+    """fm_maps.h compiled for the host with this library's tile: TileMap, Maps and fm_ref's numpy maps agree at every
+    position every tile reads, for every block_len 20 .. 4200."""
+    print("tile %d: %d positions" % (host_maps.tile, fm_ref.sweep_host_maps(host_maps)))
+
+
+@pytest.mark.parametrize("residue", [0, 1, 2, 3])
+def test_tile_map_beyond_32_bits(host_maps, residue):
+    fm_ref.check_host_maps_beyond_32_bits(host_maps, residue)
+
+
+def test_wrong_tile_maps_pass_the_earlier_shapes_and_fail_the_new_ones(built):
+    fm_ref.check_wrong_tile_maps(_tile(built))
 
 
 def test_inputs_of_the_gpu_suite_reach_every_branch(oracle):

@@ -79,6 +79,33 @@ def test_tiles_with_block_borders_inside(engine, oracle, built, tile):
     check(engine.fm_bank(iq, R, words, L, states), fmbank_ref.expected(oracle, iq, R, words, L, states), L)
 
 
+# ---- every block shape over several tiles (fm_ref.tile_cases; tests/test_fmbank_cpu.py checks what the cases reach) ----
+
+CASES = [(regime, residue) for regime in "abc" for residue in range(4)]
+TILE_RUNS = [fmbank_ref.TILE_BANK + c for c in CASES] + [b + c for b in fmbank_ref.SKIP_BANKS for c in CASES if c[1] in (1, 3)]
+
+
+def _tile_case(built, tile, regime, residue, R, C):
+    """the case of the library's own tile, and its grid: per column tile one workgroup per tile and the one of the states"""
+    case = {(c.regime, c.residue): c for c in fm_ref.tile_cases(tile)}[regime, residue]
+    rc, blocks, _, _, t = built.fmbank_grid(R, C, case.block_len, case.nblocks)
+    assert rc == 0 and t == tile and case.ntiles(tile) >= 4 and blocks == (case.ntiles(tile) + 1) * -(-C // 8), case.id
+    return case
+
+
+@pytest.mark.parametrize("R,C,regime,residue", TILE_RUNS)
+def test_tile_cases(engine, oracle, built, tile, R, C, regime, residue):
+    """Dozens of tiny blocks per tile (block_len = 23 fills LDS as far as any shape can), borders just in front of
+    tiles, long blocks: every block_len mod 4 over four tiles or more, from carried states."""
+    case = _tile_case(built, tile, regime, residue, R, C)
+    iq, words, states = fmbank_ref.case_inputs(case, R, C)
+    want = fmbank_ref.expected(oracle, iq, R, words, case.block_len, states, key=("tile case", case, R, C))
+    got = engine.fm_bank(iq, R, words, case.block_len, states)
+    check(got, want, (case.id, R, C))
+    assert np.any(got[0] != 0)
+    assert np.array_equal(got[0][0], got[0][C - 1]) and np.array_equal(got[1][0], got[1][C - 1])      # the same station
+
+
 @pytest.mark.parametrize("name", ["axes", "all128"])
 def test_branch_inputs(engine, oracle, name):
     """The captures of tests/test_fmbank_cpu.py's input conditions: x == 0 with every sign of y, both sides of the
@@ -132,6 +159,26 @@ def test_chunks_concatenate_to_one_run(engine, oracle, built, tile, first):
     plan.close()
     if first:
         assert not np.array_equal(whole[0], engine.fm_bank(iq, R, words, L, states)[0])   # the index is in the phase
+
+
+def test_chunks_of_odd_blocks_with_borders_in_front_of_tiles(engine, oracle, built, tile):
+    """Both maps skipping, quarter = tile - 2, a first_dec_index beyond 2^40: calls cut behind blocks 1 and 4, the
+    state buffers swapped between them, equal the one call and the expected values."""
+    R, C = fmbank_ref.TILE_BANK
+    case = _tile_case(built, tile, "b", 3, R, C)
+    L, first, cuts = case.block_len, (1 << 40) + 12345, (0, 1, 4)
+    assert L % 2 == 1 and cuts[-1] == case.nblocks and all((a * L * R * 2) % 16 == 0 for a in cuts)
+    iq, words, states = fmbank_ref.case_inputs(case, R, C)
+    want = fmbank_ref.expected(oracle, iq, R, words, L, states, first)
+    whole = engine.fm_bank(iq, R, words, L, states, first_dec_index=first)
+    check(whole, want, "one call")
+    plan = built.FmBankPlan.open(engine)
+    chunks = _run_chunks(engine, plan, iq, R, words, L, states, first, cuts)
+    plan.close()
+    check(chunks, whole, cuts)
+    check(chunks, want, cuts)
+    unshifted = fmbank_ref.expected(oracle, iq, R, words, L, states, key=("tile case", case, R, C))
+    assert not np.array_equal(want[0], unshifted[0])                   # the index is in the phase
 
 
 def test_stride_and_nothing_outside_the_ranges(engine, oracle, built, tile):
