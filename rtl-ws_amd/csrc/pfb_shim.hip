@@ -1,0 +1,229 @@
+// pfb_shim.hip -- extern "C" glue of include/rtlws_pfb.h (librtlws_pfb.so): the prototype design, the transform's
+// table, argument rules, geometry, the launch.  The engine (device, stream) is librtlws_hip.so's; nothing here reads
+// the environment, and nothing of a run is computed on the host: without a device there is no plan.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "pfb_bank.h"
+#include "rtlws_pfb.h"
+
+struct rtlws_pfb_plan {
+    rtlws_engine* engine;
+    int device;
+    int log2_m, taps_per_branch;
+    int16_t* d_taps;
+    float2* d_tw;
+};
+
+namespace {
+
+using namespace rtlws::pfb;
+
+static_assert(MIN_LOG2_M == RTLWS_PFB_MIN_LOG2_CHANNELS && MAX_LOG2_M == RTLWS_PFB_MAX_LOG2_CHANNELS &&
+                  MAX_TAPS == RTLWS_PFB_MAX_TAPS && LAYOUT_CHANNEL == RTLWS_PFB_CHANNEL_MAJOR && LAYOUT_TIME == RTLWS_PFB_TIME_MAJOR,
+              "rtlws_pfb.h and pfb_bank.h disagree");
+
+thread_local std::string g_err;
+
+int fail(const char* fn, const char* why, int rc)
+{
+    g_err = std::string(fn) + ": " + why;
+    return rc;
+}
+
+int fail_hip(const char* fn, const char* what, hipError_t e)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
+    g_err = buf;
+    return -3;
+}
+
+// why a shape is not served, or nullptr; hop == 0: not asked
+const char* why_not(int k, int taps, int hop, long nframes)
+{
+    if (k < MIN_LOG2_M || k > MAX_LOG2_M) return "log2_channels must be 4 .. 10";
+    if (taps < 1 || taps > MAX_TAPS) return "taps_per_branch must be 1 .. 32";
+    if (hop != 0 && hop != 1 << k && hop != 1 << (k - 1)) return "hop must be M or M / 2";
+    if (nframes < 0) return "nframes must be >= 0";
+    if (nframes > (long)INT_MAX * tile_frames(k)) return "more frames than one grid holds";
+    return nullptr;
+}
+
+// e^(-2 pi i j / M) in f64, rounded once; the quadrant points exactly
+void build_twiddles(int k, float* re_im)
+{
+    const int M = 1 << k;
+    for (int j = 0; j < M; ++j) {
+        const double a = -2.0 * M_PI * (double)j / (double)M;
+        double c = std::cos(a), s = std::sin(a);
+        if ((4 * j) % M == 0) {
+            c = std::rint(c);
+            s = std::rint(s);
+        }
+        re_im[2 * j] = (float)c;
+        re_im[2 * j + 1] = (float)s;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* rtlws_pfb_last_error(void) { return g_err.c_str(); }
+
+int rtlws_pfb_supported(int log2_channels, int taps_per_branch, int hop)
+{
+    g_err.clear();
+    const char* why = hop == 0 ? "hop must be M or M / 2" : why_not(log2_channels, taps_per_branch, hop, 0);
+    if (why) fail("rtlws_pfb", why, 0);
+    return why ? 0 : 1;
+}
+
+int rtlws_pfb_design(int log2_channels, int taps_per_branch, int16_t* taps)
+{
+    g_err.clear();
+    if (const char* why = why_not(log2_channels, taps_per_branch, 0, 0)) return fail("rtlws_pfb_design", why, -1);
+    if (!taps) return fail("rtlws_pfb_design", "null pointer", -1);
+    const int M = 1 << log2_channels, N = taps_per_branch * M;
+    for (int n = 0; n < N; ++n) {
+        const double x = ((double)n - (double)(N - 1) / 2.0) / (double)M;
+        const double sinc = x == 0.0 ? 1.0 : std::sin(M_PI * x) / (M_PI * x);
+        const double w = 0.54 - 0.46 * std::cos(2.0 * M_PI * (double)n / (double)(N - 1));
+        taps[n] = (int16_t)std::rint(32767.0 * sinc * w);
+    }
+    return 0;
+}
+
+int rtlws_pfb_twiddles(int log2_channels, float* re_im)
+{
+    g_err.clear();
+    if (const char* why = why_not(log2_channels, 1, 0, 0)) return fail("rtlws_pfb_twiddles", why, -1);
+    if (!re_im) return fail("rtlws_pfb_twiddles", "null pointer", -1);
+    build_twiddles(log2_channels, re_im);
+    return 0;
+}
+
+long rtlws_pfb_samples_needed(int log2_channels, int taps_per_branch, int hop, long nframes)
+{
+    g_err.clear();
+    const char* why = hop == 0 ? "hop must be M or M / 2" : why_not(log2_channels, taps_per_branch, hop, nframes);
+    if (why) return fail("rtlws_pfb_samples_needed", why, -1);
+    if (nframes == 0) return 0;
+    return (nframes - 1) * hop + (long)taps_per_branch * (1L << log2_channels);
+}
+
+int rtlws_pfb_grid(int log2_channels, int taps_per_branch, int hop, long nframes, int* blocks, int* threads,
+                   int* lds_bytes, int* tile_frames_out)
+{
+    g_err.clear();
+    const char* why = hop == 0 ? "hop must be M or M / 2" : why_not(log2_channels, taps_per_branch, hop, nframes);
+    if (why) return fail("rtlws_pfb_grid", why, -1);
+    const int f = tile_frames(log2_channels);
+    if (blocks) *blocks = (int)((nframes + f - 1) / f);
+    if (threads) *threads = THREADS;
+    if (lds_bytes) *lds_bytes = rtlws::pfb::lds_bytes(log2_channels);
+    if (tile_frames_out) *tile_frames_out = f;
+    return 0;
+}
+
+rtlws_pfb_plan* rtlws_pfb_open(rtlws_engine* e, int log2_channels, int taps_per_branch, const int16_t* taps)
+{
+    const char* fn = "rtlws_pfb_open";
+    g_err.clear();
+    if (const char* why = why_not(log2_channels, taps_per_branch, 0, 0)) {
+        fail(fn, why, -1);
+        return nullptr;
+    }
+    if (!taps) {
+        fail(fn, "null taps", -1);
+        return nullptr;
+    }
+    if (!e) {
+        fail(fn, "null engine (no usable HIP device: there is no CPU path)", -1);
+        return nullptr;
+    }
+    const int device = rtlws_engine_device(e);
+    hipError_t err = hipSetDevice(device);
+    if (err != hipSuccess) {
+        fail_hip(fn, "hipSetDevice", err);
+        return nullptr;
+    }
+    const size_t M = (size_t)1 << log2_channels, ntaps = M * (size_t)taps_per_branch;
+    std::vector<float> tw(2 * M);
+    build_twiddles(log2_channels, tw.data());
+    int16_t* d_taps = nullptr;
+    float2* d_tw = nullptr;
+    err = hipMalloc(reinterpret_cast<void**>(&d_taps), ntaps * sizeof(int16_t));
+    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&d_tw), tw.size() * sizeof(float));
+    if (err == hipSuccess) err = hipMemcpy(d_taps, taps, ntaps * sizeof(int16_t), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = hipMemcpy(d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (err == hipSuccess) err = prepare_pfb(log2_channels);
+    if (err != hipSuccess) {
+        fail_hip(fn, "the taps, the table or the kernel", err);
+        if (d_taps) (void)hipFree(d_taps);
+        if (d_tw) (void)hipFree(d_tw);
+        return nullptr;
+    }
+    return new rtlws_pfb_plan{e, device, log2_channels, taps_per_branch, d_taps, d_tw};
+}
+
+void rtlws_pfb_close(rtlws_pfb_plan* p)
+{
+    if (!p) return;
+    if (hipSetDevice(p->device) == hipSuccess) {
+        (void)hipFree(p->d_taps);
+        (void)hipFree(p->d_tw);
+    }
+    delete p;
+}
+
+int rtlws_pfb_run(rtlws_pfb_plan* p, const void* d_iq_cu8, long nframes, int hop, long first_frame_index, int layout,
+                  void* d_out_cf32, long out_stride, void* stream)
+{
+    const char* fn = "rtlws_pfb_run";
+    g_err.clear();
+    // what needs no plan: the hop is a power of two 8 .. 1024, a frame holds at least 16 values
+    if (hop < 8 || hop > 1 << MAX_LOG2_M || (hop & (hop - 1))) return fail(fn, "hop must be M or M / 2", -1);
+    if (nframes < 0) return fail(fn, "nframes must be >= 0", -1);
+    if (nframes > (long)INT_MAX * tile_frames(MIN_LOG2_M)) return fail(fn, "more frames than one grid holds", -1);
+    if (first_frame_index < 0) return fail(fn, "first_frame_index must be >= 0", -1);
+    if (layout != LAYOUT_CHANNEL && layout != LAYOUT_TIME) return fail(fn, "unknown layout", -1);
+    if (out_stride < (layout == LAYOUT_CHANNEL ? nframes : 1L << MIN_LOG2_M)) return fail(fn, "out_stride too small for the layout", -1);
+    if (nframes > 0 && (!d_iq_cu8 || !d_out_cf32)) return fail(fn, "null pointer", -1);
+    if (reinterpret_cast<uintptr_t>(d_iq_cu8) & 15u) return fail(fn, "d_iq_cu8 must be 16-byte aligned", -1);
+    if (reinterpret_cast<uintptr_t>(d_out_cf32) & 7u) return fail(fn, "d_out_cf32 must be 8-byte aligned", -1);
+    if (!p) return fail(fn, "null plan (no usable HIP device: there is no CPU path)", -1);
+    // what the plan's shape decides; still before anything is asked of the device
+    if (const char* why = why_not(p->log2_m, p->taps_per_branch, hop, nframes)) return fail(fn, why, -1);
+    if (layout == LAYOUT_TIME && out_stride < 1L << p->log2_m) return fail(fn, "out_stride too small for the layout", -1);
+    if (nframes == 0) return 0;
+
+    hipError_t err = hipSetDevice(p->device);
+    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
+                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
+                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
+    PfbParams pp;
+    pp.src = d_iq_cu8;
+    pp.out = static_cast<float2*>(d_out_cf32);
+    pp.taps = p->d_taps;
+    pp.tw = p->d_tw;
+    pp.nframes = nframes;
+    pp.first = first_frame_index;
+    pp.out_stride = out_stride;
+    pp.taps_per_branch = p->taps_per_branch;
+    pp.half_hop = hop != 1 << p->log2_m;
+    pp.layout = layout;
+    err = launch_pfb(p->log2_m, pp, st);
+    if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
+    return 0;
+}
+
+}  // extern "C"

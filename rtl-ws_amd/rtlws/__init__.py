@@ -11,6 +11,7 @@ fail loudly.
   Engine.fm_audio_blocks[_cu8]  include/rtlws_fm.h (the FM receive chain in one launch)
   DdcPlan, Engine.ddc  include/rtlws_ddc.h (tuned channels from one capture: integer mixer + CIC in one launch)
   FmBankPlan, Engine.fm_bank  include/rtlws_fmbank.h (up to 32 FM stations from one capture in one launch)
+  PfbPlan, Engine.pfb  include/rtlws_pfb.h (polyphase channelizer: all 2^k channels of one capture in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -34,6 +35,7 @@ ANYLEN_LIB = os.path.join(LIB_DIR, "librtlws_anylen.so") # include/rtlws_anylen.
 FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
 FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.h
+PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -103,6 +105,10 @@ DDC_MAX_CHANNELS = 32
 FMBANK_SYMBOLS = ["rtlws_fmbank_supported", "rtlws_fmbank_grid", "rtlws_fmbank_open", "rtlws_fmbank_run",
                   "rtlws_fmbank_close", "rtlws_fmbank_last_error"]
 FMBANK_MAX_CHANNELS = 32
+PFB_SYMBOLS = ["rtlws_pfb_supported", "rtlws_pfb_design", "rtlws_pfb_twiddles", "rtlws_pfb_samples_needed", "rtlws_pfb_grid",
+               "rtlws_pfb_open", "rtlws_pfb_run", "rtlws_pfb_close", "rtlws_pfb_last_error"]
+PFB_CHANNEL_MAJOR, PFB_TIME_MAJOR = 0, 1       # rtlws_pfb.h: the output layouts
+_PFB_LAYOUTS = {"channel": PFB_CHANNEL_MAJOR, "time": PFB_TIME_MAJOR}
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -139,6 +145,7 @@ _anylen = None
 _fm = None
 _ddc = None
 _fmbank = None
+_pfb = None
 _amd = None
 _cbb = None
 
@@ -404,6 +411,75 @@ def fm_grid(block_len, nblocks, cic_r=0):
     return rc, b.value, t.value, s.value, a.value
 
 
+def pfb_lib():
+    """librtlws_pfb.so (include/rtlws_pfb.h); it needs librtlws_hip.so's engine."""
+    global _pfb
+    if _pfb is None:
+        hip_lib()
+        _need(PFB_LIB)
+        L = C.CDLL(PFB_LIB, mode=C.RTLD_GLOBAL)
+        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
+        L.rtlws_pfb_supported.argtypes = [i, i, i]
+        L.rtlws_pfb_design.argtypes = [i, i, vp]
+        L.rtlws_pfb_twiddles.argtypes = [i, vp]
+        L.rtlws_pfb_samples_needed.argtypes = [i, i, i, l]
+        L.rtlws_pfb_samples_needed.restype = l
+        L.rtlws_pfb_grid.argtypes = [i, i, i, l, ip, ip, ip, ip]
+        L.rtlws_pfb_open.argtypes = [vp, i, i, vp]
+        L.rtlws_pfb_open.restype = vp
+        L.rtlws_pfb_run.argtypes = [vp, vp, l, i, l, i, vp, l, vp]
+        L.rtlws_pfb_close.argtypes = [vp]
+        L.rtlws_pfb_close.restype = None
+        L.rtlws_pfb_last_error.restype = C.c_char_p
+        _pfb = L
+    return _pfb
+
+
+def pfb_last_error():
+    return pfb_lib().rtlws_pfb_last_error().decode()
+
+
+def pfb_supported(log2_channels, taps_per_branch, hop=None):
+    """rtlws_pfb_supported; hop None: M.  No GPU needed."""
+    hop = (1 << log2_channels if 0 <= log2_channels < 31 else 0) if hop is None else hop
+    return pfb_lib().rtlws_pfb_supported(int(log2_channels), int(taps_per_branch), int(hop))
+
+
+def pfb_design(log2_channels, taps_per_branch):
+    """rtlws_pfb_design: the Hamming-windowed sinc prototype, int16 [T * M].  No GPU needed."""
+    if pfb_supported(log2_channels, taps_per_branch) != 1:
+        raise RuntimeError("rtlws_pfb_design: %s" % pfb_last_error())
+    t = np.empty(int(taps_per_branch) << int(log2_channels), dtype=np.int16)
+    rc = pfb_lib().rtlws_pfb_design(int(log2_channels), int(taps_per_branch), _p(t))
+    if rc != 0:
+        raise RuntimeError("rtlws_pfb_design failed (rc=%d): %s" % (rc, pfb_last_error()))
+    return t
+
+
+def pfb_twiddles(log2_channels):
+    """rtlws_pfb_twiddles: e^(-2 pi i j / M) as the library builds it, float32 [M, 2].  No GPU needed."""
+    if pfb_supported(log2_channels, 1) != 1:
+        raise RuntimeError("rtlws_pfb_twiddles: %s" % pfb_last_error())
+    t = np.empty((1 << int(log2_channels), 2), dtype=np.float32)
+    rc = pfb_lib().rtlws_pfb_twiddles(int(log2_channels), _p(t))
+    if rc != 0:
+        raise RuntimeError("rtlws_pfb_twiddles failed (rc=%d): %s" % (rc, pfb_last_error()))
+    return t
+
+
+def pfb_samples_needed(log2_channels, taps_per_branch, hop, nframes):
+    """rtlws_pfb_samples_needed: (nframes - 1) hop + T M, or -1.  No GPU needed."""
+    return pfb_lib().rtlws_pfb_samples_needed(int(log2_channels), int(taps_per_branch), int(hop), int(nframes))
+
+
+def pfb_grid(log2_channels, taps_per_branch, hop, nframes):
+    """rtlws_pfb_grid: (rc, workgroups, threads, LDS bytes, frames per tile).  No GPU needed."""
+    b, t, s, f = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = pfb_lib().rtlws_pfb_grid(int(log2_channels), int(taps_per_branch), int(hop), int(nframes), C.byref(b), C.byref(t),
+                                  C.byref(s), C.byref(f))
+    return rc, b.value, t.value, s.value, f.value
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -602,6 +678,53 @@ class DdcPlan:
     def close(self):
         if self.h:
             ddc_lib().rtlws_ddc_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PfbPlan:
+    """rtlws_pfb_plan* of include/rtlws_pfb.h: the prototype (int16 [T * M]) and the transform's table on the engine's
+    device, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+
+    def __init__(self, eng, log2_channels, taps):
+        self.eng = eng
+        self.log2_channels = int(log2_channels)
+        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
+        if m == 0 or taps.size == 0 or taps.size % m:
+            raise RuntimeError("rtlws_pfb_open: the prototype holds taps_per_branch * M taps")
+        self.taps_per_branch = taps.size // m
+        self.h = pfb_lib().rtlws_pfb_open(eng.h if eng is not None else None, self.log2_channels, self.taps_per_branch, _p(taps))
+        if not self.h:
+            raise RuntimeError("rtlws_pfb_open failed: %s" % pfb_last_error())
+
+    @classmethod
+    def open(cls, eng, log2_channels, taps):
+        return cls(eng, log2_channels, taps)
+
+    def run(self, d_iq, nframes, d_out, hop=None, out_stride=None, first_frame_index=0, layout="channel", stream=None,
+            check=True):
+        """One launch.  layout "channel": channel c at d_out + c * out_stride values; "time": frame m at
+        d_out + m * out_stride values (or an integer: rtlws_pfb.h's constants)."""
+        m = 1 << self.log2_channels
+        lay = _PFB_LAYOUTS.get(layout, layout)
+        if out_stride is None:
+            out_stride = m if lay == PFB_TIME_MAJOR else nframes
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = pfb_lib().rtlws_pfb_run(self.h, ptr(d_iq), int(nframes), int(m if hop is None else hop), int(first_frame_index),
+                                     int(lay), ptr(d_out), int(out_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_pfb_run failed (rc=%d): %s" % (rc, pfb_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            pfb_lib().rtlws_pfb_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -842,6 +965,31 @@ class Engine:
             plan.run(cic_r, d_iq, dec_len, tuning_words, d_out, dec_len, first_dec_index)
             self.sync()
             out = self.download(d_out, np.int32, (nch, dec_len, 2)) if nch * dec_len else np.zeros((nch, 0, 2), np.int32)
+        finally:
+            plan.close()
+            d_iq.free()
+            d_out.free()
+        return out
+
+    # -- include/rtlws_pfb.h: host arrays in, all channels out ----
+    def pfb(self, iq, log2_channels, taps, hop=None, first_frame_index=0, layout="channel", nframes=None):
+        """rtlws_pfb_run: iq uint8 [(nframes - 1) * hop + T * M, 2], taps int16 [T * M] -> complex64 [M, nframes]
+        (layout "channel") or [nframes, M] ("time").  nframes None: as many as the capture holds."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        plan = PfbPlan(self, log2_channels, taps)
+        m, t = 1 << plan.log2_channels, plan.taps_per_branch
+        hop = m if hop is None else int(hop)
+        if nframes is None:
+            nframes = (iq.shape[0] - t * m) // hop + 1 if iq.shape[0] >= t * m and hop > 0 else 0
+        need = pfb_samples_needed(plan.log2_channels, t, hop, nframes)
+        assert need < 0 or iq.shape[0] >= need, "the capture is shorter than rtlws_pfb_samples_needed"
+        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
+        d_out = self.alloc(max(m * nframes, 1) * 8)
+        shape = (nframes, m) if _PFB_LAYOUTS.get(layout, layout) == PFB_TIME_MAJOR else (m, nframes)
+        try:
+            plan.run(d_iq, nframes, d_out, hop, None, first_frame_index, layout)
+            self.sync()
+            out = self.download(d_out, np.complex64, shape) if nframes else np.zeros(shape, np.complex64)
         finally:
             plan.close()
             d_iq.free()
