@@ -8,9 +8,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
-#include <vector>
 
 #include "pfb_bank.h"
+#include "pfb_plan.h"
 #include "rtlws_pfb.h"
 
 struct rtlws_pfb_plan {
@@ -54,22 +54,6 @@ const char* why_not(int k, int taps, int hop, long nframes)
     if (nframes < 0) return "nframes must be >= 0";
     if (nframes > (long)INT_MAX * tile_frames(k)) return "more frames than one grid holds";
     return nullptr;
-}
-
-// e^(-2 pi i j / M) in f64, rounded once; the quadrant points exactly
-void build_twiddles(int k, float* re_im)
-{
-    const int M = 1 << k;
-    for (int j = 0; j < M; ++j) {
-        const double a = -2.0 * M_PI * (double)j / (double)M;
-        double c = std::cos(a), s = std::sin(a);
-        if ((4 * j) % M == 0) {
-            c = std::rint(c);
-            s = std::rint(s);
-        }
-        re_im[2 * j] = (float)c;
-        re_im[2 * j + 1] = (float)s;
-    }
 }
 
 }  // namespace
@@ -155,20 +139,15 @@ rtlws_pfb_plan* rtlws_pfb_open(rtlws_engine* e, int log2_channels, int taps_per_
         fail_hip(fn, "hipSetDevice", err);
         return nullptr;
     }
-    const size_t M = (size_t)1 << log2_channels, ntaps = M * (size_t)taps_per_branch;
-    std::vector<float> tw(2 * M);
-    build_twiddles(log2_channels, tw.data());
     int16_t* d_taps = nullptr;
     float2* d_tw = nullptr;
-    err = hipMalloc(reinterpret_cast<void**>(&d_taps), ntaps * sizeof(int16_t));
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&d_tw), tw.size() * sizeof(float));
-    if (err == hipSuccess) err = hipMemcpy(d_taps, taps, ntaps * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_pfb(log2_channels);
+    err = upload_plan_arrays(log2_channels, taps_per_branch, taps, &d_taps, &d_tw);
+    if (err == hipSuccess) {
+        err = prepare_pfb(log2_channels);
+        if (err != hipSuccess) free_plan_arrays(d_taps, d_tw);
+    }
     if (err != hipSuccess) {
         fail_hip(fn, "the taps, the table or the kernel", err);
-        if (d_taps) (void)hipFree(d_taps);
-        if (d_tw) (void)hipFree(d_tw);
         return nullptr;
     }
     return new rtlws_pfb_plan{e, device, log2_channels, taps_per_branch, d_taps, d_tw};
@@ -177,10 +156,7 @@ rtlws_pfb_plan* rtlws_pfb_open(rtlws_engine* e, int log2_channels, int taps_per_
 void rtlws_pfb_close(rtlws_pfb_plan* p)
 {
     if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) {
-        (void)hipFree(p->d_taps);
-        (void)hipFree(p->d_tw);
-    }
+    if (hipSetDevice(p->device) == hipSuccess) free_plan_arrays(p->d_taps, p->d_tw);
     delete p;
 }
 

@@ -12,6 +12,7 @@ fail loudly.
   DdcPlan, Engine.ddc  include/rtlws_ddc.h (tuned channels from one capture: integer mixer + CIC in one launch)
   FmBankPlan, Engine.fm_bank  include/rtlws_fmbank.h (up to 32 FM stations from one capture in one launch)
   PfbPlan, Engine.pfb  include/rtlws_pfb.h (polyphase channelizer: all 2^k channels of one capture in one launch)
+  PfbSpecPlan, Engine.pfbspec  include/rtlws_pfbspec.h (polyphase spectrometer: K-frame power of all 2^k channels in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -36,6 +37,7 @@ FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
 FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.h
 PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
+PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfbspec.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -109,6 +111,12 @@ PFB_SYMBOLS = ["rtlws_pfb_supported", "rtlws_pfb_design", "rtlws_pfb_twiddles", 
                "rtlws_pfb_open", "rtlws_pfb_run", "rtlws_pfb_close", "rtlws_pfb_last_error"]
 PFB_CHANNEL_MAJOR, PFB_TIME_MAJOR = 0, 1       # rtlws_pfb.h: the output layouts
 _PFB_LAYOUTS = {"channel": PFB_CHANNEL_MAJOR, "time": PFB_TIME_MAJOR}
+PFBSPEC_SYMBOLS = ["rtlws_pfbspec_supported", "rtlws_pfbspec_samples_needed", "rtlws_pfbspec_grid", "rtlws_pfbspec_open",
+                   "rtlws_pfbspec_run", "rtlws_pfbspec_close", "rtlws_pfbspec_last_error"]
+PFBSPEC_MAX_K_AVG = 65536
+# rtlws_pfbspec.h's output kinds are enum rtlws_output's values
+_PFBSPEC_OUTPUTS = {"power": OUT_POWER_SUM, "db": OUT_MEAN_DB, "payload": OUT_PAYLOAD_U8}
+_PFBSPEC_OUTPUTS.update(_OUTPUTS)
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -146,6 +154,7 @@ _fm = None
 _ddc = None
 _fmbank = None
 _pfb = None
+_pfbspec = None
 _amd = None
 _cbb = None
 
@@ -480,6 +489,52 @@ def pfb_grid(log2_channels, taps_per_branch, hop, nframes):
     return rc, b.value, t.value, s.value, f.value
 
 
+def pfbspec_lib():
+    """librtlws_pfbspec.so (include/rtlws_pfbspec.h); it needs librtlws_hip.so's engine."""
+    global _pfbspec
+    if _pfbspec is None:
+        hip_lib()
+        _need(PFBSPEC_LIB)
+        L = C.CDLL(PFBSPEC_LIB, mode=C.RTLD_GLOBAL)
+        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
+        L.rtlws_pfbspec_supported.argtypes = [i, i, i, i, i]
+        L.rtlws_pfbspec_samples_needed.argtypes = [i, i, i, i, l]
+        L.rtlws_pfbspec_samples_needed.restype = l
+        L.rtlws_pfbspec_grid.argtypes = [i, i, i, i, l, ip, ip, ip, ip]
+        L.rtlws_pfbspec_open.argtypes = [vp, i, i, vp]
+        L.rtlws_pfbspec_open.restype = vp
+        L.rtlws_pfbspec_run.argtypes = [vp, vp, l, i, i, i, i, C.c_float, vp, l, vp]
+        L.rtlws_pfbspec_close.argtypes = [vp]
+        L.rtlws_pfbspec_close.restype = None
+        L.rtlws_pfbspec_last_error.restype = C.c_char_p
+        _pfbspec = L
+    return _pfbspec
+
+
+def pfbspec_last_error():
+    return pfbspec_lib().rtlws_pfbspec_last_error().decode()
+
+
+def pfbspec_supported(log2_channels, taps_per_branch, hop, k_avg, output="power"):
+    """rtlws_pfbspec_supported.  No GPU needed."""
+    return pfbspec_lib().rtlws_pfbspec_supported(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg),
+                                                 int(_PFBSPEC_OUTPUTS.get(output, output)))
+
+
+def pfbspec_samples_needed(log2_channels, taps_per_branch, hop, k_avg, nspectra):
+    """rtlws_pfbspec_samples_needed: (nspectra K - 1) hop + T M, or -1.  No GPU needed."""
+    return pfbspec_lib().rtlws_pfbspec_samples_needed(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg),
+                                                      int(nspectra))
+
+
+def pfbspec_grid(log2_channels, taps_per_branch, hop, k_avg, nspectra):
+    """rtlws_pfbspec_grid: (rc, workgroups, threads, LDS bytes, spectra per workgroup).  No GPU needed."""
+    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = pfbspec_lib().rtlws_pfbspec_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nspectra),
+                                          C.byref(b), C.byref(t), C.byref(s), C.byref(g))
+    return rc, b.value, t.value, s.value, g.value
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -678,6 +733,53 @@ class DdcPlan:
     def close(self):
         if self.h:
             ddc_lib().rtlws_ddc_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PfbSpecPlan:
+    """rtlws_pfbspec_plan* of include/rtlws_pfbspec.h: the prototype (int16 [T * M]) and the transform's table on the
+    engine's device, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the
+    library's text."""
+
+    def __init__(self, eng, log2_channels, taps):
+        self.eng = eng
+        self.log2_channels = int(log2_channels)
+        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
+        if m == 0 or taps.size == 0 or taps.size % m:
+            raise RuntimeError("rtlws_pfbspec_open: the prototype holds taps_per_branch * M taps")
+        self.taps_per_branch = taps.size // m
+        self.h = pfbspec_lib().rtlws_pfbspec_open(eng.h if eng is not None else None, self.log2_channels,
+                                                  self.taps_per_branch, _p(taps))
+        if not self.h:
+            raise RuntimeError("rtlws_pfbspec_open failed: %s" % pfbspec_last_error())
+
+    @classmethod
+    def open(cls, eng, log2_channels, taps):
+        return cls(eng, log2_channels, taps)
+
+    def run(self, d_iq, nspectra, k_avg, d_out, hop=None, output="power", shifted=False, scale=1.0, out_stride=None,
+            stream=None, check=True):
+        """One launch: row j at d_out + j * out_stride elements (f32, or bytes for "payload").  output: "power", "db",
+        "payload" or a value of enum rtlws_output."""
+        m = 1 << self.log2_channels
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = pfbspec_lib().rtlws_pfbspec_run(self.h, ptr(d_iq), int(nspectra), int(m if hop is None else hop), int(k_avg),
+                                             int(_PFBSPEC_OUTPUTS.get(output, output)), int(shifted), float(scale), ptr(d_out),
+                                             int(m if out_stride is None else out_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_pfbspec_run failed (rc=%d): %s" % (rc, pfbspec_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            pfbspec_lib().rtlws_pfbspec_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -990,6 +1092,33 @@ class Engine:
             plan.run(d_iq, nframes, d_out, hop, None, first_frame_index, layout)
             self.sync()
             out = self.download(d_out, np.complex64, shape) if nframes else np.zeros(shape, np.complex64)
+        finally:
+            plan.close()
+            d_iq.free()
+            d_out.free()
+        return out
+
+    # -- include/rtlws_pfbspec.h: host arrays in, one row per K frames out ----
+    def pfbspec(self, iq, log2_channels, taps, k_avg, hop=None, output="power", shifted=False, scale=1.0, nspectra=None):
+        """rtlws_pfbspec_run: iq uint8 [(nspectra * k_avg - 1) * hop + T * M, 2], taps int16 [T * M] -> float32
+        [nspectra, M] ("power": the K-frame sums; "db": 10 log10(sum * scale / K)) or uint8 [nspectra, M] ("payload").
+        nspectra None: as many as the capture holds."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        plan = PfbSpecPlan(self, log2_channels, taps)
+        m, t, k_avg = 1 << plan.log2_channels, plan.taps_per_branch, int(k_avg)
+        hop = m if hop is None else int(hop)
+        if nspectra is None:
+            nframes = (iq.shape[0] - t * m) // hop + 1 if iq.shape[0] >= t * m and hop > 0 else 0
+            nspectra = nframes // k_avg if k_avg > 0 else 0
+        need = pfbspec_samples_needed(plan.log2_channels, t, hop, k_avg, nspectra)
+        assert need < 0 or iq.shape[0] >= need, "the capture is shorter than rtlws_pfbspec_samples_needed"
+        dtype = np.uint8 if _PFBSPEC_OUTPUTS.get(output, output) == OUT_PAYLOAD_U8 else np.float32
+        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
+        d_out = self.alloc(max(m * nspectra, 1) * np.dtype(dtype).itemsize)
+        try:
+            plan.run(d_iq, nspectra, k_avg, d_out, hop, output, shifted, scale)
+            self.sync()
+            out = self.download(d_out, dtype, (nspectra, m)) if nspectra else np.zeros((nspectra, m), dtype)
         finally:
             plan.close()
             d_iq.free()
