@@ -13,6 +13,7 @@ fail loudly.
   FmBankPlan, Engine.fm_bank  include/rtlws_fmbank.h (up to 32 FM stations from one capture in one launch)
   PfbPlan, Engine.pfb  include/rtlws_pfb.h (polyphase channelizer: all 2^k channels of one capture in one launch)
   PfbSpecPlan, Engine.pfbspec  include/rtlws_pfbspec.h (polyphase spectrometer: K-frame power of all 2^k channels in one launch)
+  PfbXcPlan, Engine.pfbxc  include/rtlws_pfbxc.h (polyphase cross-correlator: K-frame powers and cross-spectra of 2-4 captures in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -38,6 +39,7 @@ DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
 FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.h
 PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
 PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfbspec.h
+PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -117,6 +119,10 @@ PFBSPEC_MAX_K_AVG = 65536
 # rtlws_pfbspec.h's output kinds are enum rtlws_output's values
 _PFBSPEC_OUTPUTS = {"power": OUT_POWER_SUM, "db": OUT_MEAN_DB, "payload": OUT_PAYLOAD_U8}
 _PFBSPEC_OUTPUTS.update(_OUTPUTS)
+PFBXC_SYMBOLS = ["rtlws_pfbxc_supported", "rtlws_pfbxc_samples_needed", "rtlws_pfbxc_pair_index", "rtlws_pfbxc_grid",
+                 "rtlws_pfbxc_open", "rtlws_pfbxc_run", "rtlws_pfbxc_close", "rtlws_pfbxc_last_error"]
+PFBXC_MAX_K_AVG = 65536
+PFBXC_MIN_INPUTS, PFBXC_MAX_INPUTS = 2, 4
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -155,6 +161,7 @@ _ddc = None
 _fmbank = None
 _pfb = None
 _pfbspec = None
+_pfbxc = None
 _amd = None
 _cbb = None
 
@@ -535,6 +542,57 @@ def pfbspec_grid(log2_channels, taps_per_branch, hop, k_avg, nspectra):
     return rc, b.value, t.value, s.value, g.value
 
 
+def pfbxc_lib():
+    """librtlws_pfbxc.so (include/rtlws_pfbxc.h); it needs librtlws_hip.so's engine."""
+    global _pfbxc
+    if _pfbxc is None:
+        hip_lib()
+        _need(PFBXC_LIB)
+        L = C.CDLL(PFBXC_LIB, mode=C.RTLD_GLOBAL)
+        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
+        L.rtlws_pfbxc_supported.argtypes = [i, i, i, i, i]
+        L.rtlws_pfbxc_samples_needed.argtypes = [i, i, i, i, l]
+        L.rtlws_pfbxc_samples_needed.restype = l
+        L.rtlws_pfbxc_pair_index.argtypes = [i, i, i]
+        L.rtlws_pfbxc_grid.argtypes = [i, i, i, i, i, l, ip, ip, ip, ip]
+        L.rtlws_pfbxc_open.argtypes = [vp, i, i, vp, i]
+        L.rtlws_pfbxc_open.restype = vp
+        L.rtlws_pfbxc_run.argtypes = [vp, C.POINTER(vp), l, i, i, i, vp, l, vp, l, vp]
+        L.rtlws_pfbxc_close.argtypes = [vp]
+        L.rtlws_pfbxc_close.restype = None
+        L.rtlws_pfbxc_last_error.restype = C.c_char_p
+        _pfbxc = L
+    return _pfbxc
+
+
+def pfbxc_last_error():
+    return pfbxc_lib().rtlws_pfbxc_last_error().decode()
+
+
+def pfbxc_supported(log2_channels, taps_per_branch, hop, k_avg, ninputs=2):
+    """rtlws_pfbxc_supported.  No GPU needed."""
+    return pfbxc_lib().rtlws_pfbxc_supported(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(ninputs))
+
+
+def pfbxc_samples_needed(log2_channels, taps_per_branch, hop, k_avg, nspectra):
+    """rtlws_pfbxc_samples_needed: (nspectra K - 1) hop + T M per capture, or -1.  No GPU needed."""
+    return pfbxc_lib().rtlws_pfbxc_samples_needed(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg),
+                                                  int(nspectra))
+
+
+def pfbxc_pair_index(ninputs, a, b):
+    """rtlws_pfbxc_pair_index: the row of the pair a < b among a spectrum's cross rows, or -1.  No GPU needed."""
+    return pfbxc_lib().rtlws_pfbxc_pair_index(int(ninputs), int(a), int(b))
+
+
+def pfbxc_grid(log2_channels, taps_per_branch, hop, k_avg, ninputs, nspectra):
+    """rtlws_pfbxc_grid: (rc, workgroups, threads, LDS bytes, spectra per workgroup).  No GPU needed."""
+    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = pfbxc_lib().rtlws_pfbxc_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(ninputs),
+                                      int(nspectra), C.byref(b), C.byref(t), C.byref(s), C.byref(g))
+    return rc, b.value, t.value, s.value, g.value
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -780,6 +838,56 @@ class PfbSpecPlan:
     def close(self):
         if self.h:
             pfbspec_lib().rtlws_pfbspec_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PfbXcPlan:
+    """rtlws_pfbxc_plan* of include/rtlws_pfbxc.h: the prototype (int16 [T * M]) and the transform's table on the
+    engine's device, the kernel for ninputs captures loaded.  eng may be None (as a C caller's NULL engine): open then
+    fails with the library's text."""
+
+    def __init__(self, eng, log2_channels, taps, ninputs):
+        self.eng = eng
+        self.log2_channels = int(log2_channels)
+        self.ninputs = int(ninputs)
+        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
+        if m == 0 or taps.size == 0 or taps.size % m:
+            raise RuntimeError("rtlws_pfbxc_open: the prototype holds taps_per_branch * M taps")
+        self.taps_per_branch = taps.size // m
+        self.h = pfbxc_lib().rtlws_pfbxc_open(eng.h if eng is not None else None, self.log2_channels,
+                                              self.taps_per_branch, _p(taps), self.ninputs)
+        if not self.h:
+            raise RuntimeError("rtlws_pfbxc_open failed: %s" % pfbxc_last_error())
+
+    @classmethod
+    def open(cls, eng, log2_channels, taps, ninputs):
+        return cls(eng, log2_channels, taps, ninputs)
+
+    def run(self, d_iqs, nspectra, k_avg, d_auto, d_cross, hop=None, shifted=False, auto_stride=None, cross_stride=None,
+            stream=None, check=True):
+        """One launch.  d_iqs: the captures' device buffers or pointers, or None (a NULL array).  Row j * A + a of
+        d_auto (auto_stride floats apart) is S_a[j]; row j * NX + x of d_cross (cross_stride complex values apart)
+        is V_ab[j]."""
+        m = 1 << self.log2_channels
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        arr = None if d_iqs is None else (C.c_void_p * max(len(d_iqs), 1))(*[ptr(x) for x in d_iqs])
+        rc = pfbxc_lib().rtlws_pfbxc_run(self.h, arr, int(nspectra), int(m if hop is None else hop), int(k_avg), int(shifted),
+                                         ptr(d_auto), int(m if auto_stride is None else auto_stride), ptr(d_cross),
+                                         int(m if cross_stride is None else cross_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_pfbxc_run failed (rc=%d): %s" % (rc, pfbxc_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            pfbxc_lib().rtlws_pfbxc_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -1124,6 +1232,47 @@ class Engine:
             d_iq.free()
             d_out.free()
         return out
+
+    # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
+    def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
+        """rtlws_pfbxc_run: iqs a sequence of A = 2 .. 4 captures, each uint8 [(nspectra * k_avg - 1) * hop + T * M, 2]
+        (one array may be given twice: it is uploaded once and its pointer passed twice), taps int16 [T * M] ->
+        (float32 [nspectra, A, M], the K-frame powers; complex64 [nspectra, A (A - 1) / 2, M], the K-frame
+        cross-spectra of the pairs a < b row-major).  nspectra None: as many as the shortest capture holds."""
+        same = {id(x): np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 2) for x in iqs if x is not None}
+        iqs = [x if x is None else same[id(x)] for x in iqs]
+        a = len(iqs)
+        plan = PfbXcPlan(self, log2_channels, taps, a)
+        nx = a * (a - 1) // 2
+        m, t, k_avg = 1 << plan.log2_channels, plan.taps_per_branch, int(k_avg)
+        hop = m if hop is None else int(hop)
+        shortest = min(x.shape[0] for x in iqs if x is not None)
+        if nspectra is None:
+            nframes = (shortest - t * m) // hop + 1 if shortest >= t * m and hop > 0 else 0
+            nspectra = nframes // k_avg if k_avg > 0 else 0
+        need = pfbxc_samples_needed(plan.log2_channels, t, hop, k_avg, nspectra)
+        assert need < 0 or shortest >= need, "a capture is shorter than rtlws_pfbxc_samples_needed"
+        bufs = {}
+        for x in iqs:
+            if x is not None and id(x) not in bufs:
+                bufs[id(x)] = self.upload(x) if x.nbytes else self.alloc(16)
+        d_auto = self.alloc(max(nspectra * a * m, 1) * 4)
+        d_cross = self.alloc(max(nspectra * nx * m, 1) * 8)
+        try:
+            plan.run([None if x is None else bufs[id(x)] for x in iqs], nspectra, k_avg, d_auto, d_cross, hop, shifted)
+            self.sync()
+            if nspectra:
+                autos = self.download(d_auto, np.float32, (nspectra, a, m))
+                cross = self.download(d_cross, np.complex64, (nspectra, nx, m))
+            else:
+                autos, cross = np.zeros((0, a, m), np.float32), np.zeros((0, nx, m), np.complex64)
+        finally:
+            plan.close()
+            for b in bufs.values():
+                b.free()
+            d_auto.free()
+            d_cross.free()
+        return autos, cross
 
     # -- include/rtlws_fmbank.h: host arrays in, (audio, new states) out ----
     def fm_bank(self, iq, cic_r, tuning_words, block_len, states, first_dec_index=0):
