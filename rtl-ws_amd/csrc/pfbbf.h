@@ -1,0 +1,48 @@
+// pfbbf.h -- shared between pfbbf.hip (the kernels) and pfbbf_shim.hip (rtlws_pfbbf.h's host glue).
+#ifndef RTLWS_CSRC_PFBBF_H
+#define RTLWS_CSRC_PFBBF_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "pfb_bank.h"
+
+namespace rtlws {
+namespace pfbbf {
+
+constexpr int MAX_K_AVG = 65536;
+constexpr int MIN_INPUTS = 1, MAX_INPUTS = 8;
+constexpr int MIN_BEAMS = 1, MAX_BEAMS = 4;
+
+// Voltage mode has the channelizer's geometry (pfb_bank.h): a workgroup owns pfb::tile_frames(k)
+// frames.  Power mode has the spectrometer's (pfbspec.h), a function of (log2 M, K) alone: with
+// F = pfb::tile_frames(k), a workgroup owns one spectrum over ceil(K / F) tile iterations where K >= F, else
+// floor(F / K) spectra in one tile; a spectrum's frames are summed in slices of SLICE = min(16, F).
+// One tile serves every number of inputs and beams: the beams' running values stay in registers.
+constexpr int slice_frames(int k) { return pfb::tile_frames(k) < 16 ? pfb::tile_frames(k) : 16; }
+constexpr int spectra_per_block(int k, int k_avg) { return k_avg >= pfb::tile_frames(k) ? 1 : pfb::tile_frames(k) / k_avg; }
+constexpr int lds_bytes(int k) { return pfb::lds_bytes(k); }
+
+struct BfParams {
+    // taps, tw, taps_per_branch, half_hop; src unused.  Voltage mode: out, nframes, first, out_stride, layout are the
+    // channelizer's.  Power mode: nframes = nspectra * k_avg, first = 0
+    pfb::PfbParams bank;
+    const void* src[MAX_INPUTS];  // the captures, cmplx_u8; those at or behind ninputs are null
+    const float2* w;              // W[b][a][c], [nbeams][ninputs][M]
+    float* rows;                  // power mode: row j * B + b is S_b[j]
+    long beam_stride;             // voltage mode: beam b at out + b * beam_stride complex values
+    long nspectra, row_stride;    // power mode; the stride in floats
+    int ninputs;
+    int k_avg;
+    int shift;                    // power mode: 0, or M / 2: value i of a row is channel (i + shift) mod M
+};
+
+// voltage mode: ceil(nframes / tile_frames) workgroups, nframes > 0; power mode: ceil(nspectra / spectra_per_block)
+// workgroups, nspectra > 0.  k = pfb::MIN_LOG2_M .. pfb::MAX_LOG2_M, nbeams = MIN_BEAMS .. MAX_BEAMS
+hipError_t launch_pfbbf(int k, int nbeams, const BfParams& p, hipStream_t st);
+hipError_t launch_pfbbf_power(int k, int nbeams, const BfParams& p, hipStream_t st);
+hipError_t prepare_pfbbf(int k, int nbeams);
+
+}  // namespace pfbbf
+}  // namespace rtlws
+#endif

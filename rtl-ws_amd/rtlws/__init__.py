@@ -14,6 +14,7 @@ fail loudly.
   PfbPlan, Engine.pfb  include/rtlws_pfb.h (polyphase channelizer: all 2^k channels of one capture in one launch)
   PfbSpecPlan, Engine.pfbspec  include/rtlws_pfbspec.h (polyphase spectrometer: K-frame power of all 2^k channels in one launch)
   PfbXcPlan, Engine.pfbxc  include/rtlws_pfbxc.h (polyphase cross-correlator: K-frame powers and cross-spectra of 2-4 captures in one launch)
+  PfbBfPlan, Engine.pfbbf, Engine.pfbbf_power  include/rtlws_pfbbf.h (polyphase beamformer: 1-4 weighted beams of 1-8 captures in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -40,6 +41,7 @@ FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.
 PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
 PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfbspec.h
 PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
+PFBBF_LIB = os.path.join(LIB_DIR, "librtlws_pfbbf.so")   # include/rtlws_pfbbf.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -123,6 +125,11 @@ PFBXC_SYMBOLS = ["rtlws_pfbxc_supported", "rtlws_pfbxc_samples_needed", "rtlws_p
                  "rtlws_pfbxc_open", "rtlws_pfbxc_run", "rtlws_pfbxc_close", "rtlws_pfbxc_last_error"]
 PFBXC_MAX_K_AVG = 65536
 PFBXC_MIN_INPUTS, PFBXC_MAX_INPUTS = 2, 4
+PFBBF_SYMBOLS = ["rtlws_pfbbf_supported", "rtlws_pfbbf_samples_needed", "rtlws_pfbbf_grid", "rtlws_pfbbf_open",
+                 "rtlws_pfbbf_run", "rtlws_pfbbf_power", "rtlws_pfbbf_close", "rtlws_pfbbf_last_error"]
+PFBBF_MAX_K_AVG = 65536
+PFBBF_MIN_INPUTS, PFBBF_MAX_INPUTS = 1, 8
+PFBBF_MIN_BEAMS, PFBBF_MAX_BEAMS = 1, 4
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -162,6 +169,7 @@ _fmbank = None
 _pfb = None
 _pfbspec = None
 _pfbxc = None
+_pfbbf = None
 _amd = None
 _cbb = None
 
@@ -593,6 +601,52 @@ def pfbxc_grid(log2_channels, taps_per_branch, hop, k_avg, ninputs, nspectra):
     return rc, b.value, t.value, s.value, g.value
 
 
+def pfbbf_lib():
+    """librtlws_pfbbf.so (include/rtlws_pfbbf.h); it needs librtlws_hip.so's engine."""
+    global _pfbbf
+    if _pfbbf is None:
+        hip_lib()
+        _need(PFBBF_LIB)
+        L = C.CDLL(PFBBF_LIB, mode=C.RTLD_GLOBAL)
+        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
+        L.rtlws_pfbbf_supported.argtypes = [i, i, i, i, i]
+        L.rtlws_pfbbf_samples_needed.argtypes = [i, i, i, i, l]
+        L.rtlws_pfbbf_samples_needed.restype = l
+        L.rtlws_pfbbf_grid.argtypes = [i, i, i, i, l, ip, ip, ip, ip]
+        L.rtlws_pfbbf_open.argtypes = [vp, i, i, vp, i, i]
+        L.rtlws_pfbbf_open.restype = vp
+        L.rtlws_pfbbf_run.argtypes = [vp, C.POINTER(vp), i, vp, i, l, i, l, i, vp, l, l, vp]
+        L.rtlws_pfbbf_power.argtypes = [vp, C.POINTER(vp), i, vp, i, l, i, i, i, vp, l, vp]
+        L.rtlws_pfbbf_close.argtypes = [vp]
+        L.rtlws_pfbbf_close.restype = None
+        L.rtlws_pfbbf_last_error.restype = C.c_char_p
+        _pfbbf = L
+    return _pfbbf
+
+
+def pfbbf_last_error():
+    return pfbbf_lib().rtlws_pfbbf_last_error().decode()
+
+
+def pfbbf_supported(log2_channels, taps_per_branch, hop, ninputs=1, nbeams=1):
+    """rtlws_pfbbf_supported.  No GPU needed."""
+    return pfbbf_lib().rtlws_pfbbf_supported(int(log2_channels), int(taps_per_branch), int(hop), int(ninputs), int(nbeams))
+
+
+def pfbbf_samples_needed(log2_channels, taps_per_branch, hop, k_avg, count):
+    """rtlws_pfbbf_samples_needed per capture: k_avg 0 (voltage mode) (count - 1) hop + T M for count frames, else
+    (count K - 1) hop + T M for count spectra; or -1.  No GPU needed."""
+    return pfbbf_lib().rtlws_pfbbf_samples_needed(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(count))
+
+
+def pfbbf_grid(log2_channels, taps_per_branch, hop, k_avg, count):
+    """rtlws_pfbbf_grid: (rc, workgroups, threads, LDS bytes, frames (k_avg 0) or spectra per workgroup).  No GPU needed."""
+    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = pfbbf_lib().rtlws_pfbbf_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(count),
+                                      C.byref(b), C.byref(t), C.byref(s), C.byref(g))
+    return rc, b.value, t.value, s.value, g.value
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -888,6 +942,80 @@ class PfbXcPlan:
     def close(self):
         if self.h:
             pfbxc_lib().rtlws_pfbxc_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PfbBfPlan:
+    """rtlws_pfbbf_plan* of include/rtlws_pfbbf.h: the prototype (int16 [T * M]) and the transform's table on the
+    engine's device, both kernels for nbeams beams loaded.  eng may be None (as a C caller's NULL engine): open then
+    fails with the library's text."""
+
+    def __init__(self, eng, log2_channels, taps, ninputs, nbeams):
+        self.eng = eng
+        self.log2_channels = int(log2_channels)
+        self.ninputs, self.nbeams = int(ninputs), int(nbeams)
+        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
+        if m == 0 or taps.size == 0 or taps.size % m:
+            raise RuntimeError("rtlws_pfbbf_open: the prototype holds taps_per_branch * M taps")
+        self.taps_per_branch = taps.size // m
+        self.h = pfbbf_lib().rtlws_pfbbf_open(eng.h if eng is not None else None, self.log2_channels,
+                                              self.taps_per_branch, _p(taps), self.ninputs, self.nbeams)
+        if not self.h:
+            raise RuntimeError("rtlws_pfbbf_open failed: %s" % pfbbf_last_error())
+
+    @classmethod
+    def open(cls, eng, log2_channels, taps, ninputs, nbeams):
+        return cls(eng, log2_channels, taps, ninputs, nbeams)
+
+    @staticmethod
+    def _array(d_iqs):
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        return None if d_iqs is None else (C.c_void_p * max(len(d_iqs), 1))(*[ptr(x) for x in d_iqs])
+
+    def run(self, d_iqs, d_weights, nframes, d_out, hop=None, out_stride=None, beam_stride=None, first_frame_index=0,
+            layout="channel", stream=None, check=True, ninputs=None, nbeams=None):
+        """Voltage mode, one launch.  d_iqs: the captures' device buffers or pointers, or None (a NULL array);
+        d_weights: complex f32 [B, A, M] on the device.  Beam b at d_out + b * beam_stride values, inside it layout
+        "channel": channel c at c * out_stride; "time": frame m at m * out_stride.  The strides default to the
+        densest."""
+        m = 1 << self.log2_channels
+        lay = _PFB_LAYOUTS.get(layout, layout)
+        if out_stride is None:
+            out_stride = m if lay == PFB_TIME_MAJOR else nframes
+        if beam_stride is None:
+            beam_stride = m * nframes
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = pfbbf_lib().rtlws_pfbbf_run(self.h, self._array(d_iqs), int(self.ninputs if ninputs is None else ninputs),
+                                         ptr(d_weights), int(self.nbeams if nbeams is None else nbeams), int(nframes),
+                                         int(m if hop is None else hop), int(first_frame_index), int(lay), ptr(d_out),
+                                         int(out_stride), int(beam_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_pfbbf_run failed (rc=%d): %s" % (rc, pfbbf_last_error()))
+        return rc
+
+    def power(self, d_iqs, d_weights, nspectra, k_avg, d_out, hop=None, shifted=False, row_stride=None, stream=None,
+              check=True, ninputs=None, nbeams=None):
+        """Power mode, one launch.  Row j * B + b of d_out (row_stride floats apart) is S_b[j]."""
+        m = 1 << self.log2_channels
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = pfbbf_lib().rtlws_pfbbf_power(self.h, self._array(d_iqs), int(self.ninputs if ninputs is None else ninputs),
+                                           ptr(d_weights), int(self.nbeams if nbeams is None else nbeams), int(nspectra),
+                                           int(m if hop is None else hop), int(k_avg), int(shifted), ptr(d_out),
+                                           int(m if row_stride is None else row_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_pfbbf_power failed (rc=%d): %s" % (rc, pfbbf_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            pfbbf_lib().rtlws_pfbbf_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -1273,6 +1401,69 @@ class Engine:
             d_auto.free()
             d_cross.free()
         return autos, cross
+
+    # -- include/rtlws_pfbbf.h: host arrays in, the beams out ----
+    def _pfbbf_inputs(self, iqs, weights, log2_channels, taps):
+        """-> (plan, captures, device buffers by id, the weights' buffer); one array given twice is uploaded once"""
+        same = {id(x): np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 2) for x in iqs}
+        iqs = [same[id(x)] for x in iqs]
+        m = 1 << int(log2_channels)
+        weights = np.ascontiguousarray(weights, dtype=np.complex64)
+        assert weights.ndim == 3 and weights.shape[1:] == (len(iqs), m), "the weights are [B, A, M]"
+        plan = PfbBfPlan(self, log2_channels, taps, len(iqs), weights.shape[0])
+        bufs = {}
+        for x in iqs:
+            if id(x) not in bufs:
+                bufs[id(x)] = self.upload(x) if x.nbytes else self.alloc(16)
+        return plan, iqs, bufs, self.upload(weights)
+
+    def pfbbf(self, iqs, weights, log2_channels, taps, hop=None, first_frame_index=0, layout="channel", nframes=None):
+        """rtlws_pfbbf_run: iqs a sequence of A = 1 .. 8 captures, each uint8 [(nframes - 1) * hop + T * M, 2], weights
+        complex64 [B, A, M], taps int16 [T * M] -> complex64 [B, M, nframes] (layout "channel") or [B, nframes, M]
+        ("time").  nframes None: as many as the shortest capture holds."""
+        plan, iqs, bufs, d_w = self._pfbbf_inputs(iqs, weights, log2_channels, taps)
+        m, t, nb = 1 << plan.log2_channels, plan.taps_per_branch, plan.nbeams
+        hop = m if hop is None else int(hop)
+        shortest = min(x.shape[0] for x in iqs)
+        if nframes is None:
+            nframes = (shortest - t * m) // hop + 1 if shortest >= t * m and hop > 0 else 0
+        need = pfbbf_samples_needed(plan.log2_channels, t, hop, 0, nframes)
+        assert need < 0 or shortest >= need, "a capture is shorter than rtlws_pfbbf_samples_needed"
+        d_out = self.alloc(max(nb * m * nframes, 1) * 8)
+        shape = (nb, nframes, m) if _PFB_LAYOUTS.get(layout, layout) == PFB_TIME_MAJOR else (nb, m, nframes)
+        try:
+            plan.run([bufs[id(x)] for x in iqs], d_w, nframes, d_out, hop, None, None, first_frame_index, layout)
+            self.sync()
+            out = self.download(d_out, np.complex64, shape) if nframes else np.zeros(shape, np.complex64)
+        finally:
+            plan.close()
+            for b in list(bufs.values()) + [d_w, d_out]:
+                b.free()
+        return out
+
+    def pfbbf_power(self, iqs, weights, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
+        """rtlws_pfbbf_power: the captures and weights of pfbbf, each capture uint8 [(nspectra * k_avg - 1) * hop +
+        T * M, 2] -> float32 [nspectra, B, M], the K-frame powers of the beams.  nspectra None: as many as the shortest
+        capture holds."""
+        plan, iqs, bufs, d_w = self._pfbbf_inputs(iqs, weights, log2_channels, taps)
+        m, t, nb, k_avg = 1 << plan.log2_channels, plan.taps_per_branch, plan.nbeams, int(k_avg)
+        hop = m if hop is None else int(hop)
+        shortest = min(x.shape[0] for x in iqs)
+        if nspectra is None:
+            nframes = (shortest - t * m) // hop + 1 if shortest >= t * m and hop > 0 else 0
+            nspectra = nframes // k_avg if k_avg > 0 else 0
+        need = pfbbf_samples_needed(plan.log2_channels, t, hop, k_avg, nspectra) if k_avg > 0 else -1
+        assert need < 0 or shortest >= need, "a capture is shorter than rtlws_pfbbf_samples_needed"
+        d_out = self.alloc(max(nspectra * nb * m, 1) * 4)
+        try:
+            plan.power([bufs[id(x)] for x in iqs], d_w, nspectra, k_avg, d_out, hop, shifted)
+            self.sync()
+            out = self.download(d_out, np.float32, (nspectra, nb, m)) if nspectra else np.zeros((0, nb, m), np.float32)
+        finally:
+            plan.close()
+            for b in list(bufs.values()) + [d_w, d_out]:
+                b.free()
+        return out
 
     # -- include/rtlws_fmbank.h: host arrays in, (audio, new states) out ----
     def fm_bank(self, iq, cic_r, tuning_words, block_len, states, first_dec_index=0):
