@@ -10,11 +10,10 @@
 #include <vector>
 
 #include "rtlws_anylen.h"
+#include "shim_common.h"
 #include "spectrum_anylen.h"
 
 namespace {
-
-thread_local std::string g_err;
 
 void set_err(const char* what, hipError_t e)
 {
@@ -260,9 +259,7 @@ int rtlws_anylen_run(rtlws_anylen_plan* plan, const void* d_in, long nframes, vo
         set_err("rtlws_anylen_run: hipSetDevice", err);
         return -3;
     }
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(plan->eng));
+    hipStream_t st = stream_of(plan->eng, stream);
 
     AnyParams p = params_of(plan);
     const size_t N = (size_t)d.n_fft;

@@ -6,13 +6,12 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 #include <vector>
 
 #include "ddc_bank.h"
 #include "ddc_table.h"
 #include "rtlws_ddc.h"
+#include "shim_common.h"
 
 struct rtlws_ddc_plan {
     rtlws_engine* engine;
@@ -25,22 +24,6 @@ namespace {
 using namespace rtlws::ddc;
 
 static_assert(LOG2_P == RTLWS_DDC_LOG2_PERIOD && MAX_CH == RTLWS_DDC_MAX_CHANNELS, "rtlws_ddc.h and ddc_bank.h disagree");
-
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
 
 long tiles_of(long dec_len) { return (dec_len + TILE_DEC - 1) / TILE_DEC; }
 
@@ -160,9 +143,7 @@ int rtlws_ddc_run(rtlws_ddc_plan* p, int cic_r, const void* d_iq_cu8, long dec_l
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
+    hipStream_t st = stream_of(p->engine, stream);
     bp.src = d_iq_cu8;
     bp.out = d_out_cs32;
     bp.table = p->d_table;

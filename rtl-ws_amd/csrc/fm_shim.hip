@@ -5,29 +5,12 @@
 
 #include <climits>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "fm_chain.h"
 #include "rtlws_fm.h"
+#include "shim_common.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
 
 long tiles_of(int block_len, long nblocks)
 {
@@ -65,9 +48,7 @@ int run(const char* fn, rtlws_engine* e, int cic_r, bool cu8, const void* d_src,
 
     hipError_t err = hipSetDevice(rtlws_engine_device(e));
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(e));
+    hipStream_t st = stream_of(e, stream);
     if (nblocks == 0) {
         err = launch_state_copy(d_state_in, d_state_out, st);
     } else {

@@ -5,8 +5,6 @@
 
 #include <climits>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 #include <vector>
 
 #include "ddc_table.h"
@@ -14,6 +12,7 @@
 #include "rtlws_ddc.h"
 #include "rtlws_fm.h"
 #include "rtlws_fmbank.h"
+#include "shim_common.h"
 
 struct rtlws_fmbank_plan {
     rtlws_engine* engine;
@@ -29,22 +28,6 @@ constexpr int P = rtlws::ddc::P;
 static_assert(MAX_CH == RTLWS_FMBANK_MAX_CHANNELS && MAX_CH == RTLWS_DDC_MAX_CHANNELS && STATE == RTLWS_FM_STATE_FLOATS &&
                   rtlws::ddc::LOG2_P == RTLWS_DDC_LOG2_PERIOD,
               "rtlws_fmbank.h, rtlws_ddc.h, rtlws_fm.h and fm_bank.h disagree");
-
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
 
 long tiles_of(int block_len, long nblocks)
 {
@@ -155,9 +138,7 @@ int rtlws_fmbank_run(rtlws_fmbank_plan* p, int cic_r, const void* d_iq_cu8, int 
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
+    hipStream_t st = stream_of(p->engine, stream);
     if (nblocks == 0) {
         err = launch_state_copy(d_state_in, d_state_out, nchannels * STATE, st);
     } else {

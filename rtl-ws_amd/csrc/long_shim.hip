@@ -10,11 +10,10 @@
 #include <vector>
 
 #include "rtlws_long.h"
+#include "shim_common.h"
 #include "spectrum_long.h"
 
 namespace {
-
-thread_local std::string g_err;
 
 void set_err(const char* what, hipError_t e)
 {
@@ -181,9 +180,7 @@ int rtlws_long_run(rtlws_long_plan* plan, const void* d_in, long nframes, void* 
         set_err("rtlws_long_run: hipSetDevice", err);
         return -3;
     }
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(plan->eng));
+    hipStream_t st = stream_of(plan->eng, stream);
 
     LongParams p;
     std::memset(&p, 0, sizeof p);

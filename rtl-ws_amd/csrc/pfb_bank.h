@@ -1,4 +1,5 @@
-// pfb_bank.h -- shared between pfb_bank.hip (the kernels) and pfb_shim.hip (rtlws_pfb.h's host glue).
+// pfb_bank.h -- shared between pfb_bank.hip (the kernels) and pfb_shim.hip (rtlws_pfb.h's host glue), and the geometry
+// of the whole polyphase family (pfbspec, pfbxc, pfbbf): the tile, and how K-frame sums are laid over it.
 #ifndef RTLWS_PFB_BANK_H
 #define RTLWS_PFB_BANK_H
 
@@ -22,6 +23,16 @@ constexpr int tile_frames(int k) { return TILE_POINTS >> k; }
 constexpr int row_pad(int k) { return (1 << k) / 16; }
 constexpr int row_stride(int k) { return (1 << k) + row_pad(k); }
 constexpr int lds_bytes(int k) { return tile_frames(k) * row_stride(k) * 8; }
+
+// The geometry of a launch that sums K = k_avg frames per spectrum (the spectrometer, the correlator, the beamformer's
+// power mode), a function of (log2 M, K) alone.  With F = tile_frames(k), a workgroup owns
+//   K >= F: one spectrum, ceil(K / F) tile iterations (the last one ragged);
+//   K <  F: floor(F / K) spectra in one tile.
+// A spectrum's K frames r = 0 .. K - 1 are summed in slices of SLICE = min(16, F) consecutive frames; slice s of a
+// tile iteration holds the frames it * F + s * SLICE + (0 .. SLICE - 1).  The order of the sums is pfbspec.hip's.
+constexpr int MAX_K_AVG = 65536;
+constexpr int slice_frames(int k) { return tile_frames(k) < 16 ? tile_frames(k) : 16; }
+constexpr int spectra_per_block(int k, int k_avg) { return k_avg >= tile_frames(k) ? 1 : tile_frames(k) / k_avg; }
 
 struct PfbParams {
     const void* src;          // cmplx_u8, (nframes - 1) * hop + taps * M samples

@@ -68,48 +68,22 @@ __global__ __launch_bounds__(THREADS) void pfb_kernel(const PfbParams p)
     }
 }
 
-template <int K>
-static hipError_t launch_k(const PfbParams& p, hipStream_t st)
+// the launch table: f is handed the plan's instantiation
+template <typename F>
+static hipError_t with_kernel(int k, F&& f)
 {
-    const long blocks = (p.nframes + tile_frames(K) - 1) / tile_frames(K);
-    hipLaunchKernelGGL((pfb_kernel<K>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
-}
-
-template <int K>
-static hipError_t prepare_k()
-{
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&pfb_kernel<K>));
+    return pick(Log2Ms{}, k, [&](auto kk) { return f(&pfb_kernel<kk>); });
 }
 
 hipError_t launch_pfb(int k, const PfbParams& p, hipStream_t st)
 {
-    switch (k) {
-    case 4: return launch_k<4>(p, st);
-    case 5: return launch_k<5>(p, st);
-    case 6: return launch_k<6>(p, st);
-    case 7: return launch_k<7>(p, st);
-    case 8: return launch_k<8>(p, st);
-    case 9: return launch_k<9>(p, st);
-    case 10: return launch_k<10>(p, st);
-    default: return hipErrorInvalidValue;
-    }
+    const long blocks = (p.nframes + tile_frames(k) - 1) / tile_frames(k);
+    return with_kernel(k, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call
 hipError_t prepare_pfb(int k)
 {
-    switch (k) {
-    case 4: return prepare_k<4>();
-    case 5: return prepare_k<5>();
-    case 6: return prepare_k<6>();
-    case 7: return prepare_k<7>();
-    case 8: return prepare_k<8>();
-    case 9: return prepare_k<9>();
-    case 10: return prepare_k<10>();
-    default: return hipErrorInvalidValue;
-    }
+    return with_kernel(k, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace pfb

@@ -3,23 +3,13 @@
 // the environment, and nothing of a run is computed on the host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
-#include "pfb_bank.h"
 #include "pfb_plan.h"
 #include "rtlws_pfb.h"
 
-struct rtlws_pfb_plan {
-    rtlws_engine* engine;
-    int device;
-    int log2_m, taps_per_branch;
-    int16_t* d_taps;
-    float2* d_tw;
-};
+struct rtlws_pfb_plan : rtlws::pfb::Plan {};
 
 namespace {
 
@@ -29,31 +19,13 @@ static_assert(MIN_LOG2_M == RTLWS_PFB_MIN_LOG2_CHANNELS && MAX_LOG2_M == RTLWS_P
                   MAX_TAPS == RTLWS_PFB_MAX_TAPS && LAYOUT_CHANNEL == RTLWS_PFB_CHANNEL_MAJOR && LAYOUT_TIME == RTLWS_PFB_TIME_MAJOR,
               "rtlws_pfb.h and pfb_bank.h disagree");
 
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
-
 // why a shape is not served, or nullptr; hop == 0: not asked
 const char* why_not(int k, int taps, int hop, long nframes)
 {
-    if (k < MIN_LOG2_M || k > MAX_LOG2_M) return "log2_channels must be 4 .. 10";
-    if (taps < 1 || taps > MAX_TAPS) return "taps_per_branch must be 1 .. 32";
-    if (hop != 0 && hop != 1 << k && hop != 1 << (k - 1)) return "hop must be M or M / 2";
-    if (nframes < 0) return "nframes must be >= 0";
-    if (nframes > (long)INT_MAX * tile_frames(k)) return "more frames than one grid holds";
-    return nullptr;
+    if (const char* why = why_not_bank(k, taps)) return why;
+    if (hop != 0)
+        if (const char* why = why_not_hop(k, hop)) return why;
+    return why_not_count(nframes, tile_frames(k), false);
 }
 
 }  // namespace
@@ -119,46 +91,12 @@ int rtlws_pfb_grid(int log2_channels, int taps_per_branch, int hop, long nframes
 
 rtlws_pfb_plan* rtlws_pfb_open(rtlws_engine* e, int log2_channels, int taps_per_branch, const int16_t* taps)
 {
-    const char* fn = "rtlws_pfb_open";
     g_err.clear();
-    if (const char* why = why_not(log2_channels, taps_per_branch, 0, 0)) {
-        fail(fn, why, -1);
-        return nullptr;
-    }
-    if (!taps) {
-        fail(fn, "null taps", -1);
-        return nullptr;
-    }
-    if (!e) {
-        fail(fn, "null engine (no usable HIP device: there is no CPU path)", -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "hipSetDevice", err);
-        return nullptr;
-    }
-    int16_t* d_taps = nullptr;
-    float2* d_tw = nullptr;
-    err = upload_plan_arrays(log2_channels, taps_per_branch, taps, &d_taps, &d_tw);
-    if (err == hipSuccess) {
-        err = prepare_pfb(log2_channels);
-        if (err != hipSuccess) free_plan_arrays(d_taps, d_tw);
-    }
-    if (err != hipSuccess) {
-        fail_hip(fn, "the taps, the table or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_pfb_plan{e, device, log2_channels, taps_per_branch, d_taps, d_tw};
+    return open_plan<rtlws_pfb_plan>("rtlws_pfb_open", why_not(log2_channels, taps_per_branch, 0, 0), e, log2_channels,
+                                     taps_per_branch, taps, prepare_pfb);
 }
 
-void rtlws_pfb_close(rtlws_pfb_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) free_plan_arrays(p->d_taps, p->d_tw);
-    delete p;
-}
+void rtlws_pfb_close(rtlws_pfb_plan* p) { close_plan(p); }
 
 int rtlws_pfb_run(rtlws_pfb_plan* p, const void* d_iq_cu8, long nframes, int hop, long first_frame_index, int layout,
                   void* d_out_cf32, long out_stride, void* stream)
@@ -166,9 +104,8 @@ int rtlws_pfb_run(rtlws_pfb_plan* p, const void* d_iq_cu8, long nframes, int hop
     const char* fn = "rtlws_pfb_run";
     g_err.clear();
     // what needs no plan: the hop is a power of two 8 .. 1024, a frame holds at least 16 values
-    if (hop < 8 || hop > 1 << MAX_LOG2_M || (hop & (hop - 1))) return fail(fn, "hop must be M or M / 2", -1);
-    if (nframes < 0) return fail(fn, "nframes must be >= 0", -1);
-    if (nframes > (long)INT_MAX * tile_frames(MIN_LOG2_M)) return fail(fn, "more frames than one grid holds", -1);
+    if (const char* why = why_not_any_hop(hop)) return fail(fn, why, -1);
+    if (const char* why = why_not_count(nframes, tile_frames(MIN_LOG2_M), false)) return fail(fn, why, -1);
     if (first_frame_index < 0) return fail(fn, "first_frame_index must be >= 0", -1);
     if (layout != LAYOUT_CHANNEL && layout != LAYOUT_TIME) return fail(fn, "unknown layout", -1);
     if (out_stride < (layout == LAYOUT_CHANNEL ? nframes : 1L << MIN_LOG2_M)) return fail(fn, "out_stride too small for the layout", -1);
@@ -183,21 +120,13 @@ int rtlws_pfb_run(rtlws_pfb_plan* p, const void* d_iq_cu8, long nframes, int hop
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
-    PfbParams pp;
+    PfbParams pp = bank_params(*p, hop, nframes);
     pp.src = d_iq_cu8;
     pp.out = static_cast<float2*>(d_out_cf32);
-    pp.taps = p->d_taps;
-    pp.tw = p->d_tw;
-    pp.nframes = nframes;
     pp.first = first_frame_index;
     pp.out_stride = out_stride;
-    pp.taps_per_branch = p->taps_per_branch;
-    pp.half_hop = hop != 1 << p->log2_m;
     pp.layout = layout;
-    err = launch_pfb(p->log2_m, pp, st);
+    err = launch_pfb(p->log2_m, pp, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }

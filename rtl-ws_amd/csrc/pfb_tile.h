@@ -1,6 +1,7 @@
 // pfb_tile.h -- passes 1-4 of the polyphase filter bank's tile: the integer branch filters, the
 // radix-16 passes and the radix-R pass with its reordering.  The one text of pfb_bank.hip (librtlws_pfb.so: pass 5
-// stores the tile) and pfbspec.hip (librtlws_pfbspec.so: the epilogue squares and sums it).
+// stores the tile), pfbspec.hip, pfbxc.hip and pfbbf.hip (their epilogues square, multiply and sum it through
+// pfb_ksum.h); and the head of every launch table of the family.
 #ifndef RTLWS_PFB_TILE_H
 #define RTLWS_PFB_TILE_H
 
@@ -9,6 +10,7 @@
 
 #include "fft_regs.h"
 #include "pfb_bank.h"
+#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace pfb {
@@ -183,6 +185,20 @@ __device__ __forceinline__ void tile_passes(const PfbParams& p, long m0, int tid
         }
     }
     __syncthreads();
+}
+
+// The launch tables' first choice (rtlws_internal.h): log2 M, a template parameter of every kernel of the family
+using Log2Ms = Vals<4, 5, 6, 7, 8, 9, 10>;
+static_assert(MIN_LOG2_M == 4 && MAX_LOG2_M == 10, "pfb_bank.h and the launch tables disagree");
+
+// A plan's prepare step: hipFuncGetAttributes loads the code object of the current device, so that a launch makes no
+// other call.  The tiles are static LDS, which a launch takes up to the 160 KiB of a compute unit as it is: the
+// opt-in of lds_opt_in (rtlws_internal.h) is for dynamic LDS and has nothing to raise here
+template <typename P>
+hipError_t load_kernel(void (*kernel)(P))
+{
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
 }
 
 }  // namespace pfb

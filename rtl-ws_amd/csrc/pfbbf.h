@@ -10,17 +10,12 @@
 namespace rtlws {
 namespace pfbbf {
 
-constexpr int MAX_K_AVG = 65536;
 constexpr int MIN_INPUTS = 1, MAX_INPUTS = 8;
 constexpr int MIN_BEAMS = 1, MAX_BEAMS = 4;
 
-// Voltage mode has the channelizer's geometry (pfb_bank.h): a workgroup owns pfb::tile_frames(k)
-// frames.  Power mode has the spectrometer's (pfbspec.h), a function of (log2 M, K) alone: with
-// F = pfb::tile_frames(k), a workgroup owns one spectrum over ceil(K / F) tile iterations where K >= F, else
-// floor(F / K) spectra in one tile; a spectrum's frames are summed in slices of SLICE = min(16, F).
-// One tile serves every number of inputs and beams: the beams' running values stay in registers.
-constexpr int slice_frames(int k) { return pfb::tile_frames(k) < 16 ? pfb::tile_frames(k) : 16; }
-constexpr int spectra_per_block(int k, int k_avg) { return k_avg >= pfb::tile_frames(k) ? 1 : pfb::tile_frames(k) / k_avg; }
+// Voltage mode has the channelizer's geometry (pfb::tile_frames frames per workgroup), power mode the one of the
+// K-frame sums (pfb::slice_frames, pfb::spectra_per_block): both pfb_bank.h's.  One tile serves every number of inputs
+// and beams: the beams' running values stay in registers.
 constexpr int lds_bytes(int k) { return pfb::lds_bytes(k); }
 
 struct BfParams {

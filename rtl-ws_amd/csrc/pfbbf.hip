@@ -28,9 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pfb_tile.h"
+#include "pfb_ksum.h"
 #include "pfbbf.h"
-#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace pfbbf {
@@ -39,18 +38,8 @@ using namespace rtlws::pfb;
 
 constexpr int PER = TILE_POINTS / THREADS;            // items of the tile per thread
 
-// The products pass through an empty asm, so that no sum or difference can take one of them into a fused
-// multiply-add (the file is compiled with contraction on, as the filter bank's transform needs).
-// fl(fl(re re) + fl(im im)): pfbspec.hip's power(), the same three roundings
-__device__ __forceinline__ float power(float2 y)
-{
-    float a = y.x * y.x, b = y.y * y.y;
-    asm("" : "+v"(a));
-    asm("" : "+v"(b));
-    return a + b;
-}
-
-// w y
+// w y.  The products pass through an empty asm, as in power() (pfb_ksum.h), so that no sum or difference can take
+// one of them into a fused multiply-add
 __device__ __forceinline__ float2 weighted(float2 w, float2 y)
 {
     float rr = w.x * y.x, ii = w.y * y.y, ri = w.x * y.y, ir = w.y * y.x;
@@ -102,14 +91,10 @@ __device__ __forceinline__ void beams_of_tile(const BfParams& p, PfbParams& bank
 #pragma unroll
         for (int i = 0; i < PER; ++i) z[b][i] = make_float2(0.0f, 0.0f);
     const int A = p.ninputs;
-    // The thread index and the arrays' addresses are made opaque before every call, as in pfbspec.hip: what the
-    // passes derive from them is formed there and not held in registers across the loop
 #pragma unroll 1
     for (int a = 0; a < A; ++a) {
-        int t = tid;
         bank.src = p.src[a];
-        asm volatile("" : "+v"(t), "+s"(bank.src), "+s"(bank.taps), "+s"(bank.tw));
-        tile_passes<K>(bank, m0, t, tile);
+        int t = tile_passes_afresh<K>(bank, m0, tid, tile);
         asm volatile("" : "+v"(t));                                      // nor the accumulate step's places and addresses
         add_capture<K, B>(tile, p.w + (long)a * M, A * M, t, z);
         __syncthreads();                                                 // before the tile is refilled
@@ -280,73 +265,48 @@ __global__ __launch_bounds__(THREADS) void pfbbf_power_kernel(const BfParams p)
     }
 }
 
-template <int K, int B>
-static hipError_t launch_kb(const BfParams& p, hipStream_t st)
+// the launch tables: f is handed the plan's instantiation.  The host chooses WHOLE
+using Beams = Vals<1, 2, 3, 4>;
+static_assert(MIN_BEAMS == 1 && MAX_BEAMS == 4, "pfbbf.h and the launch tables disagree");
+
+template <typename F>
+static hipError_t with_kernel(int k, int nbeams, F&& f)
 {
-    const long blocks = (p.bank.nframes + tile_frames(K) - 1) / tile_frames(K);
-    hipLaunchKernelGGL((pfbbf_kernel<K, B>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
+    return pick(Log2Ms{}, k, [&](auto kk) { return pick(Beams{}, nbeams, [&](auto b) { return f(&pfbbf_kernel<kk, b>); }); });
 }
 
-template <int K, int B>
-static hipError_t launch_power_kb(const BfParams& p, hipStream_t st)
+template <typename F>
+static hipError_t with_power_kernel(int k, int nbeams, bool whole, F&& f)
 {
-    const int g = spectra_per_block(K, p.k_avg);
+    return pick(Log2Ms{}, k, [&](auto kk) {
+        return pick(Beams{}, nbeams, [&](auto b) {
+            return pick(Bools{}, whole, [&](auto w) { return f(&pfbbf_power_kernel<kk, b, w>); });
+        });
+    });
+}
+
+hipError_t launch_pfbbf(int k, int nbeams, const BfParams& p, hipStream_t st)
+{
+    const long blocks = (p.bank.nframes + tile_frames(k) - 1) / tile_frames(k);
+    return with_kernel(k, nbeams, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
+}
+
+hipError_t launch_pfbbf_power(int k, int nbeams, const BfParams& p, hipStream_t st)
+{
+    const int g = spectra_per_block(k, p.k_avg);
     const long blocks = (p.nspectra + g - 1) / g;
-    if (p.k_avg >= tile_frames(K)) hipLaunchKernelGGL((pfbbf_power_kernel<K, B, true>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    else hipLaunchKernelGGL((pfbbf_power_kernel<K, B, false>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
+    return with_power_kernel(k, nbeams, p.k_avg >= tile_frames(k),
+                             [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  The tile is
-// static LDS, which a launch takes as it is
-template <int K, int B>
-static hipError_t prepare_kb()
+hipError_t prepare_pfbbf(int k, int nbeams)
 {
-    hipFuncAttributes a;
-    hipError_t err = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&pfbbf_kernel<K, B>));
-    if (err == hipSuccess) err = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&pfbbf_power_kernel<K, B, true>));
-    if (err == hipSuccess) err = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&pfbbf_power_kernel<K, B, false>));
+    const auto load = [](auto kernel) { return load_kernel(kernel); };
+    hipError_t err = with_kernel(k, nbeams, load);
+    if (err == hipSuccess) err = with_power_kernel(k, nbeams, true, load);
+    if (err == hipSuccess) err = with_power_kernel(k, nbeams, false, load);
     return err;
 }
-
-enum { VOLTAGE, POWER, PREPARE };
-
-template <int K, int B>
-static hipError_t call_kb(int what, const BfParams* p, hipStream_t st)
-{
-    return what == VOLTAGE ? launch_kb<K, B>(*p, st) : what == POWER ? launch_power_kb<K, B>(*p, st) : prepare_kb<K, B>();
-}
-
-template <int K>
-static hipError_t call_k(int nbeams, int what, const BfParams* p, hipStream_t st)
-{
-    switch (nbeams) {
-    case 1: return call_kb<K, 1>(what, p, st);
-    case 2: return call_kb<K, 2>(what, p, st);
-    case 3: return call_kb<K, 3>(what, p, st);
-    case 4: return call_kb<K, 4>(what, p, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-static hipError_t call(int k, int nbeams, int what, const BfParams* p, hipStream_t st)
-{
-    switch (k) {
-    case 4: return call_k<4>(nbeams, what, p, st);
-    case 5: return call_k<5>(nbeams, what, p, st);
-    case 6: return call_k<6>(nbeams, what, p, st);
-    case 7: return call_k<7>(nbeams, what, p, st);
-    case 8: return call_k<8>(nbeams, what, p, st);
-    case 9: return call_k<9>(nbeams, what, p, st);
-    case 10: return call_k<10>(nbeams, what, p, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-hipError_t launch_pfbbf(int k, int nbeams, const BfParams& p, hipStream_t st) { return call(k, nbeams, VOLTAGE, &p, st); }
-hipError_t launch_pfbbf_power(int k, int nbeams, const BfParams& p, hipStream_t st) { return call(k, nbeams, POWER, &p, st); }
-hipError_t prepare_pfbbf(int k, int nbeams) { return call(k, nbeams, PREPARE, nullptr, nullptr); }
 
 }  // namespace pfbbf
 }  // namespace rtlws

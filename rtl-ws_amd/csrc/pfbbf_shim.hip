@@ -4,56 +4,27 @@
 // device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "pfb_plan.h"
 #include "pfbbf.h"
 #include "rtlws_pfb.h"
 #include "rtlws_pfbbf.h"
 
-struct rtlws_pfbbf_plan {
-    rtlws_engine* engine;
-    int device;
-    int log2_m, taps_per_branch, ninputs, nbeams;
-    int16_t* d_taps;
-    float2* d_tw;
+struct rtlws_pfbbf_plan : rtlws::pfb::Plan {
+    int ninputs, nbeams;
 };
 
 namespace {
 
+using namespace rtlws::pfb;
 using namespace rtlws::pfbbf;
-using rtlws::pfb::LAYOUT_CHANNEL;
-using rtlws::pfb::LAYOUT_TIME;
-using rtlws::pfb::MAX_LOG2_M;
-using rtlws::pfb::MAX_TAPS;
-using rtlws::pfb::MIN_LOG2_M;
-using rtlws::pfb::THREADS;
-using rtlws::pfb::tile_frames;
 
 static_assert(MIN_LOG2_M == RTLWS_PFB_MIN_LOG2_CHANNELS && MAX_LOG2_M == RTLWS_PFB_MAX_LOG2_CHANNELS &&
                   MAX_TAPS == RTLWS_PFB_MAX_TAPS && LAYOUT_CHANNEL == RTLWS_PFB_CHANNEL_MAJOR && LAYOUT_TIME == RTLWS_PFB_TIME_MAJOR &&
                   MAX_K_AVG == RTLWS_PFBBF_MAX_K_AVG && MIN_INPUTS == RTLWS_PFBBF_MIN_INPUTS && MAX_INPUTS == RTLWS_PFBBF_MAX_INPUTS &&
                   MIN_BEAMS == RTLWS_PFBBF_MIN_BEAMS && MAX_BEAMS == RTLWS_PFBBF_MAX_BEAMS,
               "rtlws_pfbbf.h, rtlws_pfb.h and pfbbf.h disagree");
-
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
 
 const char* why_not_counts(int ninputs, int nbeams)
 {
@@ -65,8 +36,7 @@ const char* why_not_counts(int ninputs, int nbeams)
 // why a plan's shape is not served, or nullptr
 const char* why_not_plan(int k, int taps, int ninputs, int nbeams)
 {
-    if (k < MIN_LOG2_M || k > MAX_LOG2_M) return "log2_channels must be 4 .. 10";
-    if (taps < 1 || taps > MAX_TAPS) return "taps_per_branch must be 1 .. 32";
+    if (const char* why = why_not_bank(k, taps)) return why;
     return why_not_counts(ninputs, nbeams);
 }
 
@@ -74,16 +44,9 @@ const char* why_not_plan(int k, int taps, int ninputs, int nbeams)
 const char* why_not(int k, int taps, int hop, int k_avg, int ninputs, int nbeams, long count)
 {
     if (const char* why = why_not_plan(k, taps, ninputs, nbeams)) return why;
-    if (hop != 1 << k && hop != 1 << (k - 1)) return "hop must be M or M / 2";
+    if (const char* why = why_not_hop(k, hop)) return why;
     if (k_avg < 0 || k_avg > MAX_K_AVG) return "k_avg must be 1 .. 65536 (0: voltage mode)";
-    if (k_avg == 0) {
-        if (count < 0) return "nframes must be >= 0";
-        if (count > (long)INT_MAX * tile_frames(k)) return "more frames than one grid holds";
-    } else {
-        if (count < 0) return "nspectra must be >= 0";
-        if (count > (long)INT_MAX * spectra_per_block(k, k_avg)) return "more spectra than one grid holds";
-    }
-    return nullptr;
+    return k_avg == 0 ? why_not_count(count, tile_frames(k), false) : why_not_count(count, spectra_per_block(k, k_avg), true);
 }
 
 // the extent of one beam's voltages in complex values; nframes > 0
@@ -93,36 +56,10 @@ __int128 beam_extent(int layout, long nframes, long out_stride, int log2_m)
     return layout == LAYOUT_TIME ? (__int128)(nframes - 1) * out_stride + M : (__int128)(M - 1) * out_stride + nframes;
 }
 
-hipStream_t stream_of(const rtlws_pfbbf_plan* p, void* stream)
-{
-    return stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-           : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                          : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
-}
-
-// the captures' pointers, the last of the refusals
-const char* why_not_captures(const rtlws_pfbbf_plan* p, const void* const* d_iq_cu8)
-{
-    for (int a = 0; a < p->ninputs; ++a) {
-        if (!d_iq_cu8[a]) return "null pointer among the captures";
-        if (reinterpret_cast<uintptr_t>(d_iq_cu8[a]) & 15u) return "every capture must be 16-byte aligned";
-    }
-    return nullptr;
-}
-
 BfParams params_of(const rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, const float* d_weights, int hop, long nframes)
 {
     BfParams bp;
-    bp.bank.src = nullptr;
-    bp.bank.out = nullptr;
-    bp.bank.taps = p->d_taps;
-    bp.bank.tw = p->d_tw;
-    bp.bank.nframes = nframes;
-    bp.bank.first = 0;
-    bp.bank.out_stride = 0;
-    bp.bank.taps_per_branch = p->taps_per_branch;
-    bp.bank.half_hop = hop != 1 << p->log2_m;
-    bp.bank.layout = 0;
+    bp.bank = bank_params(*p, hop, nframes);
     for (int a = 0; a < MAX_INPUTS; ++a) bp.src[a] = a < p->ninputs ? d_iq_cu8[a] : nullptr;
     bp.w = reinterpret_cast<const float2*>(d_weights);
     bp.rows = nullptr;
@@ -176,46 +113,18 @@ int rtlws_pfbbf_grid(int log2_channels, int taps_per_branch, int hop, int k_avg,
 rtlws_pfbbf_plan* rtlws_pfbbf_open(rtlws_engine* e, int log2_channels, int taps_per_branch, const int16_t* taps, int ninputs,
                                    int nbeams)
 {
-    const char* fn = "rtlws_pfbbf_open";
     g_err.clear();
-    if (const char* why = why_not_plan(log2_channels, taps_per_branch, ninputs, nbeams)) {
-        fail(fn, why, -1);
-        return nullptr;
+    rtlws_pfbbf_plan* p = open_plan<rtlws_pfbbf_plan>(
+        "rtlws_pfbbf_open", why_not_plan(log2_channels, taps_per_branch, ninputs, nbeams), e, log2_channels, taps_per_branch, taps,
+        [nbeams](int k) { return prepare_pfbbf(k, nbeams); }, "the taps, the table or the kernels");
+    if (p) {
+        p->ninputs = ninputs;
+        p->nbeams = nbeams;
     }
-    if (!taps) {
-        fail(fn, "null taps", -1);
-        return nullptr;
-    }
-    if (!e) {
-        fail(fn, "null engine (no usable HIP device: there is no CPU path)", -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "hipSetDevice", err);
-        return nullptr;
-    }
-    int16_t* d_taps = nullptr;
-    float2* d_tw = nullptr;
-    err = rtlws::pfb::upload_plan_arrays(log2_channels, taps_per_branch, taps, &d_taps, &d_tw);
-    if (err == hipSuccess) {
-        err = prepare_pfbbf(log2_channels, nbeams);
-        if (err != hipSuccess) rtlws::pfb::free_plan_arrays(d_taps, d_tw);
-    }
-    if (err != hipSuccess) {
-        fail_hip(fn, "the taps, the table or the kernels", err);
-        return nullptr;
-    }
-    return new rtlws_pfbbf_plan{e, device, log2_channels, taps_per_branch, ninputs, nbeams, d_taps, d_tw};
+    return p;
 }
 
-void rtlws_pfbbf_close(rtlws_pfbbf_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) rtlws::pfb::free_plan_arrays(p->d_taps, p->d_tw);
-    delete p;
-}
+void rtlws_pfbbf_close(rtlws_pfbbf_plan* p) { close_plan(p); }
 
 int rtlws_pfbbf_run(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninputs, const float* d_weights, int nbeams,
                     long nframes, int hop, long first_frame_index, int layout, void* d_out_cf32, long out_stride,
@@ -224,10 +133,9 @@ int rtlws_pfbbf_run(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninput
     const char* fn = "rtlws_pfbbf_run";
     g_err.clear();
     // what needs no plan: the hop is a power of two 8 .. 1024, a frame holds at least 16 values
-    if (hop < 8 || hop > 1 << MAX_LOG2_M || (hop & (hop - 1))) return fail(fn, "hop must be M or M / 2", -1);
+    if (const char* why = why_not_any_hop(hop)) return fail(fn, why, -1);
     if (const char* why = why_not_counts(ninputs, nbeams)) return fail(fn, why, -1);
-    if (nframes < 0) return fail(fn, "nframes must be >= 0", -1);
-    if (nframes > (long)INT_MAX * tile_frames(MIN_LOG2_M)) return fail(fn, "more frames than one grid holds", -1);
+    if (const char* why = why_not_count(nframes, tile_frames(MIN_LOG2_M), false)) return fail(fn, why, -1);
     if (first_frame_index < 0) return fail(fn, "first_frame_index must be >= 0", -1);
     if (layout != LAYOUT_CHANNEL && layout != LAYOUT_TIME) return fail(fn, "unknown layout", -1);
     if (out_stride < (layout == LAYOUT_CHANNEL ? nframes : 1L << MIN_LOG2_M)) return fail(fn, "out_stride too small for the layout", -1);
@@ -244,7 +152,7 @@ int rtlws_pfbbf_run(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninput
     if (layout == LAYOUT_TIME && out_stride < 1L << p->log2_m) return fail(fn, "out_stride too small for the layout", -1);
     if (nframes == 0) return 0;
     if (beam_stride < beam_extent(layout, nframes, out_stride, p->log2_m)) return fail(fn, "beam_stride smaller than one beam's output", -1);
-    if (const char* why = why_not_captures(p, d_iq_cu8)) return fail(fn, why, -1);
+    if (const char* why = why_not_captures(d_iq_cu8, p->ninputs)) return fail(fn, why, -1);
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
@@ -254,7 +162,7 @@ int rtlws_pfbbf_run(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninput
     bp.bank.out_stride = out_stride;
     bp.bank.layout = layout;
     bp.beam_stride = beam_stride;
-    err = launch_pfbbf(p->log2_m, p->nbeams, bp, stream_of(p, stream));
+    err = launch_pfbbf(p->log2_m, p->nbeams, bp, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }
@@ -266,12 +174,11 @@ int rtlws_pfbbf_power(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninp
     g_err.clear();
     // what needs no plan: the hop is a power of two 8 .. 1024, a row holds at least 16 values, a workgroup at most
     // 256 / k_avg spectra
-    if (hop < 8 || hop > 1 << MAX_LOG2_M || (hop & (hop - 1))) return fail(fn, "hop must be M or M / 2", -1);
-    if (k_avg < 1 || k_avg > MAX_K_AVG) return fail(fn, "k_avg must be 1 .. 65536", -1);
+    if (const char* why = why_not_any_hop(hop)) return fail(fn, why, -1);
+    if (const char* why = why_not_k_avg(k_avg)) return fail(fn, why, -1);
     if (shifted != 0 && shifted != 1) return fail(fn, "shifted must be 0 or 1", -1);
     if (const char* why = why_not_counts(ninputs, nbeams)) return fail(fn, why, -1);
-    if (nspectra < 0) return fail(fn, "nspectra must be >= 0", -1);
-    if (nspectra > (long)INT_MAX * spectra_per_block(MIN_LOG2_M, k_avg)) return fail(fn, "more spectra than one grid holds", -1);
+    if (const char* why = why_not_count(nspectra, spectra_per_block(MIN_LOG2_M, k_avg), true)) return fail(fn, why, -1);
     if (row_stride < 1L << MIN_LOG2_M) return fail(fn, "row_stride must be >= M", -1);
     if (row_stride % 4) return fail(fn, "row_stride must be a multiple of 4", -1);
     if (nspectra > 0 && (!d_iq_cu8 || !d_weights || !d_out)) return fail(fn, "null pointer", -1);
@@ -284,7 +191,7 @@ int rtlws_pfbbf_power(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninp
     if (nbeams != p->nbeams) return fail(fn, "nbeams is not the plan's", -1);
     if (row_stride < 1L << p->log2_m) return fail(fn, "row_stride must be >= M", -1);
     if (nspectra == 0) return 0;
-    if (const char* why = why_not_captures(p, d_iq_cu8)) return fail(fn, why, -1);
+    if (const char* why = why_not_captures(d_iq_cu8, p->ninputs)) return fail(fn, why, -1);
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
@@ -294,7 +201,7 @@ int rtlws_pfbbf_power(rtlws_pfbbf_plan* p, const void* const* d_iq_cu8, int ninp
     bp.row_stride = row_stride;
     bp.k_avg = k_avg;
     bp.shift = shifted ? 1 << (p->log2_m - 1) : 0;
-    err = launch_pfbbf_power(p->log2_m, p->nbeams, bp, stream_of(p, stream));
+    err = launch_pfbbf_power(p->log2_m, p->nbeams, bp, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }

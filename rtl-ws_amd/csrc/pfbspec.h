@@ -10,17 +10,9 @@
 namespace rtlws {
 namespace pfbspec {
 
-constexpr int MAX_K_AVG = 65536;
 constexpr int OUT_SUM = 0, OUT_DB = 1, OUT_PAYLOAD = 2;   // RTLWS_OUT_POWER_SUM, RTLWS_OUT_MEAN_DB, RTLWS_OUT_PAYLOAD_U8
 
-// The geometry of a launch, a function of (log2 M, K) alone.  With F = pfb::tile_frames(k) frames
-// in the filter bank's tile, a workgroup owns
-//   K >= F: one spectrum, ceil(K / F) tile iterations (the last one ragged);
-//   K <  F: floor(F / K) spectra in one tile.
-// A spectrum's K frames r = 0 .. K - 1 are summed in slices of SLICE = min(16, F) consecutive frames; slice s of a
-// tile iteration holds the frames it * F + s * SLICE + (0 .. SLICE - 1).
-constexpr int slice_frames(int k) { return pfb::tile_frames(k) < 16 ? pfb::tile_frames(k) : 16; }
-constexpr int spectra_per_block(int k, int k_avg) { return k_avg >= pfb::tile_frames(k) ? 1 : pfb::tile_frames(k) / k_avg; }
+// The geometry of a launch is pfb_bank.h's (slice_frames, spectra_per_block), a function of (log2 M, K) alone.
 // the tile (pfb::lds_bytes) is reused for the partial sums and the finished rows: no LDS beyond it
 constexpr int lds_bytes(int k) { return pfb::lds_bytes(k); }
 

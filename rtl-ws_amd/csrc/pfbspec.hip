@@ -5,7 +5,7 @@
 //   P[m][c] = fl(fl(re re) + fl(im im))       Y[m][c] = re + i im: passes 1 .. 4 of the filter bank's tile (pfb_tile.h)
 //   S[j][c] = sum_{r < K} P[j K + r][c]       f32, in an order that (M, K) alone decide
 //
-// A workgroup of 256 threads owns whole spectra (pfbspec.h): one spectrum over ceil(K / F) tile iterations where
+// A workgroup of 256 threads owns whole spectra (pfb_bank.h): one spectrum over ceil(K / F) tile iterations where
 // K >= F = 4096 / M, else floor(F / K) spectra in one tile.  After pass 4 a row of the tile holds a frame's M bins in
 // natural order, and
 //   5 square   an item is (spectrum g of the workgroup, slice s, bin c), items tid, tid + 256, ..: consecutive lanes
@@ -14,15 +14,15 @@
 //   6 combine  the slices of a spectrum are added in the order s = 0, 1, .. through LDS (the tile, which is free by
 //              then), and the finished rows are laid out in LDS in the order of the output (shifted or not);
 //   7 store    rows as 16-byte vectors: four f32 sums or dB values, or sixteen payload bytes.
+// power() and the passes' call are pfb_ksum.h's; pfbxc.hip and pfbbf.hip restate steps 5 and 6 in this order.
 // So S[j][c] = ((A_0 + A_1) + ..) + A_(n-1) with A_s = ((P[s SLICE] + P[s SLICE + 1]) + ..), frames at or behind K
 // left out: the order does not know j, the place of a spectrum in its tile or in the grid, T, the hop or the output
 // kind (an empty slice would add +0 to a sum that is never negative, which changes no bit).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pfb_tile.h"
+#include "pfb_ksum.h"
 #include "pfbspec.h"
-#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace pfbspec {
@@ -31,16 +31,6 @@ using namespace rtlws::pfb;
 
 static_assert(OUT_SUM == rtlws::OUT_SUM && OUT_DB == rtlws::OUT_DB && OUT_PAYLOAD == rtlws::OUT_PAYLOAD,
               "pfbspec.h and rtlws_internal.h disagree");
-
-// fl(fl(re re) + fl(im im)): the products pass through an empty asm, so the sum cannot take one of them into a
-// fused multiply-add (the file is compiled with contraction on, as the filter bank's transform needs)
-__device__ __forceinline__ float power(float2 y)
-{
-    float a = y.x * y.x, b = y.y * y.y;
-    asm("" : "+v"(a));
-    asm("" : "+v"(b));
-    return a + b;
-}
 
 template <int K>
 __global__ __launch_bounds__(THREADS) void pfbspec_kernel(const SpecParams p)
@@ -70,13 +60,8 @@ __global__ __launch_bounds__(THREADS) void pfbspec_kernel(const SpecParams p)
 
     PfbParams bank = p.bank;
     for (int it = 0; it < nit; ++it) {
-        // 1 .. 4: the branch filters and the transform of every row (pfb_tile.h).  The thread index and the arrays'
-        // addresses are made opaque in every iteration: what the passes derive from them (some forty addresses and
-        // the first loads) is formed inside the loop, as in the channelizer's kernel, and not held in registers
-        // across it, which would cost the fourth workgroup per compute unit
-        int t = tid;
-        asm volatile("" : "+v"(t), "+s"(bank.src), "+s"(bank.taps), "+s"(bank.tw));
-        tile_passes<K>(bank, j0 * k_avg + (long)it * F, t, tile);
+        // 1 .. 4: the branch filters and the transform of every row (pfb_tile.h), their addresses formed afresh
+        tile_passes_afresh<K>(bank, j0 * k_avg + (long)it * F, tid, tile);
 
         // 5: the powers of a slice's frames, in frame order
         if (whole) {
@@ -173,49 +158,23 @@ __global__ __launch_bounds__(THREADS) void pfbspec_kernel(const SpecParams p)
     }
 }
 
-template <int K>
-static hipError_t launch_k(const SpecParams& p, hipStream_t st)
+// the launch table: f is handed the plan's instantiation
+template <typename F>
+static hipError_t with_kernel(int k, F&& f)
 {
-    const int g = spectra_per_block(K, p.k_avg);
-    const long blocks = (p.nspectra + g - 1) / g;
-    hipLaunchKernelGGL((pfbspec_kernel<K>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
-}
-
-template <int K>
-static hipError_t prepare_k()
-{
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&pfbspec_kernel<K>));
+    return pick(Log2Ms{}, k, [&](auto kk) { return f(&pfbspec_kernel<kk>); });
 }
 
 hipError_t launch_pfbspec(int k, const SpecParams& p, hipStream_t st)
 {
-    switch (k) {
-    case 4: return launch_k<4>(p, st);
-    case 5: return launch_k<5>(p, st);
-    case 6: return launch_k<6>(p, st);
-    case 7: return launch_k<7>(p, st);
-    case 8: return launch_k<8>(p, st);
-    case 9: return launch_k<9>(p, st);
-    case 10: return launch_k<10>(p, st);
-    default: return hipErrorInvalidValue;
-    }
+    const int g = spectra_per_block(k, p.k_avg);
+    const long blocks = (p.nspectra + g - 1) / g;
+    return with_kernel(k, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call
 hipError_t prepare_pfbspec(int k)
 {
-    switch (k) {
-    case 4: return prepare_k<4>();
-    case 5: return prepare_k<5>();
-    case 6: return prepare_k<6>();
-    case 7: return prepare_k<7>();
-    case 8: return prepare_k<8>();
-    case 9: return prepare_k<9>();
-    case 10: return prepare_k<10>();
-    default: return hipErrorInvalidValue;
-    }
+    return with_kernel(k, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace pfbspec

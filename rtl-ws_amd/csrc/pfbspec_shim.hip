@@ -4,71 +4,31 @@
 // device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "pfb_plan.h"
 #include "pfbspec.h"
 #include "rtlws_pfb.h"
 #include "rtlws_pfbspec.h"
 
-struct rtlws_pfbspec_plan {
-    rtlws_engine* engine;
-    int device;
-    int log2_m, taps_per_branch;
-    int16_t* d_taps;
-    float2* d_tw;
-};
+struct rtlws_pfbspec_plan : rtlws::pfb::Plan {};
 
 namespace {
 
+using namespace rtlws::pfb;
 using namespace rtlws::pfbspec;
-using rtlws::pfb::MAX_LOG2_M;
-using rtlws::pfb::MAX_TAPS;
-using rtlws::pfb::MIN_LOG2_M;
-using rtlws::pfb::THREADS;
 
 static_assert(MIN_LOG2_M == RTLWS_PFB_MIN_LOG2_CHANNELS && MAX_LOG2_M == RTLWS_PFB_MAX_LOG2_CHANNELS &&
                   MAX_TAPS == RTLWS_PFB_MAX_TAPS && MAX_K_AVG == RTLWS_PFBSPEC_MAX_K_AVG && OUT_SUM == RTLWS_OUT_POWER_SUM &&
                   OUT_DB == RTLWS_OUT_MEAN_DB && OUT_PAYLOAD == RTLWS_OUT_PAYLOAD_U8,
               "rtlws_pfbspec.h, rtlws_pfb.h, rtlws_hip.h and pfbspec.h disagree");
 
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
-
-// why a plan's shape is not served, or nullptr
-const char* why_not_plan(int k, int taps)
-{
-    if (k < MIN_LOG2_M || k > MAX_LOG2_M) return "log2_channels must be 4 .. 10";
-    if (taps < 1 || taps > MAX_TAPS) return "taps_per_branch must be 1 .. 32";
-    return nullptr;
-}
-
 // why a run's shape is not served, or nullptr
 const char* why_not(int k, int taps, int hop, int k_avg, long nspectra)
 {
-    if (const char* why = why_not_plan(k, taps)) return why;
-    if (hop != 1 << k && hop != 1 << (k - 1)) return "hop must be M or M / 2";
-    if (k_avg < 1 || k_avg > MAX_K_AVG) return "k_avg must be 1 .. 65536";
-    if (nspectra < 0) return "nspectra must be >= 0";
-    if (nspectra > (long)INT_MAX * spectra_per_block(k, k_avg)) return "more spectra than one grid holds";
-    return nullptr;
+    if (const char* why = why_not_bank(k, taps)) return why;
+    return why_not_sums(k, hop, k_avg, nspectra);
 }
 
 bool known_output(int output) { return output == OUT_SUM || output == OUT_DB || output == OUT_PAYLOAD; }
@@ -113,46 +73,12 @@ int rtlws_pfbspec_grid(int log2_channels, int taps_per_branch, int hop, int k_av
 
 rtlws_pfbspec_plan* rtlws_pfbspec_open(rtlws_engine* e, int log2_channels, int taps_per_branch, const int16_t* taps)
 {
-    const char* fn = "rtlws_pfbspec_open";
     g_err.clear();
-    if (const char* why = why_not_plan(log2_channels, taps_per_branch)) {
-        fail(fn, why, -1);
-        return nullptr;
-    }
-    if (!taps) {
-        fail(fn, "null taps", -1);
-        return nullptr;
-    }
-    if (!e) {
-        fail(fn, "null engine (no usable HIP device: there is no CPU path)", -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "hipSetDevice", err);
-        return nullptr;
-    }
-    int16_t* d_taps = nullptr;
-    float2* d_tw = nullptr;
-    err = rtlws::pfb::upload_plan_arrays(log2_channels, taps_per_branch, taps, &d_taps, &d_tw);
-    if (err == hipSuccess) {
-        err = prepare_pfbspec(log2_channels);
-        if (err != hipSuccess) rtlws::pfb::free_plan_arrays(d_taps, d_tw);
-    }
-    if (err != hipSuccess) {
-        fail_hip(fn, "the taps, the table or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_pfbspec_plan{e, device, log2_channels, taps_per_branch, d_taps, d_tw};
+    return open_plan<rtlws_pfbspec_plan>("rtlws_pfbspec_open", why_not_bank(log2_channels, taps_per_branch), e, log2_channels,
+                                         taps_per_branch, taps, prepare_pfbspec);
 }
 
-void rtlws_pfbspec_close(rtlws_pfbspec_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) rtlws::pfb::free_plan_arrays(p->d_taps, p->d_tw);
-    delete p;
-}
+void rtlws_pfbspec_close(rtlws_pfbspec_plan* p) { close_plan(p); }
 
 int rtlws_pfbspec_run(rtlws_pfbspec_plan* p, const void* d_iq_cu8, long nspectra, int hop, int k_avg, int output, int shifted,
                       float scale, void* d_out, long out_stride, void* stream)
@@ -161,13 +87,12 @@ int rtlws_pfbspec_run(rtlws_pfbspec_plan* p, const void* d_iq_cu8, long nspectra
     g_err.clear();
     // what needs no plan: the hop is a power of two 8 .. 1024, a row holds at least 16 values, a workgroup at most
     // 256 / k_avg spectra
-    if (hop < 8 || hop > 1 << MAX_LOG2_M || (hop & (hop - 1))) return fail(fn, "hop must be M or M / 2", -1);
-    if (k_avg < 1 || k_avg > MAX_K_AVG) return fail(fn, "k_avg must be 1 .. 65536", -1);
+    if (const char* why = why_not_any_hop(hop)) return fail(fn, why, -1);
+    if (const char* why = why_not_k_avg(k_avg)) return fail(fn, why, -1);
     if (!known_output(output)) return fail(fn, "unknown output", -1);
     if (shifted != 0 && shifted != 1) return fail(fn, "shifted must be 0 or 1", -1);
     if (output != OUT_SUM && !(std::isfinite(scale) && scale > 0.0f)) return fail(fn, "scale must be finite and > 0", -1);
-    if (nspectra < 0) return fail(fn, "nspectra must be >= 0", -1);
-    if (nspectra > (long)INT_MAX * spectra_per_block(MIN_LOG2_M, k_avg)) return fail(fn, "more spectra than one grid holds", -1);
+    if (const char* why = why_not_count(nspectra, spectra_per_block(MIN_LOG2_M, k_avg), true)) return fail(fn, why, -1);
     const int row_align = output == OUT_PAYLOAD ? 16 : 4;
     if (out_stride < 1L << MIN_LOG2_M) return fail(fn, "out_stride must be >= M", -1);
     if (out_stride % row_align) return fail(fn, output == OUT_PAYLOAD ? "out_stride must be a multiple of 16 for byte rows"
@@ -183,20 +108,9 @@ int rtlws_pfbspec_run(rtlws_pfbspec_plan* p, const void* d_iq_cu8, long nspectra
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
     SpecParams sp;
+    sp.bank = bank_params(*p, hop, nspectra * k_avg);
     sp.bank.src = d_iq_cu8;
-    sp.bank.out = nullptr;
-    sp.bank.taps = p->d_taps;
-    sp.bank.tw = p->d_tw;
-    sp.bank.nframes = nspectra * k_avg;
-    sp.bank.first = 0;
-    sp.bank.out_stride = 0;
-    sp.bank.taps_per_branch = p->taps_per_branch;
-    sp.bank.half_hop = hop != 1 << p->log2_m;
-    sp.bank.layout = 0;
     sp.out = d_out;
     sp.nspectra = nspectra;
     sp.out_stride = out_stride;
@@ -204,7 +118,7 @@ int rtlws_pfbspec_run(rtlws_pfbspec_plan* p, const void* d_iq_cu8, long nspectra
     sp.output = output;
     sp.shift = shifted ? 1 << (p->log2_m - 1) : 0;
     sp.lin = output == OUT_SUM ? 1.0f : scale / (float)k_avg;
-    err = launch_pfbspec(p->log2_m, sp, st);
+    err = launch_pfbspec(p->log2_m, sp, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }

@@ -10,15 +10,10 @@
 namespace rtlws {
 namespace pfbxc {
 
-constexpr int MAX_K_AVG = 65536;
 constexpr int MIN_INPUTS = 2, MAX_INPUTS = 4;
 
-// The geometry of a launch is the spectrometer's (pfbspec.h), a function of (log2 M, K) alone: with
-// F = pfb::tile_frames(k) frames in a tile, a workgroup owns one spectrum over ceil(K / F) tile iterations where
-// K >= F, else floor(F / K) spectra in one tile; a spectrum's frames are summed in slices of SLICE = min(16, F).
-// Every input has a tile of its own.
-constexpr int slice_frames(int k) { return pfb::tile_frames(k) < 16 ? pfb::tile_frames(k) : 16; }
-constexpr int spectra_per_block(int k, int k_avg) { return k_avg >= pfb::tile_frames(k) ? 1 : pfb::tile_frames(k) / k_avg; }
+// The geometry of a launch is pfb_bank.h's (slice_frames, spectra_per_block), a function of (log2 M, K) alone.  Every
+// input has a tile of its own.
 constexpr int pairs(int ninputs) { return ninputs * (ninputs - 1) / 2; }
 // ninputs tiles (the slices' partial sums reuse them): 69 632, 104 448 or 139 264 bytes of the 160 KiB of a CU
 constexpr int lds_bytes(int k, int ninputs) { return ninputs * pfb::lds_bytes(k); }

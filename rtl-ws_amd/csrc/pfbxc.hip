@@ -21,27 +21,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "pfb_tile.h"
+#include "pfb_ksum.h"
 #include "pfbxc.h"
-#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace pfbxc {
 
 using namespace rtlws::pfb;
 
-// The products pass through an empty asm, so that no sum or difference can take one of them into a fused
-// multiply-add (the file is compiled with contraction on, as the filter bank's transform needs).
-// fl(fl(re re) + fl(im im)): pfbspec.hip's power(), the same three roundings
-__device__ __forceinline__ float power(float2 y)
-{
-    float a = y.x * y.x, b = y.y * y.y;
-    asm("" : "+v"(a));
-    asm("" : "+v"(b));
-    return a + b;
-}
-
-// a conj(b)
+// a conj(b).  The products pass through an empty asm, as in power() (pfb_ksum.h), so that no sum or difference can
+// take one of them into a fused multiply-add
 __device__ __forceinline__ float2 cross(float2 a, float2 b)
 {
     float rr = a.x * b.x, ii = a.y * b.y, ir = a.y * b.x, ri = a.x * b.y;
@@ -132,8 +121,9 @@ __global__ __launch_bounds__(THREADS) void pfbxc_kernel(const XcParams p)
     PfbParams bank = p.bank;
     for (int it = 0; it < nit; ++it) {
         // 1 .. 4: the branch filters and the transform of every row, one input after the other, each into its tile.
-        // The thread index and the arrays' addresses are made opaque before every call, as in pfbspec.hip: what the
-        // passes derive from them is formed there and not held in registers across the loops
+        // The thread index and the arrays' addresses are made opaque before every call, as tile_passes_afresh
+        // (pfb_ksum.h) does: what the passes derive from them is formed there and not held in registers across the
+        // loops.  Spelled out here: through that wrapper the A tiles' addresses compile differently
 #pragma unroll 1
         for (int a = 0; a < A; ++a) {
             int t = tid;
@@ -201,73 +191,26 @@ __global__ __launch_bounds__(THREADS) void pfbxc_kernel(const XcParams p)
     }
 }
 
-template <int K, int A>
-static hipError_t launch_ka(const XcParams& p, hipStream_t st)
-{
-    const int g = spectra_per_block(K, p.k_avg);
-    const long blocks = (p.nspectra + g - 1) / g;
-    hipLaunchKernelGGL((pfbxc_kernel<K, A>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
-}
+// the launch table: f is handed the plan's instantiation
+using Inputs = Vals<2, 3, 4>;
+static_assert(MIN_INPUTS == 2 && MAX_INPUTS == 4, "pfbxc.h and the launch table disagree");
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  The tiles
-// are static LDS, which a launch takes up to the 160 KiB of a compute unit as it is: the opt-in of lds_opt_in
-// (rtlws_internal.h) is for dynamic LDS and has nothing to raise here
-template <int K, int A>
-static hipError_t prepare_ka()
+template <typename F>
+static hipError_t with_kernel(int k, int ninputs, F&& f)
 {
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&pfbxc_kernel<K, A>));
-}
-
-template <int K>
-static hipError_t launch_k(int ninputs, const XcParams& p, hipStream_t st)
-{
-    switch (ninputs) {
-    case 2: return launch_ka<K, 2>(p, st);
-    case 3: return launch_ka<K, 3>(p, st);
-    case 4: return launch_ka<K, 4>(p, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-template <int K>
-static hipError_t prepare_k(int ninputs)
-{
-    switch (ninputs) {
-    case 2: return prepare_ka<K, 2>();
-    case 3: return prepare_ka<K, 3>();
-    case 4: return prepare_ka<K, 4>();
-    default: return hipErrorInvalidValue;
-    }
+    return pick(Log2Ms{}, k, [&](auto kk) { return pick(Inputs{}, ninputs, [&](auto a) { return f(&pfbxc_kernel<kk, a>); }); });
 }
 
 hipError_t launch_pfbxc(int k, int ninputs, const XcParams& p, hipStream_t st)
 {
-    switch (k) {
-    case 4: return launch_k<4>(ninputs, p, st);
-    case 5: return launch_k<5>(ninputs, p, st);
-    case 6: return launch_k<6>(ninputs, p, st);
-    case 7: return launch_k<7>(ninputs, p, st);
-    case 8: return launch_k<8>(ninputs, p, st);
-    case 9: return launch_k<9>(ninputs, p, st);
-    case 10: return launch_k<10>(ninputs, p, st);
-    default: return hipErrorInvalidValue;
-    }
+    const int g = spectra_per_block(k, p.k_avg);
+    const long blocks = (p.nspectra + g - 1) / g;
+    return with_kernel(k, ninputs, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
 hipError_t prepare_pfbxc(int k, int ninputs)
 {
-    switch (k) {
-    case 4: return prepare_k<4>(ninputs);
-    case 5: return prepare_k<5>(ninputs);
-    case 6: return prepare_k<6>(ninputs);
-    case 7: return prepare_k<7>(ninputs);
-    case 8: return prepare_k<8>(ninputs);
-    case 9: return prepare_k<9>(ninputs);
-    case 10: return prepare_k<10>(ninputs);
-    default: return hipErrorInvalidValue;
-    }
+    return with_kernel(k, ninputs, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace pfbxc

@@ -4,58 +4,31 @@
 // device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 #include "pfb_plan.h"
 #include "pfbxc.h"
 #include "rtlws_pfb.h"
 #include "rtlws_pfbxc.h"
 
-struct rtlws_pfbxc_plan {
-    rtlws_engine* engine;
-    int device;
-    int log2_m, taps_per_branch, ninputs;
-    int16_t* d_taps;
-    float2* d_tw;
+struct rtlws_pfbxc_plan : rtlws::pfb::Plan {
+    int ninputs;
 };
 
 namespace {
 
+using namespace rtlws::pfb;
 using namespace rtlws::pfbxc;
-using rtlws::pfb::MAX_LOG2_M;
-using rtlws::pfb::MAX_TAPS;
-using rtlws::pfb::MIN_LOG2_M;
-using rtlws::pfb::THREADS;
 
 static_assert(MIN_LOG2_M == RTLWS_PFB_MIN_LOG2_CHANNELS && MAX_LOG2_M == RTLWS_PFB_MAX_LOG2_CHANNELS &&
                   MAX_TAPS == RTLWS_PFB_MAX_TAPS && MAX_K_AVG == RTLWS_PFBXC_MAX_K_AVG && MIN_INPUTS == RTLWS_PFBXC_MIN_INPUTS &&
                   MAX_INPUTS == RTLWS_PFBXC_MAX_INPUTS,
               "rtlws_pfbxc.h, rtlws_pfb.h and pfbxc.h disagree");
 
-thread_local std::string g_err;
-
-int fail(const char* fn, const char* why, int rc)
-{
-    g_err = std::string(fn) + ": " + why;
-    return rc;
-}
-
-int fail_hip(const char* fn, const char* what, hipError_t e)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
-    g_err = buf;
-    return -3;
-}
-
 // why a plan's shape is not served, or nullptr
 const char* why_not_plan(int k, int taps, int ninputs)
 {
-    if (k < MIN_LOG2_M || k > MAX_LOG2_M) return "log2_channels must be 4 .. 10";
-    if (taps < 1 || taps > MAX_TAPS) return "taps_per_branch must be 1 .. 32";
+    if (const char* why = why_not_bank(k, taps)) return why;
     if (ninputs < MIN_INPUTS || ninputs > MAX_INPUTS) return "ninputs must be 2 .. 4";
     return nullptr;
 }
@@ -64,11 +37,7 @@ const char* why_not_plan(int k, int taps, int ninputs)
 const char* why_not(int k, int taps, int hop, int k_avg, int ninputs, long nspectra)
 {
     if (const char* why = why_not_plan(k, taps, ninputs)) return why;
-    if (hop != 1 << k && hop != 1 << (k - 1)) return "hop must be M or M / 2";
-    if (k_avg < 1 || k_avg > MAX_K_AVG) return "k_avg must be 1 .. 65536";
-    if (nspectra < 0) return "nspectra must be >= 0";
-    if (nspectra > (long)INT_MAX * spectra_per_block(k, k_avg)) return "more spectra than one grid holds";
-    return nullptr;
+    return why_not_sums(k, hop, k_avg, nspectra);
 }
 
 }  // namespace
@@ -117,46 +86,15 @@ int rtlws_pfbxc_grid(int log2_channels, int taps_per_branch, int hop, int k_avg,
 
 rtlws_pfbxc_plan* rtlws_pfbxc_open(rtlws_engine* e, int log2_channels, int taps_per_branch, const int16_t* taps, int ninputs)
 {
-    const char* fn = "rtlws_pfbxc_open";
     g_err.clear();
-    if (const char* why = why_not_plan(log2_channels, taps_per_branch, ninputs)) {
-        fail(fn, why, -1);
-        return nullptr;
-    }
-    if (!taps) {
-        fail(fn, "null taps", -1);
-        return nullptr;
-    }
-    if (!e) {
-        fail(fn, "null engine (no usable HIP device: there is no CPU path)", -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "hipSetDevice", err);
-        return nullptr;
-    }
-    int16_t* d_taps = nullptr;
-    float2* d_tw = nullptr;
-    err = rtlws::pfb::upload_plan_arrays(log2_channels, taps_per_branch, taps, &d_taps, &d_tw);
-    if (err == hipSuccess) {
-        err = prepare_pfbxc(log2_channels, ninputs);
-        if (err != hipSuccess) rtlws::pfb::free_plan_arrays(d_taps, d_tw);
-    }
-    if (err != hipSuccess) {
-        fail_hip(fn, "the taps, the table or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_pfbxc_plan{e, device, log2_channels, taps_per_branch, ninputs, d_taps, d_tw};
+    rtlws_pfbxc_plan* p = open_plan<rtlws_pfbxc_plan>("rtlws_pfbxc_open", why_not_plan(log2_channels, taps_per_branch, ninputs), e,
+                                                      log2_channels, taps_per_branch, taps,
+                                                      [ninputs](int k) { return prepare_pfbxc(k, ninputs); });
+    if (p) p->ninputs = ninputs;
+    return p;
 }
 
-void rtlws_pfbxc_close(rtlws_pfbxc_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) rtlws::pfb::free_plan_arrays(p->d_taps, p->d_tw);
-    delete p;
-}
+void rtlws_pfbxc_close(rtlws_pfbxc_plan* p) { close_plan(p); }
 
 int rtlws_pfbxc_run(rtlws_pfbxc_plan* p, const void* const* d_iq_cu8, long nspectra, int hop, int k_avg, int shifted,
                     float* d_auto, long auto_stride, float* d_cross, long cross_stride, void* stream)
@@ -165,11 +103,10 @@ int rtlws_pfbxc_run(rtlws_pfbxc_plan* p, const void* const* d_iq_cu8, long nspec
     g_err.clear();
     // what needs no plan: the hop is a power of two 8 .. 1024, a row holds at least 16 values, a workgroup at most
     // 256 / k_avg spectra
-    if (hop < 8 || hop > 1 << MAX_LOG2_M || (hop & (hop - 1))) return fail(fn, "hop must be M or M / 2", -1);
-    if (k_avg < 1 || k_avg > MAX_K_AVG) return fail(fn, "k_avg must be 1 .. 65536", -1);
+    if (const char* why = why_not_any_hop(hop)) return fail(fn, why, -1);
+    if (const char* why = why_not_k_avg(k_avg)) return fail(fn, why, -1);
     if (shifted != 0 && shifted != 1) return fail(fn, "shifted must be 0 or 1", -1);
-    if (nspectra < 0) return fail(fn, "nspectra must be >= 0", -1);
-    if (nspectra > (long)INT_MAX * spectra_per_block(MIN_LOG2_M, k_avg)) return fail(fn, "more spectra than one grid holds", -1);
+    if (const char* why = why_not_count(nspectra, spectra_per_block(MIN_LOG2_M, k_avg), true)) return fail(fn, why, -1);
     if (auto_stride < 1L << MIN_LOG2_M) return fail(fn, "auto_stride must be >= M", -1);
     if (auto_stride % 4) return fail(fn, "auto_stride must be a multiple of 4", -1);
     if (cross_stride < 1L << MIN_LOG2_M) return fail(fn, "cross_stride must be >= M", -1);
@@ -183,27 +120,12 @@ int rtlws_pfbxc_run(rtlws_pfbxc_plan* p, const void* const* d_iq_cu8, long nspec
     if (auto_stride < 1L << p->log2_m) return fail(fn, "auto_stride must be >= M", -1);
     if (cross_stride < 1L << p->log2_m) return fail(fn, "cross_stride must be >= M", -1);
     if (nspectra == 0) return 0;
-    for (int a = 0; a < p->ninputs; ++a) {
-        if (!d_iq_cu8[a]) return fail(fn, "null pointer among the captures", -1);
-        if (reinterpret_cast<uintptr_t>(d_iq_cu8[a]) & 15u) return fail(fn, "every capture must be 16-byte aligned", -1);
-    }
+    if (const char* why = why_not_captures(d_iq_cu8, p->ninputs)) return fail(fn, why, -1);
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    hipStream_t st = stream == RTLWS_STREAM_DEFAULT ? hipStreamLegacy
-                     : stream                       ? reinterpret_cast<hipStream_t>(stream)
-                                                    : reinterpret_cast<hipStream_t>(rtlws_engine_stream(p->engine));
     XcParams xp;
-    xp.bank.src = nullptr;
-    xp.bank.out = nullptr;
-    xp.bank.taps = p->d_taps;
-    xp.bank.tw = p->d_tw;
-    xp.bank.nframes = nspectra * k_avg;
-    xp.bank.first = 0;
-    xp.bank.out_stride = 0;
-    xp.bank.taps_per_branch = p->taps_per_branch;
-    xp.bank.half_hop = hop != 1 << p->log2_m;
-    xp.bank.layout = 0;
+    xp.bank = bank_params(*p, hop, nspectra * k_avg);
     for (int a = 0; a < MAX_INPUTS; ++a) xp.src[a] = a < p->ninputs ? d_iq_cu8[a] : nullptr;
     xp.autos = d_auto;
     xp.cross = reinterpret_cast<float2*>(d_cross);
@@ -212,7 +134,7 @@ int rtlws_pfbxc_run(rtlws_pfbxc_plan* p, const void* const* d_iq_cu8, long nspec
     xp.cross_stride = cross_stride;
     xp.k_avg = k_avg;
     xp.shift = shifted ? 1 << (p->log2_m - 1) : 0;
-    err = launch_pfbxc(p->log2_m, p->ninputs, xp, st);
+    err = launch_pfbxc(p->log2_m, p->ninputs, xp, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }

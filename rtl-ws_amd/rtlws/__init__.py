@@ -161,15 +161,7 @@ SYNTH_SYMBOLS = ["rtl_init", "rtl_set_frequency", "rtl_set_sample_rate", "rtl_se
                  "signal_source_remove_callbacks", "signal_source_stop"]
 
 _hip = None
-_long = None
-_anylen = None
-_fm = None
-_ddc = None
-_fmbank = None
-_pfb = None
-_pfbspec = None
-_pfbxc = None
-_pfbbf = None
+_satellites = {}          # path -> the loaded satellite library (_satellite)
 _amd = None
 _cbb = None
 
@@ -248,107 +240,82 @@ def hip_lib():
     return _hip
 
 
+def _satellite(path, prototypes):
+    """A library of its own on top of librtlws_hip.so's engine (include/rtlws_<name>.h), loaded once: librtlws_hip.so
+    first, the build where it is missing, then its prototypes from a table name -> argtypes (an int comes back) or
+    (argtypes, restype)."""
+    L = _satellites.get(path)
+    if L is None:
+        hip_lib()
+        _need(path)
+        L = C.CDLL(path, mode=C.RTLD_GLOBAL)
+        for name, proto in prototypes.items():
+            f = getattr(L, name)
+            if isinstance(proto, tuple):
+                f.argtypes, f.restype = proto
+            else:
+                f.argtypes = proto
+        _satellites[path] = L
+    return L
+
+
+_i, _l, _vp, _ip, _str = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int), C.c_char_p
+_desc, _vpp = C.POINTER(SpectraDesc), C.POINTER(C.c_void_p)
+
+_LONG_PROTOTYPES = {
+    "rtlws_long_supported": [_desc], "rtlws_long_open": ([_vp, _desc, _l], _vp),
+    "rtlws_long_workspace_bytes": ([_vp], C.c_size_t), "rtlws_long_run": [_vp, _vp, _l, _vp, _vp],
+    "rtlws_long_close": ([_vp], None), "rtlws_long_last_error": ([], _str)}
+
+
 def long_lib():
     """librtlws_long.so (include/rtlws_long.h); it needs librtlws_hip.so's engine."""
-    global _long
-    if _long is None:
-        hip_lib()
-        _need(LONG_LIB)
-        L = C.CDLL(LONG_LIB, mode=C.RTLD_GLOBAL)
-        vp, l = C.c_void_p, C.c_long
-        L.rtlws_long_supported.argtypes = [C.POINTER(SpectraDesc)]
-        L.rtlws_long_open.argtypes = [vp, C.POINTER(SpectraDesc), l]
-        L.rtlws_long_open.restype = vp
-        L.rtlws_long_workspace_bytes.argtypes = [vp]
-        L.rtlws_long_workspace_bytes.restype = C.c_size_t
-        L.rtlws_long_run.argtypes = [vp, vp, l, vp, vp]
-        L.rtlws_long_close.argtypes = [vp]
-        L.rtlws_long_close.restype = None
-        L.rtlws_long_last_error.restype = C.c_char_p
-        _long = L
-    return _long
+    return _satellite(LONG_LIB, _LONG_PROTOTYPES)
+
+
+_ANYLEN_PROTOTYPES = {
+    "rtlws_anylen_supported": [_desc], "rtlws_anylen_conv_log2": [_desc], "rtlws_anylen_open": ([_vp, _desc, _l], _vp),
+    "rtlws_anylen_workspace_bytes": ([_vp], C.c_size_t), "rtlws_anylen_run": [_vp, _vp, _l, _vp, _vp],
+    "rtlws_anylen_close": ([_vp], None), "rtlws_anylen_last_error": ([], _str)}
 
 
 def anylen_lib():
     """librtlws_anylen.so (include/rtlws_anylen.h); it needs librtlws_hip.so's engine."""
-    global _anylen
-    if _anylen is None:
-        hip_lib()
-        _need(ANYLEN_LIB)
-        L = C.CDLL(ANYLEN_LIB, mode=C.RTLD_GLOBAL)
-        vp, l = C.c_void_p, C.c_long
-        L.rtlws_anylen_supported.argtypes = [C.POINTER(SpectraDesc)]
-        L.rtlws_anylen_conv_log2.argtypes = [C.POINTER(SpectraDesc)]
-        L.rtlws_anylen_open.argtypes = [vp, C.POINTER(SpectraDesc), l]
-        L.rtlws_anylen_open.restype = vp
-        L.rtlws_anylen_workspace_bytes.argtypes = [vp]
-        L.rtlws_anylen_workspace_bytes.restype = C.c_size_t
-        L.rtlws_anylen_run.argtypes = [vp, vp, l, vp, vp]
-        L.rtlws_anylen_close.argtypes = [vp]
-        L.rtlws_anylen_close.restype = None
-        L.rtlws_anylen_last_error.restype = C.c_char_p
-        _anylen = L
-    return _anylen
+    return _satellite(ANYLEN_LIB, _ANYLEN_PROTOTYPES)
+
+
+_FM_PROTOTYPES = {
+    "rtlws_fm_supported": [_i, _l, _i], "rtlws_fm_grid": [_i, _l, _i, _ip, _ip, _ip, _ip], "rtlws_fm_prepare": [_vp],
+    "rtlws_fm_audio_blocks": [_vp, _vp, _i, _l, _vp, _vp, _i, _vp, _vp],
+    "rtlws_fm_audio_blocks_cu8": [_vp, _i, _vp, _i, _l, _vp, _vp, _i, _vp, _vp, _vp], "rtlws_fm_last_error": ([], _str)}
 
 
 def fm_lib():
     """librtlws_fm.so (include/rtlws_fm.h); it needs librtlws_hip.so's engine."""
-    global _fm
-    if _fm is None:
-        hip_lib()
-        _need(FM_LIB)
-        L = C.CDLL(FM_LIB, mode=C.RTLD_GLOBAL)
-        vp, i, l, ip = C.c_void_p, C.c_int, C.c_long, C.POINTER(C.c_int)
-        L.rtlws_fm_supported.argtypes = [i, l, i]
-        L.rtlws_fm_grid.argtypes = [i, l, i, ip, ip, ip, ip]
-        L.rtlws_fm_prepare.argtypes = [vp]
-        L.rtlws_fm_audio_blocks.argtypes = [vp, vp, i, l, vp, vp, i, vp, vp]
-        L.rtlws_fm_audio_blocks_cu8.argtypes = [vp, i, vp, i, l, vp, vp, i, vp, vp, vp]
-        L.rtlws_fm_last_error.restype = C.c_char_p
-        _fm = L
-    return _fm
+    return _satellite(FM_LIB, _FM_PROTOTYPES)
+
+
+_DDC_PROTOTYPES = {
+    "rtlws_ddc_supported": [_i, _i], "rtlws_ddc_table": [_vp], "rtlws_ddc_tuning_word": [C.c_double, C.c_double, _ip],
+    "rtlws_ddc_open": ([_vp], _vp), "rtlws_ddc_grid": [_i, _i, _l, _ip, _ip, _ip, _ip],
+    "rtlws_ddc_run": [_vp, _i, _vp, _l, _l, _i, _vp, _vp, _l, _vp], "rtlws_ddc_close": ([_vp], None),
+    "rtlws_ddc_last_error": ([], _str)}
 
 
 def ddc_lib():
     """librtlws_ddc.so (include/rtlws_ddc.h); it needs librtlws_hip.so's engine."""
-    global _ddc
-    if _ddc is None:
-        hip_lib()
-        _need(DDC_LIB)
-        L = C.CDLL(DDC_LIB, mode=C.RTLD_GLOBAL)
-        vp, i, l, ip = C.c_void_p, C.c_int, C.c_long, C.POINTER(C.c_int)
-        L.rtlws_ddc_supported.argtypes = [i, i]
-        L.rtlws_ddc_table.argtypes = [vp]
-        L.rtlws_ddc_tuning_word.argtypes = [C.c_double, C.c_double, ip]
-        L.rtlws_ddc_open.argtypes = [vp]
-        L.rtlws_ddc_open.restype = vp
-        L.rtlws_ddc_grid.argtypes = [i, i, l, ip, ip, ip, ip]
-        L.rtlws_ddc_run.argtypes = [vp, i, vp, l, l, i, vp, vp, l, vp]
-        L.rtlws_ddc_close.argtypes = [vp]
-        L.rtlws_ddc_close.restype = None
-        L.rtlws_ddc_last_error.restype = C.c_char_p
-        _ddc = L
-    return _ddc
+    return _satellite(DDC_LIB, _DDC_PROTOTYPES)
+
+
+_FMBANK_PROTOTYPES = {
+    "rtlws_fmbank_supported": [_i, _i, _i, _l], "rtlws_fmbank_grid": [_i, _i, _i, _l, _ip, _ip, _ip, _ip],
+    "rtlws_fmbank_open": ([_vp], _vp), "rtlws_fmbank_run": [_vp, _i, _vp, _i, _l, _l, _i, _vp, _vp, _vp, _vp, _l, _vp],
+    "rtlws_fmbank_close": ([_vp], None), "rtlws_fmbank_last_error": ([], _str)}
 
 
 def fmbank_lib():
     """librtlws_fmbank.so (include/rtlws_fmbank.h); it needs librtlws_hip.so's engine."""
-    global _fmbank
-    if _fmbank is None:
-        hip_lib()
-        _need(FMBANK_LIB)
-        L = C.CDLL(FMBANK_LIB, mode=C.RTLD_GLOBAL)
-        vp, i, l, ip = C.c_void_p, C.c_int, C.c_long, C.POINTER(C.c_int)
-        L.rtlws_fmbank_supported.argtypes = [i, i, i, l]
-        L.rtlws_fmbank_grid.argtypes = [i, i, i, l, ip, ip, ip, ip]
-        L.rtlws_fmbank_open.argtypes = [vp]
-        L.rtlws_fmbank_open.restype = vp
-        L.rtlws_fmbank_run.argtypes = [vp, i, vp, i, l, l, i, vp, vp, vp, vp, l, vp]
-        L.rtlws_fmbank_close.argtypes = [vp]
-        L.rtlws_fmbank_close.restype = None
-        L.rtlws_fmbank_last_error.restype = C.c_char_p
-        _fmbank = L
-    return _fmbank
+    return _satellite(FMBANK_LIB, _FMBANK_PROTOTYPES)
 
 
 def amd_lib():
@@ -435,28 +402,16 @@ def fm_grid(block_len, nblocks, cic_r=0):
     return rc, b.value, t.value, s.value, a.value
 
 
+_PFB_PROTOTYPES = {
+    "rtlws_pfb_supported": [_i, _i, _i], "rtlws_pfb_design": [_i, _i, _vp], "rtlws_pfb_twiddles": [_i, _vp],
+    "rtlws_pfb_samples_needed": ([_i, _i, _i, _l], _l), "rtlws_pfb_grid": [_i, _i, _i, _l, _ip, _ip, _ip, _ip],
+    "rtlws_pfb_open": ([_vp, _i, _i, _vp], _vp), "rtlws_pfb_run": [_vp, _vp, _l, _i, _l, _i, _vp, _l, _vp],
+    "rtlws_pfb_close": ([_vp], None), "rtlws_pfb_last_error": ([], _str)}
+
+
 def pfb_lib():
     """librtlws_pfb.so (include/rtlws_pfb.h); it needs librtlws_hip.so's engine."""
-    global _pfb
-    if _pfb is None:
-        hip_lib()
-        _need(PFB_LIB)
-        L = C.CDLL(PFB_LIB, mode=C.RTLD_GLOBAL)
-        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
-        L.rtlws_pfb_supported.argtypes = [i, i, i]
-        L.rtlws_pfb_design.argtypes = [i, i, vp]
-        L.rtlws_pfb_twiddles.argtypes = [i, vp]
-        L.rtlws_pfb_samples_needed.argtypes = [i, i, i, l]
-        L.rtlws_pfb_samples_needed.restype = l
-        L.rtlws_pfb_grid.argtypes = [i, i, i, l, ip, ip, ip, ip]
-        L.rtlws_pfb_open.argtypes = [vp, i, i, vp]
-        L.rtlws_pfb_open.restype = vp
-        L.rtlws_pfb_run.argtypes = [vp, vp, l, i, l, i, vp, l, vp]
-        L.rtlws_pfb_close.argtypes = [vp]
-        L.rtlws_pfb_close.restype = None
-        L.rtlws_pfb_last_error.restype = C.c_char_p
-        _pfb = L
-    return _pfb
+    return _satellite(PFB_LIB, _PFB_PROTOTYPES)
 
 
 def pfb_last_error():
@@ -504,26 +459,16 @@ def pfb_grid(log2_channels, taps_per_branch, hop, nframes):
     return rc, b.value, t.value, s.value, f.value
 
 
+_PFBSPEC_PROTOTYPES = {
+    "rtlws_pfbspec_supported": [_i, _i, _i, _i, _i], "rtlws_pfbspec_samples_needed": ([_i, _i, _i, _i, _l], _l),
+    "rtlws_pfbspec_grid": [_i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_pfbspec_open": ([_vp, _i, _i, _vp], _vp),
+    "rtlws_pfbspec_run": [_vp, _vp, _l, _i, _i, _i, _i, C.c_float, _vp, _l, _vp], "rtlws_pfbspec_close": ([_vp], None),
+    "rtlws_pfbspec_last_error": ([], _str)}
+
+
 def pfbspec_lib():
     """librtlws_pfbspec.so (include/rtlws_pfbspec.h); it needs librtlws_hip.so's engine."""
-    global _pfbspec
-    if _pfbspec is None:
-        hip_lib()
-        _need(PFBSPEC_LIB)
-        L = C.CDLL(PFBSPEC_LIB, mode=C.RTLD_GLOBAL)
-        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
-        L.rtlws_pfbspec_supported.argtypes = [i, i, i, i, i]
-        L.rtlws_pfbspec_samples_needed.argtypes = [i, i, i, i, l]
-        L.rtlws_pfbspec_samples_needed.restype = l
-        L.rtlws_pfbspec_grid.argtypes = [i, i, i, i, l, ip, ip, ip, ip]
-        L.rtlws_pfbspec_open.argtypes = [vp, i, i, vp]
-        L.rtlws_pfbspec_open.restype = vp
-        L.rtlws_pfbspec_run.argtypes = [vp, vp, l, i, i, i, i, C.c_float, vp, l, vp]
-        L.rtlws_pfbspec_close.argtypes = [vp]
-        L.rtlws_pfbspec_close.restype = None
-        L.rtlws_pfbspec_last_error.restype = C.c_char_p
-        _pfbspec = L
-    return _pfbspec
+    return _satellite(PFBSPEC_LIB, _PFBSPEC_PROTOTYPES)
 
 
 def pfbspec_last_error():
@@ -550,27 +495,16 @@ def pfbspec_grid(log2_channels, taps_per_branch, hop, k_avg, nspectra):
     return rc, b.value, t.value, s.value, g.value
 
 
+_PFBXC_PROTOTYPES = {
+    "rtlws_pfbxc_supported": [_i, _i, _i, _i, _i], "rtlws_pfbxc_samples_needed": ([_i, _i, _i, _i, _l], _l),
+    "rtlws_pfbxc_pair_index": [_i, _i, _i], "rtlws_pfbxc_grid": [_i, _i, _i, _i, _i, _l, _ip, _ip, _ip, _ip],
+    "rtlws_pfbxc_open": ([_vp, _i, _i, _vp, _i], _vp), "rtlws_pfbxc_run": [_vp, _vpp, _l, _i, _i, _i, _vp, _l, _vp, _l, _vp],
+    "rtlws_pfbxc_close": ([_vp], None), "rtlws_pfbxc_last_error": ([], _str)}
+
+
 def pfbxc_lib():
     """librtlws_pfbxc.so (include/rtlws_pfbxc.h); it needs librtlws_hip.so's engine."""
-    global _pfbxc
-    if _pfbxc is None:
-        hip_lib()
-        _need(PFBXC_LIB)
-        L = C.CDLL(PFBXC_LIB, mode=C.RTLD_GLOBAL)
-        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
-        L.rtlws_pfbxc_supported.argtypes = [i, i, i, i, i]
-        L.rtlws_pfbxc_samples_needed.argtypes = [i, i, i, i, l]
-        L.rtlws_pfbxc_samples_needed.restype = l
-        L.rtlws_pfbxc_pair_index.argtypes = [i, i, i]
-        L.rtlws_pfbxc_grid.argtypes = [i, i, i, i, i, l, ip, ip, ip, ip]
-        L.rtlws_pfbxc_open.argtypes = [vp, i, i, vp, i]
-        L.rtlws_pfbxc_open.restype = vp
-        L.rtlws_pfbxc_run.argtypes = [vp, C.POINTER(vp), l, i, i, i, vp, l, vp, l, vp]
-        L.rtlws_pfbxc_close.argtypes = [vp]
-        L.rtlws_pfbxc_close.restype = None
-        L.rtlws_pfbxc_last_error.restype = C.c_char_p
-        _pfbxc = L
-    return _pfbxc
+    return _satellite(PFBXC_LIB, _PFBXC_PROTOTYPES)
 
 
 def pfbxc_last_error():
@@ -601,27 +535,17 @@ def pfbxc_grid(log2_channels, taps_per_branch, hop, k_avg, ninputs, nspectra):
     return rc, b.value, t.value, s.value, g.value
 
 
+_PFBBF_PROTOTYPES = {
+    "rtlws_pfbbf_supported": [_i, _i, _i, _i, _i], "rtlws_pfbbf_samples_needed": ([_i, _i, _i, _i, _l], _l),
+    "rtlws_pfbbf_grid": [_i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_pfbbf_open": ([_vp, _i, _i, _vp, _i, _i], _vp),
+    "rtlws_pfbbf_run": [_vp, _vpp, _i, _vp, _i, _l, _i, _l, _i, _vp, _l, _l, _vp],
+    "rtlws_pfbbf_power": [_vp, _vpp, _i, _vp, _i, _l, _i, _i, _i, _vp, _l, _vp], "rtlws_pfbbf_close": ([_vp], None),
+    "rtlws_pfbbf_last_error": ([], _str)}
+
+
 def pfbbf_lib():
     """librtlws_pfbbf.so (include/rtlws_pfbbf.h); it needs librtlws_hip.so's engine."""
-    global _pfbbf
-    if _pfbbf is None:
-        hip_lib()
-        _need(PFBBF_LIB)
-        L = C.CDLL(PFBBF_LIB, mode=C.RTLD_GLOBAL)
-        i, l, vp, ip = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int)
-        L.rtlws_pfbbf_supported.argtypes = [i, i, i, i, i]
-        L.rtlws_pfbbf_samples_needed.argtypes = [i, i, i, i, l]
-        L.rtlws_pfbbf_samples_needed.restype = l
-        L.rtlws_pfbbf_grid.argtypes = [i, i, i, i, l, ip, ip, ip, ip]
-        L.rtlws_pfbbf_open.argtypes = [vp, i, i, vp, i, i]
-        L.rtlws_pfbbf_open.restype = vp
-        L.rtlws_pfbbf_run.argtypes = [vp, C.POINTER(vp), i, vp, i, l, i, l, i, vp, l, l, vp]
-        L.rtlws_pfbbf_power.argtypes = [vp, C.POINTER(vp), i, vp, i, l, i, i, i, vp, l, vp]
-        L.rtlws_pfbbf_close.argtypes = [vp]
-        L.rtlws_pfbbf_close.restype = None
-        L.rtlws_pfbbf_last_error.restype = C.c_char_p
-        _pfbbf = L
-    return _pfbbf
+    return _satellite(PFBBF_LIB, _PFBBF_PROTOTYPES)
 
 
 def pfbbf_last_error():
@@ -854,44 +778,52 @@ class DdcPlan:
             pass
 
 
-class PfbSpecPlan:
-    """rtlws_pfbspec_plan* of include/rtlws_pfbspec.h: the prototype (int16 [T * M]) and the transform's table on the
-    engine's device, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the
-    library's text."""
+class _PolyphasePlan:
+    """What the plans of the polyphase family share (include/rtlws_pfb.h and the headers on top of it): the prototype
+    (int16 [T * M]) and the transform's table on the engine's device, the kernels loaded.  eng may be None (as a C
+    caller's NULL engine): open then fails with the library's text.  A subclass names its library (_name, _lib), hands
+    __init__ what its open takes behind the taps, and keeps its run signatures."""
+    _name, _lib, h = None, None, None
 
-    def __init__(self, eng, log2_channels, taps):
+    def __init__(self, eng, log2_channels, taps, *counts):
+        """counts: what the library's open takes behind the taps (none, ninputs, or ninputs and nbeams)."""
         self.eng = eng
         self.log2_channels = int(log2_channels)
         taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
         m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
         if m == 0 or taps.size == 0 or taps.size % m:
-            raise RuntimeError("rtlws_pfbspec_open: the prototype holds taps_per_branch * M taps")
+            raise RuntimeError("rtlws_%s_open: the prototype holds taps_per_branch * M taps" % self._name)
         self.taps_per_branch = taps.size // m
-        self.h = pfbspec_lib().rtlws_pfbspec_open(eng.h if eng is not None else None, self.log2_channels,
-                                                  self.taps_per_branch, _p(taps))
+        self.h = self._fn("open")(eng.h if eng is not None else None, self.log2_channels, self.taps_per_branch, _p(taps), *counts)
         if not self.h:
-            raise RuntimeError("rtlws_pfbspec_open failed: %s" % pfbspec_last_error())
+            raise RuntimeError("rtlws_%s_open failed: %s" % (self._name, self._fn("last_error")().decode()))
 
     @classmethod
-    def open(cls, eng, log2_channels, taps):
-        return cls(eng, log2_channels, taps)
+    def open(cls, *args, **kwargs):
+        return cls(*args, **kwargs)
 
-    def run(self, d_iq, nspectra, k_avg, d_out, hop=None, output="power", shifted=False, scale=1.0, out_stride=None,
-            stream=None, check=True):
-        """One launch: row j at d_out + j * out_stride elements (f32, or bytes for "payload").  output: "power", "db",
-        "payload" or a value of enum rtlws_output."""
-        m = 1 << self.log2_channels
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = pfbspec_lib().rtlws_pfbspec_run(self.h, ptr(d_iq), int(nspectra), int(m if hop is None else hop), int(k_avg),
-                                             int(_PFBSPEC_OUTPUTS.get(output, output)), int(shifted), float(scale), ptr(d_out),
-                                             int(m if out_stride is None else out_stride), stream)
+    @classmethod
+    def _fn(cls, what):
+        return getattr(cls._lib(), "rtlws_%s_%s" % (cls._name, what))
+
+    @staticmethod
+    def _ptr(x):
+        return None if x is None else Engine._ptr(x)
+
+    @classmethod
+    def _array(cls, d_iqs):
+        """The captures' device buffers or pointers as a C array, or None (a NULL array)."""
+        return None if d_iqs is None else (C.c_void_p * max(len(d_iqs), 1))(*[cls._ptr(x) for x in d_iqs])
+
+    def _call(self, what, check, *args):
+        rc = self._fn(what)(self.h, *args)
         if check and rc != 0:
-            raise RuntimeError("rtlws_pfbspec_run failed (rc=%d): %s" % (rc, pfbspec_last_error()))
+            raise RuntimeError("rtlws_%s_%s failed (rc=%d): %s" % (self._name, what, rc, self._fn("last_error")().decode()))
         return rc
 
     def close(self):
         if self.h:
-            pfbspec_lib().rtlws_pfbspec_close(self.h)
+            self._fn("close")(self.h)
             self.h = None
 
     def __del__(self):
@@ -901,28 +833,31 @@ class PfbSpecPlan:
             pass
 
 
-class PfbXcPlan:
+class PfbSpecPlan(_PolyphasePlan):
+    """rtlws_pfbspec_plan* of include/rtlws_pfbspec.h: the prototype (int16 [T * M]) and the transform's table on the
+    engine's device, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the
+    library's text."""
+    _name, _lib = "pfbspec", staticmethod(pfbspec_lib)
+
+    def run(self, d_iq, nspectra, k_avg, d_out, hop=None, output="power", shifted=False, scale=1.0, out_stride=None,
+            stream=None, check=True):
+        """One launch: row j at d_out + j * out_stride elements (f32, or bytes for "payload").  output: "power", "db",
+        "payload" or a value of enum rtlws_output."""
+        m = 1 << self.log2_channels
+        return self._call("run", check, self._ptr(d_iq), int(nspectra), int(m if hop is None else hop), int(k_avg),
+                          int(_PFBSPEC_OUTPUTS.get(output, output)), int(shifted), float(scale), self._ptr(d_out),
+                          int(m if out_stride is None else out_stride), stream)
+
+
+class PfbXcPlan(_PolyphasePlan):
     """rtlws_pfbxc_plan* of include/rtlws_pfbxc.h: the prototype (int16 [T * M]) and the transform's table on the
     engine's device, the kernel for ninputs captures loaded.  eng may be None (as a C caller's NULL engine): open then
     fails with the library's text."""
+    _name, _lib = "pfbxc", staticmethod(pfbxc_lib)
 
     def __init__(self, eng, log2_channels, taps, ninputs):
-        self.eng = eng
-        self.log2_channels = int(log2_channels)
         self.ninputs = int(ninputs)
-        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
-        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
-        if m == 0 or taps.size == 0 or taps.size % m:
-            raise RuntimeError("rtlws_pfbxc_open: the prototype holds taps_per_branch * M taps")
-        self.taps_per_branch = taps.size // m
-        self.h = pfbxc_lib().rtlws_pfbxc_open(eng.h if eng is not None else None, self.log2_channels,
-                                              self.taps_per_branch, _p(taps), self.ninputs)
-        if not self.h:
-            raise RuntimeError("rtlws_pfbxc_open failed: %s" % pfbxc_last_error())
-
-    @classmethod
-    def open(cls, eng, log2_channels, taps, ninputs):
-        return cls(eng, log2_channels, taps, ninputs)
+        super().__init__(eng, log2_channels, taps, self.ninputs)
 
     def run(self, d_iqs, nspectra, k_avg, d_auto, d_cross, hop=None, shifted=False, auto_stride=None, cross_stride=None,
             stream=None, check=True):
@@ -930,54 +865,20 @@ class PfbXcPlan:
         d_auto (auto_stride floats apart) is S_a[j]; row j * NX + x of d_cross (cross_stride complex values apart)
         is V_ab[j]."""
         m = 1 << self.log2_channels
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        arr = None if d_iqs is None else (C.c_void_p * max(len(d_iqs), 1))(*[ptr(x) for x in d_iqs])
-        rc = pfbxc_lib().rtlws_pfbxc_run(self.h, arr, int(nspectra), int(m if hop is None else hop), int(k_avg), int(shifted),
-                                         ptr(d_auto), int(m if auto_stride is None else auto_stride), ptr(d_cross),
-                                         int(m if cross_stride is None else cross_stride), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_pfbxc_run failed (rc=%d): %s" % (rc, pfbxc_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            pfbxc_lib().rtlws_pfbxc_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._call("run", check, self._array(d_iqs), int(nspectra), int(m if hop is None else hop), int(k_avg),
+                          int(shifted), self._ptr(d_auto), int(m if auto_stride is None else auto_stride), self._ptr(d_cross),
+                          int(m if cross_stride is None else cross_stride), stream)
 
 
-class PfbBfPlan:
+class PfbBfPlan(_PolyphasePlan):
     """rtlws_pfbbf_plan* of include/rtlws_pfbbf.h: the prototype (int16 [T * M]) and the transform's table on the
     engine's device, both kernels for nbeams beams loaded.  eng may be None (as a C caller's NULL engine): open then
     fails with the library's text."""
+    _name, _lib = "pfbbf", staticmethod(pfbbf_lib)
 
     def __init__(self, eng, log2_channels, taps, ninputs, nbeams):
-        self.eng = eng
-        self.log2_channels = int(log2_channels)
         self.ninputs, self.nbeams = int(ninputs), int(nbeams)
-        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
-        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
-        if m == 0 or taps.size == 0 or taps.size % m:
-            raise RuntimeError("rtlws_pfbbf_open: the prototype holds taps_per_branch * M taps")
-        self.taps_per_branch = taps.size // m
-        self.h = pfbbf_lib().rtlws_pfbbf_open(eng.h if eng is not None else None, self.log2_channels,
-                                              self.taps_per_branch, _p(taps), self.ninputs, self.nbeams)
-        if not self.h:
-            raise RuntimeError("rtlws_pfbbf_open failed: %s" % pfbbf_last_error())
-
-    @classmethod
-    def open(cls, eng, log2_channels, taps, ninputs, nbeams):
-        return cls(eng, log2_channels, taps, ninputs, nbeams)
-
-    @staticmethod
-    def _array(d_iqs):
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        return None if d_iqs is None else (C.c_void_p * max(len(d_iqs), 1))(*[ptr(x) for x in d_iqs])
+        super().__init__(eng, log2_channels, taps, self.ninputs, self.nbeams)
 
     def run(self, d_iqs, d_weights, nframes, d_out, hop=None, out_stride=None, beam_stride=None, first_frame_index=0,
             layout="channel", stream=None, check=True, ninputs=None, nbeams=None):
@@ -991,59 +892,25 @@ class PfbBfPlan:
             out_stride = m if lay == PFB_TIME_MAJOR else nframes
         if beam_stride is None:
             beam_stride = m * nframes
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = pfbbf_lib().rtlws_pfbbf_run(self.h, self._array(d_iqs), int(self.ninputs if ninputs is None else ninputs),
-                                         ptr(d_weights), int(self.nbeams if nbeams is None else nbeams), int(nframes),
-                                         int(m if hop is None else hop), int(first_frame_index), int(lay), ptr(d_out),
-                                         int(out_stride), int(beam_stride), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_pfbbf_run failed (rc=%d): %s" % (rc, pfbbf_last_error()))
-        return rc
+        return self._call("run", check, self._array(d_iqs), int(self.ninputs if ninputs is None else ninputs),
+                          self._ptr(d_weights), int(self.nbeams if nbeams is None else nbeams), int(nframes),
+                          int(m if hop is None else hop), int(first_frame_index), int(lay), self._ptr(d_out),
+                          int(out_stride), int(beam_stride), stream)
 
     def power(self, d_iqs, d_weights, nspectra, k_avg, d_out, hop=None, shifted=False, row_stride=None, stream=None,
               check=True, ninputs=None, nbeams=None):
         """Power mode, one launch.  Row j * B + b of d_out (row_stride floats apart) is S_b[j]."""
         m = 1 << self.log2_channels
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = pfbbf_lib().rtlws_pfbbf_power(self.h, self._array(d_iqs), int(self.ninputs if ninputs is None else ninputs),
-                                           ptr(d_weights), int(self.nbeams if nbeams is None else nbeams), int(nspectra),
-                                           int(m if hop is None else hop), int(k_avg), int(shifted), ptr(d_out),
-                                           int(m if row_stride is None else row_stride), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_pfbbf_power failed (rc=%d): %s" % (rc, pfbbf_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            pfbbf_lib().rtlws_pfbbf_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._call("power", check, self._array(d_iqs), int(self.ninputs if ninputs is None else ninputs),
+                          self._ptr(d_weights), int(self.nbeams if nbeams is None else nbeams), int(nspectra),
+                          int(m if hop is None else hop), int(k_avg), int(shifted), self._ptr(d_out),
+                          int(m if row_stride is None else row_stride), stream)
 
 
-class PfbPlan:
+class PfbPlan(_PolyphasePlan):
     """rtlws_pfb_plan* of include/rtlws_pfb.h: the prototype (int16 [T * M]) and the transform's table on the engine's
     device, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
-
-    def __init__(self, eng, log2_channels, taps):
-        self.eng = eng
-        self.log2_channels = int(log2_channels)
-        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
-        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
-        if m == 0 or taps.size == 0 or taps.size % m:
-            raise RuntimeError("rtlws_pfb_open: the prototype holds taps_per_branch * M taps")
-        self.taps_per_branch = taps.size // m
-        self.h = pfb_lib().rtlws_pfb_open(eng.h if eng is not None else None, self.log2_channels, self.taps_per_branch, _p(taps))
-        if not self.h:
-            raise RuntimeError("rtlws_pfb_open failed: %s" % pfb_last_error())
-
-    @classmethod
-    def open(cls, eng, log2_channels, taps):
-        return cls(eng, log2_channels, taps)
+    _name, _lib = "pfb", staticmethod(pfb_lib)
 
     def run(self, d_iq, nframes, d_out, hop=None, out_stride=None, first_frame_index=0, layout="channel", stream=None,
             check=True):
@@ -1053,23 +920,8 @@ class PfbPlan:
         lay = _PFB_LAYOUTS.get(layout, layout)
         if out_stride is None:
             out_stride = m if lay == PFB_TIME_MAJOR else nframes
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = pfb_lib().rtlws_pfb_run(self.h, ptr(d_iq), int(nframes), int(m if hop is None else hop), int(first_frame_index),
-                                     int(lay), ptr(d_out), int(out_stride), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_pfb_run failed (rc=%d): %s" % (rc, pfb_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            pfb_lib().rtlws_pfb_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._call("run", check, self._ptr(d_iq), int(nframes), int(m if hop is None else hop), int(first_frame_index),
+                          int(lay), self._ptr(d_out), int(out_stride), stream)
 
 
 class FmBankPlan:

@@ -22,6 +22,19 @@ STRICT_K1_P999 = 1e-4
 STRICT_K1_MAX = 5e-3
 
 
+def hash_bytes(n, seed):
+    """n uniform bytes from a counter hash, uint8: byte i = top byte of splitmix64's finaliser of (seed << 40) + i + 1.
+    Integer numpy operations only, so the bytes are the same on every machine: the input of the digest tests."""
+    with np.errstate(over="ignore"):
+        z = (np.arange(1, n + 1, dtype=np.uint64) + (np.uint64(seed) << np.uint64(40))) * np.uint64(0x9E3779B97F4A7C15)
+        z ^= z >> np.uint64(30)
+        z *= np.uint64(0xBF58476D1CE4E5B9)
+        z ^= z >> np.uint64(27)
+        z *= np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    return (z >> np.uint64(56)).astype(np.uint8)
+
+
 def eps_for(K):
     return EPS_K1 if K == 1 else EPS_STRICT
 

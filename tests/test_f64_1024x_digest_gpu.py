@@ -15,6 +15,8 @@ import hashlib
 import numpy as np
 import pytest
 
+from helpers import hash_bytes
+
 # (frames, forced wavefronts per workgroup): 8 192 frames on one workgroup of eight wavefronts per CU -- the form the
 # launcher picks for batches of >= 32 rows per CU -- and a 3-row batch on one-wavefront workgroups
 CASES = {"w8": (8192, 8), "w1": (3, 1)}
@@ -30,15 +32,7 @@ PARENT_DIGESTS = {
 
 def uniform_bytes_iq(frames, seed):
     """(frames, 1024, 2) uint8: byte i = top byte of splitmix64's finaliser of (seed << 40) + i + 1."""
-    n = frames * 1024 * 2
-    with np.errstate(over="ignore"):
-        z = (np.arange(1, n + 1, dtype=np.uint64) + (np.uint64(seed) << np.uint64(40))) * np.uint64(0x9E3779B97F4A7C15)
-        z ^= z >> np.uint64(30)
-        z *= np.uint64(0xBF58476D1CE4E5B9)
-        z ^= z >> np.uint64(27)
-        z *= np.uint64(0x94D049BB133111EB)
-        z ^= z >> np.uint64(31)
-    return (z >> np.uint64(56)).astype(np.uint8).reshape(frames, 1024, 2)
+    return hash_bytes(frames * 1024 * 2, seed).reshape(frames, 1024, 2)
 
 
 def rows_digest(engine, case, rows):
