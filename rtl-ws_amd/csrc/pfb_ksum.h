@@ -7,7 +7,8 @@
 // which rtlws_pfbxc.h and rtlws_pfbbf.h promise to be the spectrometer's bit for bit, stays spelled out in each
 // kernel: one text of the slice loop, of the combine through LDS and of the (spectrum, bin) loop compiled to other
 // instructions in every kernel that took it, and rows of all three libraries then measured outside the spread of
-// the kernels' own text (profiles/pfb_family_refactor_ab.txt).  tests/test_pfb*_gpu.py hold the three to one order.
+// the kernels' own text (profiles/pfb_family_refactor_ab.txt).  tests/test_pfb*_gpu.py hold the three to one order;
+// tests/test_pfb_ksum_gpu.py holds it to the bit at a K of every class of (log2 M, K) (tests/pfb_ksum_cases.py).
 #ifndef RTLWS_PFB_KSUM_H
 #define RTLWS_PFB_KSUM_H
 
