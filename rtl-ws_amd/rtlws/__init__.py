@@ -15,6 +15,7 @@ fail loudly.
   PfbSpecPlan, Engine.pfbspec  include/rtlws_pfbspec.h (polyphase spectrometer: K-frame power of all 2^k channels in one launch)
   PfbXcPlan, Engine.pfbxc  include/rtlws_pfbxc.h (polyphase cross-correlator: K-frame powers and cross-spectra of 2-4 captures in one launch)
   PfbBfPlan, Engine.pfbbf, Engine.pfbbf_power  include/rtlws_pfbbf.h (polyphase beamformer: 1-4 weighted beams of 1-8 captures in one launch)
+  PfbSkPlan, Engine.pfbsk  include/rtlws_pfbsk.h (polyphase spectrometer with spectral-kurtosis excision: the power over the kept ones of L sub-integrations, one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -42,6 +43,7 @@ PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
 PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfbspec.h
 PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
 PFBBF_LIB = os.path.join(LIB_DIR, "librtlws_pfbbf.so")   # include/rtlws_pfbbf.h
+PFBSK_LIB = os.path.join(LIB_DIR, "librtlws_pfbsk.so")   # include/rtlws_pfbsk.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -130,6 +132,9 @@ PFBBF_SYMBOLS = ["rtlws_pfbbf_supported", "rtlws_pfbbf_samples_needed", "rtlws_p
 PFBBF_MAX_K_AVG = 65536
 PFBBF_MIN_INPUTS, PFBBF_MAX_INPUTS = 1, 8
 PFBBF_MIN_BEAMS, PFBBF_MAX_BEAMS = 1, 4
+PFBSK_SYMBOLS = ["rtlws_pfbsk_supported", "rtlws_pfbsk_samples_needed", "rtlws_pfbsk_grid", "rtlws_pfbsk_power_scale",
+                 "rtlws_pfbsk_bounds", "rtlws_pfbsk_open", "rtlws_pfbsk_run", "rtlws_pfbsk_close", "rtlws_pfbsk_last_error"]
+PFBSK_MAX_K_AVG, PFBSK_MAX_NSUB = 65536, 65535
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -571,6 +576,63 @@ def pfbbf_grid(log2_channels, taps_per_branch, hop, k_avg, count):
     return rc, b.value, t.value, s.value, g.value
 
 
+_fp = C.POINTER(C.c_float)
+_PFBSK_PROTOTYPES = {
+    "rtlws_pfbsk_supported": [_i, _i, _i, _i, _i, _i], "rtlws_pfbsk_samples_needed": ([_i, _i, _i, _i, _i, _l], _l),
+    "rtlws_pfbsk_grid": [_i, _i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_pfbsk_power_scale": ([_i, _i, _vp], C.c_float),
+    "rtlws_pfbsk_bounds": [_i, C.c_double, C.c_double, _fp, _fp], "rtlws_pfbsk_open": ([_vp, _i, _i, _vp], _vp),
+    "rtlws_pfbsk_run": [_vp, _vp, _l, _i, _i, _i, C.c_float, C.c_float, C.c_float, _i, _i, C.c_float, _vp, _l, _vp, _l, _vp, _vp,
+                        _l, _vp],
+    "rtlws_pfbsk_close": ([_vp], None), "rtlws_pfbsk_last_error": ([], _str)}
+
+
+def pfbsk_lib():
+    """librtlws_pfbsk.so (include/rtlws_pfbsk.h); it needs librtlws_hip.so's engine."""
+    return _satellite(PFBSK_LIB, _PFBSK_PROTOTYPES)
+
+
+def pfbsk_last_error():
+    return pfbsk_lib().rtlws_pfbsk_last_error().decode()
+
+
+def pfbsk_supported(log2_channels, taps_per_branch, hop, k_avg, nsub, output="power"):
+    """rtlws_pfbsk_supported.  No GPU needed."""
+    return pfbsk_lib().rtlws_pfbsk_supported(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nsub),
+                                             int(_PFBSPEC_OUTPUTS.get(output, output)))
+
+
+def pfbsk_samples_needed(log2_channels, taps_per_branch, hop, k_avg, nsub, nspectra):
+    """rtlws_pfbsk_samples_needed: (nspectra L K - 1) hop + T M, or -1.  No GPU needed."""
+    return pfbsk_lib().rtlws_pfbsk_samples_needed(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nsub),
+                                                  int(nspectra))
+
+
+def pfbsk_grid(log2_channels, taps_per_branch, hop, k_avg, nsub, nspectra):
+    """rtlws_pfbsk_grid: (rc, workgroups, threads, LDS bytes, output rows per workgroup).  No GPU needed."""
+    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = pfbsk_lib().rtlws_pfbsk_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nsub), int(nspectra),
+                                      C.byref(b), C.byref(t), C.byref(s), C.byref(g))
+    return rc, b.value, t.value, s.value, g.value
+
+
+def pfbsk_power_scale(log2_channels, taps):
+    """rtlws_pfbsk_power_scale of a prototype int16 [T * M]: 2^(-2 ceil(log2(128 sum|h|))) as a float.  No GPU needed."""
+    taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+    s = pfbsk_lib().rtlws_pfbsk_power_scale(int(log2_channels), taps.size >> int(log2_channels), _p(taps))
+    if s == 0.0:
+        raise RuntimeError("rtlws_pfbsk_power_scale failed: %s" % pfbsk_last_error())
+    return s
+
+
+def pfbsk_bounds(k_avg, sk_lo, sk_hi):
+    """rtlws_pfbsk_bounds: thresholds on the estimator -> (ratio_lo, ratio_hi) as floats.  No GPU needed."""
+    lo, hi = C.c_float(), C.c_float()
+    rc = pfbsk_lib().rtlws_pfbsk_bounds(int(k_avg), float(sk_lo), float(sk_hi), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise RuntimeError("rtlws_pfbsk_bounds failed (rc=%d): %s" % (rc, pfbsk_last_error()))
+    return lo.value, hi.value
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -847,6 +909,27 @@ class PfbSpecPlan(_PolyphasePlan):
         return self._call("run", check, self._ptr(d_iq), int(nspectra), int(m if hop is None else hop), int(k_avg),
                           int(_PFBSPEC_OUTPUTS.get(output, output)), int(shifted), float(scale), self._ptr(d_out),
                           int(m if out_stride is None else out_stride), stream)
+
+
+class PfbSkPlan(_PolyphasePlan):
+    """rtlws_pfbsk_plan* of include/rtlws_pfbsk.h: the prototype (int16 [T * M]) and the transform's table on the
+    engine's device, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the
+    library's text."""
+    _name, _lib = "pfbsk", staticmethod(pfbsk_lib)
+
+    def run(self, d_iq, nspectra, k_avg, nsub, power_scale, d_clean, ratio_lo=0.0, ratio_hi=float("inf"), d_kept=None,
+            d_s1=None, d_s2=None, hop=None, output="power", shifted=False, scale=1.0, clean_stride=None, kept_stride=None,
+            sub_stride=None, stream=None, check=True):
+        """One launch: clean row j at d_clean + j * clean_stride elements (f32, or bytes for "payload"), its counts at
+        d_kept + j * kept_stride (uint32), the S1 and S2 rows of sub-integration q at d_s1 and d_s2 + q * sub_stride
+        (f32); d_kept, and d_s1 with d_s2, may be None.  output: "power", "db", "payload" or a value of enum
+        rtlws_output."""
+        m = 1 << self.log2_channels
+        return self._call("run", check, self._ptr(d_iq), int(nspectra), int(m if hop is None else hop), int(k_avg), int(nsub),
+                          float(power_scale), float(ratio_lo), float(ratio_hi), int(_PFBSPEC_OUTPUTS.get(output, output)),
+                          int(shifted), float(scale), self._ptr(d_clean), int(m if clean_stride is None else clean_stride),
+                          self._ptr(d_kept), int(m if kept_stride is None else kept_stride), self._ptr(d_s1), self._ptr(d_s2),
+                          int(m if sub_stride is None else sub_stride), stream)
 
 
 class PfbXcPlan(_PolyphasePlan):
@@ -1211,6 +1294,42 @@ class Engine:
             plan.close()
             d_iq.free()
             d_out.free()
+        return out
+
+    # -- include/rtlws_pfbsk.h: host arrays in, (clean rows, kept counts[, S1 rows, S2 rows]) out ----
+    def pfbsk(self, iq, log2_channels, taps, k_avg, nsub, ratio_lo=0.0, ratio_hi=float("inf"), power_scale=None, hop=None,
+              output="power", shifted=False, scale=1.0, nspectra=None, sub_rows=False):
+        """rtlws_pfbsk_run: iq uint8 [(nspectra * nsub * k_avg - 1) * hop + T * M, 2], taps int16 [T * M] -> (float32
+        [nspectra, M] ("power": the sums over the kept sub-integrations; "db") or uint8 [nspectra, M] ("payload"),
+        uint32 [nspectra, M] the numbers kept) and, with sub_rows, float32 [nspectra * nsub, M] S1 and S2 behind them.
+        power_scale None: rtlws_pfbsk_power_scale's.  nspectra None: as many as the capture holds."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        plan = PfbSkPlan(self, log2_channels, taps)
+        m, t, k_avg, nsub = 1 << plan.log2_channels, plan.taps_per_branch, int(k_avg), int(nsub)
+        hop = m if hop is None else int(hop)
+        if power_scale is None:
+            power_scale = pfbsk_power_scale(plan.log2_channels, taps)
+        if nspectra is None:
+            nframes = (iq.shape[0] - t * m) // hop + 1 if iq.shape[0] >= t * m and hop > 0 else 0
+            nspectra = nframes // (k_avg * nsub) if k_avg > 0 and nsub > 0 else 0
+        need = pfbsk_samples_needed(plan.log2_channels, t, hop, k_avg, nsub, nspectra)
+        assert need < 0 or iq.shape[0] >= need, "the capture is shorter than rtlws_pfbsk_samples_needed"
+        dtype = np.uint8 if _PFBSPEC_OUTPUTS.get(output, output) == OUT_PAYLOAD_U8 else np.float32
+        nsubs = nspectra * max(nsub, 0)
+        bufs = [self.upload(iq) if iq.nbytes else self.alloc(16), self.alloc(max(m * nspectra, 1) * np.dtype(dtype).itemsize),
+                self.alloc(max(m * nspectra, 1) * 4)]
+        if sub_rows:
+            bufs += [self.alloc(max(m * nsubs, 1) * 4), self.alloc(max(m * nsubs, 1) * 4)]
+        try:
+            plan.run(bufs[0], nspectra, k_avg, nsub, power_scale, bufs[1], ratio_lo, ratio_hi, bufs[2], *bufs[3:], hop=hop,
+                     output=output, shifted=shifted, scale=scale)
+            self.sync()
+            shapes = [(dtype, (nspectra, m)), (np.uint32, (nspectra, m))] + [(np.float32, (nsubs, m))] * (len(bufs) - 3)
+            out = tuple(self.download(b, dt, sh) if sh[0] else np.zeros(sh, dt) for b, (dt, sh) in zip(bufs[1:], shapes))
+        finally:
+            plan.close()
+            for b in bufs:
+                b.free()
         return out
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
