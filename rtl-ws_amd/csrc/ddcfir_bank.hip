@@ -1,0 +1,210 @@
+// ddcfir_bank.hip -- a bank of digital down-converters with an int16 FIR as the channel filter, in ONE pass over a
+// cmplx_u8 capture (include/rtlws_ddcfir.h): every channel c mixes the capture with exp(-2 pi i k_c n / P), filters
+// with the plan's L taps and decimates by R, all in integers.
+//
+// The arithmetic (P, T as in ddc_bank.hip; h the taps, s the caller's shift):
+//   G_c[n]    = ((h[n] T[k_c n mod P] + 2^13 (1 + i)) >> 14                                part by part, |G| <= |h[n]|
+//   U[c][m]   = sum_{n<L} (x[m R + n] - 128 (1 + i)) * conj(G_c[n])                        int32, windows overlap
+//   out[c][m] = (U[c][m] * conj(T[k_c R g mod P]) + 2^(13+s) (1 + i)) >> (14 + s),  g = first + m
+// It is ddc_bank.hip's contraction with K = 2 L bytes per output, D = A B with v_mfma_i32_16x16x32_i8:
+//   B (32 x 16)  column j = decimated sample m0 + j, k = byte of K step ks of its window: lane l holds column l & 15,
+//                bytes 8 (l >> 4) .. + 7 of the 32 at byte 2 (m R + 16 ks) of the capture, offset binary off by ^ 0x80.
+//                Windows of neighbouring columns overlap; they are read from global memory as they are and the L1/L2
+//                serve the overlap.  R and L multiples of four: one aligned 8-byte load; else two 4-byte loads where both
+//                are even, four 2-byte loads where one is odd;
+//   A (16 x 32)  row 2 c' = Re, 2 c' + 1 = Im of channel c' of a column tile of eight channels: (Gc_n, Gs_n) and
+//                (-Gs_n, Gc_n) at the bytes of tap n, zero from tap L on.  G = 256 Gh + Gl with Gl in -128 .. 127 and,
+//                because |h| <= 32639, Gh in -127 .. 127: two int8 operands, D = 256 (A_h B) + A_l B exactly.  The
+//                workgroup builds them from T, the words and the taps at its start and keeps them in LDS, 16 bytes per
+//                lane and (column tile, K step): at most 4 x 16 x 1 KiB;
+//   D            as in ddc_bank.hip: lane l holds column l & 15 and rows 4 (l >> 4) + i, Re and Im of two channels; the
+//                16 lanes of a row group store 128 consecutive bytes of one channel's stream.
+// ceil(L / 16) K steps go into the same accumulators; a wavefront takes PAIR row tiles against one read of an operand.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ddc_ops.h"
+#include "ddcfir.h"
+#include "rtlws_internal.h"
+
+namespace rtlws {
+namespace ddcfir {
+
+using ddc::inner_sum;
+using ddc::nt_i2;
+using ddc::nt_u2;
+using ddc::pack;
+using ddc::phasor;
+using ddc::v4i;
+
+// The A operands of lane `lane` for column tile ct and K step ks: {high bytes (2 dwords), low bytes (2 dwords)} of
+// G of taps n = 16 ks + 4 (lane >> 4) + t, t < 4, on row lane & 15.  Zero beyond L and beyond C.
+__device__ __forceinline__ uint4 filter_operand(const FirParams& p, int ct, int ks, int lane)
+{
+    const int r = lane & 15, q = lane >> 4;
+    const int c = 8 * ct + (r >> 1);
+    const bool im_row = r & 1;
+    const int k = p.words[c & (MAX_CH - 1)];
+    unsigned hi[2] = {0u, 0u}, lo[2] = {0u, 0u};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int n = 16 * ks + 4 * q + t;
+        int w_re = 0, w_im = 0;                          // what multiplies the sample's re byte and its im byte
+        if (c < p.nch && n < p.ntaps) {
+            const int2 e = phasor(p.table, (unsigned)(k * n));
+            const int h = p.taps[n];
+            const int gc = (h * e.x + (1 << 13)) >> 14, gs = (h * e.y + (1 << 13)) >> 14;
+            w_re = im_row ? -gs : gc;
+            w_im = im_row ? gc : gs;
+        }
+        const int re_l = (int8_t)w_re, im_l = (int8_t)w_im;
+        const unsigned pair_l = ((unsigned)re_l & 0xffu) | (((unsigned)im_l & 0xffu) << 8);
+        const unsigned pair_h = ((unsigned)((w_re - re_l) >> 8) & 0xffu) | (((unsigned)((w_im - im_l) >> 8) & 0xffu) << 8);
+        lo[t >> 1] |= pair_l << (16 * (t & 1));
+        hi[t >> 1] |= pair_h << (16 * (t & 1));
+    }
+    return make_uint4(hi[0], hi[1], lo[0], lo[1]);
+}
+
+// Samples n0 .. n0 + 3 of the window of decimated sample m, two bytes each; nothing from sample L on is read (zero
+// there).  The windows are re-read by the neighbouring outputs: plain loads, the caches keep them.
+template <bool ALIGNED>
+__device__ __forceinline__ long load_window(const void* src, long m, int R, int L, int n0)
+{
+    if constexpr (ALIGNED) {                             // R, L, n0 multiples of four: all four samples or none
+        if (n0 >= L) return 0;
+        const nt_u2 v = *reinterpret_cast<const nt_u2*>(reinterpret_cast<const uint16_t*>(src) + m * R + n0);
+        return pack(v.x, v.y);
+    } else {
+        const uint16_t* s = reinterpret_cast<const uint16_t*>(src) + m * R;
+        if (((R | L) & 1) == 0) {                        // both even (the same for every lane): whole pairs, 4-byte aligned
+            const unsigned lo = n0 < L ? *reinterpret_cast<const unsigned*>(s + n0) : 0u;
+            const unsigned hi = n0 + 2 < L ? *reinterpret_cast<const unsigned*>(s + n0 + 2) : 0u;
+            return pack(lo, hi);
+        }
+        unsigned v[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = n0 + t < L ? (unsigned)s[n0 + t] : 0u;
+        return pack(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+    }
+}
+
+// The block phasor and the store: this lane's two channels c0, c0 + 1 of decimated sample m.
+__device__ __forceinline__ void emit(const FirParams& p, v4i hi, v4i lo, int c0, unsigned kr0, unsigned kr1, long m)
+{
+    const unsigned g16 = ((unsigned)p.first + (unsigned)m) & 0xffffu;      // only the low 16 bits of k R g matter
+    nt_i2* out = reinterpret_cast<nt_i2*>(p.out);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (c0 + h >= p.nch) continue;
+        const int2 v = rotate_shift(inner_sum(hi[2 * h], lo[2 * h]), inner_sum(hi[2 * h + 1], lo[2 * h + 1]),
+                                    phasor(p.table, (h ? kr1 : kr0) * g16), p.shift);
+        const nt_i2 o = {v.x, v.y};
+        out[(long)(c0 + h) * p.out_stride + m] = o;
+    }
+}
+
+// NCT column tiles of eight channels: the accumulators of PAIR row tiles stay in registers at every NCT
+template <bool ALIGNED, int NCT>
+__device__ __forceinline__ void bank_tile(const FirParams& p, const uint4* ops, int nks)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j = lane & 15, q = lane >> 4;
+    const int R = p.decim, L = p.ntaps;
+    const long tile0 = (long)blockIdx.x * TILE_DEC;
+
+    // k_c R mod P of the channels this lane stores
+    unsigned kr[NCT][2];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) kr[ct][h] = (unsigned)(p.words[(8 * ct + 2 * q + h) & (MAX_CH - 1)] * R) & 0xffffu;
+
+#pragma unroll 1
+    for (int it = 0; it < ROW_TILES / (4 * PAIR); ++it) {
+        const long m0 = tile0 + (long)((it * 4 + wave) * PAIR) * ROWS;
+        if (m0 >= p.dec_len) break;                      // the wavefront's later row tiles lie further on
+        long m[PAIR];
+        bool valid[PAIR];
+        v4i hi[PAIR][NCT], lo[PAIR][NCT];
+#pragma unroll
+        for (int i = 0; i < PAIR; ++i) {
+            m[i] = m0 + i * ROWS + j;
+            valid[i] = m[i] < p.dec_len;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) hi[i][ct] = lo[i][ct] = v4i{0, 0, 0, 0};
+        }
+#pragma unroll 1
+        for (int ks = 0; ks < nks; ++ks) {
+            long x[PAIR];
+#pragma unroll
+            for (int i = 0; i < PAIR; ++i)
+                x[i] = (valid[i] ? load_window<ALIGNED>(p.src, m[i], R, L, 16 * ks + 4 * q) : 0) ^ (long)0x8080808080808080UL;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const uint4 a = ops[(ct * nks + ks) * 64 + lane];
+#pragma unroll
+                for (int i = 0; i < PAIR; ++i) {
+                    hi[i][ct] = __builtin_amdgcn_mfma_i32_16x16x32_i8(pack(a.x, a.y), x[i], hi[i][ct], 0, 0, 0);
+                    lo[i][ct] = __builtin_amdgcn_mfma_i32_16x16x32_i8(pack(a.z, a.w), x[i], lo[i][ct], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PAIR; ++i) {
+            if (valid[i]) {
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) emit(p, hi[i][ct], lo[i][ct], 8 * ct + 2 * q, kr[ct][0], kr[ct][1], m[i]);
+            }
+        }
+    }
+}
+
+// ALIGNED: decim and ntaps multiples of four (8-byte operand loads); else any decim 1 .. 128 and ntaps 1 .. 256.
+// Dynamic LDS: lds_bytes(ntaps, nch), the operands of the launch's column tiles and K steps
+template <bool ALIGNED>
+__global__ __launch_bounds__(THREADS) void ddcfir_bank_kernel(const FirParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint4 ops[];
+    const int tid = threadIdx.x;
+    const int nct = col_tiles(p.nch), nks = k_steps(p.ntaps);
+    for (int e = tid; e < nct * nks * 64; e += THREADS) {
+        const int ks = (e >> 6) % nks, ct = (e >> 6) / nks;
+        ops[e] = filter_operand(p, ct, ks, e & 63);
+    }
+    __syncthreads();
+
+    if (nct == 1) bank_tile<ALIGNED, 1>(p, ops, nks);
+    else if (nct == 2) bank_tile<ALIGNED, 2>(p, ops, nks);
+    else if (nct == 3) bank_tile<ALIGNED, 3>(p, ops, nks);
+    else bank_tile<ALIGNED, 4>(p, ops, nks);
+}
+
+// the launch table: f is handed the instantiation of (decim, ntaps)
+template <typename F>
+static hipError_t with_kernel(int decim, int ntaps, F&& f)
+{
+    return pick(Bools{}, aligned_loads(decim, ntaps), [&](auto aligned) { return f(&ddcfir_bank_kernel<aligned>); });
+}
+
+hipError_t launch_bank(const FirParams& p, hipStream_t st)
+{
+    const long blocks = (p.dec_len + TILE_DEC - 1) / TILE_DEC;
+    const size_t lds = (size_t)lds_bytes(p.ntaps, p.nch);
+    return with_kernel(p.decim, p.ntaps,
+                       [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, st, p); });
+}
+
+// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  The largest
+// launch asks for 64 KiB of dynamic LDS, the most that lds_opt_in (rtlws_internal.h) passes without raising a limit
+hipError_t prepare_bank(int decim, int ntaps, int device)
+{
+    return with_kernel(decim, ntaps, [&](auto kernel) {
+        hipFuncAttributes a;
+        const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
+        return e != hipSuccess ? e : lds_opt_in(kernel, device, (size_t)lds_bytes(MAX_TAPS, MAX_CH));
+    });
+}
+
+}  // namespace ddcfir
+}  // namespace rtlws

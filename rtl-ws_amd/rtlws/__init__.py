@@ -10,6 +10,7 @@ fail loudly.
   AnyLenPlan ........ include/rtlws_anylen.h (f64 spectra of any frame length 2 .. 2^19)
   Engine.fm_audio_blocks[_cu8]  include/rtlws_fm.h (the FM receive chain in one launch)
   DdcPlan, Engine.ddc  include/rtlws_ddc.h (tuned channels from one capture: integer mixer + CIC in one launch)
+  DdcFirPlan, Engine.ddcfir  include/rtlws_ddcfir.h (tuned channels with an int16 FIR of up to 256 taps as the channel filter, one launch)
   FmBankPlan, Engine.fm_bank  include/rtlws_fmbank.h (up to 32 FM stations from one capture in one launch)
   PfbPlan, Engine.pfb  include/rtlws_pfb.h (polyphase channelizer: all 2^k channels of one capture in one launch)
   PfbSpecPlan, Engine.pfbspec  include/rtlws_pfbspec.h (polyphase spectrometer: K-frame power of all 2^k channels in one launch)
@@ -39,6 +40,7 @@ ANYLEN_LIB = os.path.join(LIB_DIR, "librtlws_anylen.so") # include/rtlws_anylen.
 FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
 FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.h
+DDCFIR_LIB = os.path.join(LIB_DIR, "librtlws_ddcfir.so") # include/rtlws_ddcfir.h
 PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
 PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfbspec.h
 PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
@@ -110,6 +112,9 @@ DDC_SYMBOLS = ["rtlws_ddc_supported", "rtlws_ddc_table", "rtlws_ddc_tuning_word"
                "rtlws_ddc_run", "rtlws_ddc_close", "rtlws_ddc_last_error"]
 DDC_LOG2_PERIOD = 16       # rtlws_ddc.h: the phase period P = 2^16
 DDC_MAX_CHANNELS = 32
+DDCFIR_SYMBOLS = ["rtlws_ddcfir_supported", "rtlws_ddcfir_samples_needed", "rtlws_ddcfir_grid", "rtlws_ddcfir_design",
+                  "rtlws_ddcfir_bound", "rtlws_ddcfir_open", "rtlws_ddcfir_run", "rtlws_ddcfir_close", "rtlws_ddcfir_last_error"]
+DDCFIR_MAX_TAPS, DDCFIR_MAX_TAP, DDCFIR_MAX_SHIFT = 256, 32639, 30       # rtlws_ddcfir.h
 FMBANK_SYMBOLS = ["rtlws_fmbank_supported", "rtlws_fmbank_grid", "rtlws_fmbank_open", "rtlws_fmbank_run",
                   "rtlws_fmbank_close", "rtlws_fmbank_last_error"]
 FMBANK_MAX_CHANNELS = 32
@@ -310,6 +315,19 @@ _DDC_PROTOTYPES = {
 def ddc_lib():
     """librtlws_ddc.so (include/rtlws_ddc.h); it needs librtlws_hip.so's engine."""
     return _satellite(DDC_LIB, _DDC_PROTOTYPES)
+
+
+_DDCFIR_PROTOTYPES = {
+    "rtlws_ddcfir_supported": [_i, _i, _i], "rtlws_ddcfir_samples_needed": ([_i, _i, _l], _l),
+    "rtlws_ddcfir_grid": [_i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_ddcfir_design": [_i, _i, _vp],
+    "rtlws_ddcfir_bound": [_i, _vp, _i, C.POINTER(C.c_double)], "rtlws_ddcfir_open": ([_vp, _i, _i, _vp], _vp),
+    "rtlws_ddcfir_run": [_vp, _vp, _l, _l, _i, _vp, _i, _vp, _l, _vp], "rtlws_ddcfir_close": ([_vp], None),
+    "rtlws_ddcfir_last_error": ([], _str)}
+
+
+def ddcfir_lib():
+    """librtlws_ddcfir.so (include/rtlws_ddcfir.h); it needs librtlws_hip.so's engine."""
+    return _satellite(DDCFIR_LIB, _DDCFIR_PROTOTYPES)
 
 
 _FMBANK_PROTOTYPES = {
@@ -664,6 +682,46 @@ def ddc_grid(cic_r, nchannels, dec_len):
     return rc, b.value, t.value, s.value, d.value
 
 
+def ddcfir_last_error():
+    return ddcfir_lib().rtlws_ddcfir_last_error().decode()
+
+
+def ddcfir_supported(decim, ntaps, nchannels=1):
+    return ddcfir_lib().rtlws_ddcfir_supported(int(decim), int(ntaps), int(nchannels))
+
+
+def ddcfir_samples_needed(decim, ntaps, dec_len):
+    """rtlws_ddcfir_samples_needed: (dec_len - 1) * decim + ntaps, or -1.  No GPU needed."""
+    return ddcfir_lib().rtlws_ddcfir_samples_needed(int(decim), int(ntaps), int(dec_len))
+
+
+def ddcfir_grid(decim, ntaps, nchannels, dec_len):
+    """rtlws_ddcfir_grid: (rc, workgroups, threads, LDS bytes, decimated samples per tile).  No GPU needed."""
+    b, t, s, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = ddcfir_lib().rtlws_ddcfir_grid(int(decim), int(ntaps), int(nchannels), int(dec_len), C.byref(b), C.byref(t), C.byref(s),
+                                        C.byref(d))
+    return rc, b.value, t.value, s.value, d.value
+
+
+def ddcfir_design(decim, ntaps):
+    """rtlws_ddcfir_design: the Hamming-windowed sinc for decimation by decim, int16 [ntaps].  No GPU needed."""
+    taps = np.zeros(max(int(ntaps), 1), dtype=np.int16)
+    rc = ddcfir_lib().rtlws_ddcfir_design(int(decim), int(ntaps), _p(taps))
+    if rc != 0:
+        raise RuntimeError("rtlws_ddcfir_design failed (rc=%d): %s" % (rc, ddcfir_last_error()))
+    return taps[:ntaps]
+
+
+def ddcfir_bound(taps, out_shift):
+    """rtlws_ddcfir_bound: how far a component lies from the ideal mixer and filter at most.  No GPU needed."""
+    taps = np.ascontiguousarray(taps, dtype=np.int16)
+    b = C.c_double(0.0)
+    rc = ddcfir_lib().rtlws_ddcfir_bound(taps.size, _p(taps), int(out_shift), C.byref(b))
+    if rc != 0:
+        raise RuntimeError("rtlws_ddcfir_bound failed (rc=%d): %s" % (rc, ddcfir_last_error()))
+    return b.value
+
+
 def fmbank_last_error():
     return fmbank_lib().rtlws_fmbank_last_error().decode()
 
@@ -831,6 +889,46 @@ class DdcPlan:
     def close(self):
         if self.h:
             ddc_lib().rtlws_ddc_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DdcFirPlan:
+    """rtlws_ddcfir_plan* of include/rtlws_ddcfir.h: the taps and the phasor table on the engine's device, the kernel of
+    (decim, ntaps) loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+
+    def __init__(self, eng, decim, taps):
+        self.eng = eng
+        self.decim = int(decim)
+        self.taps = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        self.ntaps = 0 if self.taps is None else self.taps.size
+        self.h = ddcfir_lib().rtlws_ddcfir_open(eng.h if eng is not None else None, self.decim, self.ntaps,
+                                                None if self.taps is None else _p(self.taps))
+        if not self.h:
+            raise RuntimeError("rtlws_ddcfir_open failed: %s" % ddcfir_last_error())
+
+    @classmethod
+    def open(cls, eng, decim, taps):
+        return cls(eng, decim, taps)
+
+    def run(self, d_iq, dec_len, tuning_words, d_out, out_shift=14, out_stride=None, first_dec_index=0, stream=None, check=True):
+        """One launch: channel c of the bank is the cmplx_s32 stream at d_out + c * out_stride samples."""
+        words = (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
+        ptr = lambda x: None if x is None else Engine._ptr(x)
+        rc = ddcfir_lib().rtlws_ddcfir_run(self.h, ptr(d_iq), int(dec_len), int(first_dec_index), len(tuning_words), words,
+                                           int(out_shift), ptr(d_out), int(dec_len if out_stride is None else out_stride), stream)
+        if check and rc != 0:
+            raise RuntimeError("rtlws_ddcfir_run failed (rc=%d): %s" % (rc, ddcfir_last_error()))
+        return rc
+
+    def close(self):
+        if self.h:
+            ddcfir_lib().rtlws_ddcfir_close(self.h)
             self.h = None
 
     def __del__(self):
@@ -1236,6 +1334,29 @@ class Engine:
         d_out = self.alloc(max(nch * dec_len, 1) * 8)
         try:
             plan.run(cic_r, d_iq, dec_len, tuning_words, d_out, dec_len, first_dec_index)
+            self.sync()
+            out = self.download(d_out, np.int32, (nch, dec_len, 2)) if nch * dec_len else np.zeros((nch, 0, 2), np.int32)
+        finally:
+            plan.close()
+            d_iq.free()
+            d_out.free()
+        return out
+
+    # -- include/rtlws_ddcfir.h: host arrays in, the filtered bank's streams out ----
+    def ddcfir(self, iq, decim, taps, tuning_words, out_shift=14, first_dec_index=0, dec_len=None):
+        """rtlws_ddcfir_run: iq uint8 [(dec_len - 1) * decim + ntaps, 2] (dec_len: as many as iq holds), taps int16 [ntaps],
+        one tuning word per channel -> int32 [C, dec_len, 2].  The capture is uploaded at exactly the samples needed."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        plan = DdcFirPlan(self, decim, taps)
+        if dec_len is None:
+            dec_len = (iq.shape[0] - plan.ntaps) // plan.decim + 1 if iq.shape[0] >= plan.ntaps else 0
+        need = ddcfir_samples_needed(plan.decim, plan.ntaps, dec_len)
+        assert 0 <= need <= iq.shape[0]
+        nch = len(tuning_words)
+        d_iq = self.upload(iq[:need]) if need else self.alloc(16)
+        d_out = self.alloc(max(nch * dec_len, 1) * 8)
+        try:
+            plan.run(d_iq, dec_len, tuning_words, d_out, out_shift, dec_len, first_dec_index)
             self.sync()
             out = self.download(d_out, np.int32, (nch, dec_len, 2)) if nch * dec_len else np.zeros((nch, 0, 2), np.int32)
         finally:
