@@ -25,6 +25,9 @@ constexpr int ROW_TILES = TILE_DEC / ROWS;
 constexpr int COL_TILES = MAX_CH / 8;     // 4
 constexpr int K_STEPS = MAX_R / 16;       // 8: the generic kernel's phasor operands, 16 bytes per lane and (tile, step)
 constexpr int LDS_BYTES_ANY = COL_TILES * K_STEPS * 64 * 16;
+// the kernels' template argument: the factors with an instantiation of their own (one K step, the phasor operands in
+// registers), 0 for the kernel of any factor (the operands in LDS).  Also fm_bank.hip's
+constexpr int rt_of(int cic_r) { return cic_r == 8 || cic_r == 10 || cic_r == 12 ? cic_r : 0; }
 
 struct BankParams {
     const void* src;          // cmplx_u8, dec_len * cic_r samples

@@ -23,24 +23,10 @@
 
 #include "ddc_bank.h"
 #include "ddc_ops.h"
+#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace ddc {
-
-// The block phasor and the store: this lane's two channels c0, c0 + 1 of decimated sample m.
-__device__ __forceinline__ void emit(const BankParams& p, v4i hi, v4i lo, int c0, unsigned kr0, unsigned kr1, long m)
-{
-    const unsigned g16 = ((unsigned)p.first + (unsigned)m) & 0xffffu;      // only the low 16 bits of k R g matter
-    nt_i2* out = reinterpret_cast<nt_i2*>(p.out);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (c0 + h >= p.nch) continue;
-        const int2 v = rotate(inner_sum(hi[2 * h], lo[2 * h]), inner_sum(hi[2 * h + 1], lo[2 * h + 1]),
-                              phasor(p.table, (h ? kr1 : kr0) * g16));
-        const nt_i2 o = {v.x, v.y};
-        out[(long)(c0 + h) * p.out_stride + m] = o;
-    }
-}
 
 // RT = 8, 10, 12: that factor, one K step, the phasor operands in registers.  RT = 0: any factor 1 .. 128.
 template <int RT>
@@ -130,31 +116,27 @@ __global__ __launch_bounds__(THREADS) void ddc_bank_kernel(const BankParams p)
     }
 }
 
-template <int RT>
-static hipError_t launch_rt(const BankParams& p, hipStream_t st)
+// the launch table: f is handed the instantiation of cic_r (pick) or every instantiation in turn (visit_all)
+template <typename Choice, typename F>
+static hipError_t with_kernel(Choice choose, int cic_r, F&& f)
 {
-    const long blocks = (p.dec_len + TILE_DEC - 1) / TILE_DEC;
-    hipLaunchKernelGGL((ddc_bank_kernel<RT>), dim3((unsigned)blocks), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
+    return choose(Vals<0, 8, 10, 12>{}, rt_of(cic_r), [&](auto rt) { return f(&ddc_bank_kernel<rt>); });
 }
 
 hipError_t launch_bank(const BankParams& p, hipStream_t st)
 {
-    if (p.cic_r == 8) return launch_rt<8>(p, st);
-    if (p.cic_r == 10) return launch_rt<10>(p, st);
-    if (p.cic_r == 12) return launch_rt<12>(p, st);
-    return launch_rt<0>(p, st);
+    const long blocks = (p.dec_len + TILE_DEC - 1) / TILE_DEC;
+    return with_kernel(pick, p.cic_r, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call
+// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  A plan does
+// not know cic_r: every instantiation
 hipError_t prepare_bank()
 {
-    hipFuncAttributes a;
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<0>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<8>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<10>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&ddc_bank_kernel<12>));
-    return e;
+    return with_kernel(visit_all, 0, [](auto kernel) {
+        hipFuncAttributes a;
+        return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
+    });
 }
 
 }  // namespace ddc

@@ -1,5 +1,5 @@
 // ddc_table.h -- the phasor table T of include/rtlws_ddc.h, one builder text for every library that holds a copy
-// (ddc_shim.hip, fmbank_shim.hip).  Host only, and no header but the standard library's: tests/test_fmbank_cpu.py
+// (ddc_plan.h's open_plan, rtlws_ddc_table).  Host only, and no header but the standard library's: tests/test_fmbank_cpu.py
 // compiles it alone.
 #ifndef RTLWS_DDC_TABLE_H
 #define RTLWS_DDC_TABLE_H

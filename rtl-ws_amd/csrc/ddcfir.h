@@ -1,6 +1,6 @@
 // ddcfir.h -- shared between ddcfir_bank.hip (the kernels) and ddcfir_shim.hip (rtlws_ddcfir.h's host glue): the
-// geometry of the filtered down-converter bank, its kernel parameters and the one integer piece it does not take
-// from ddc_ops.h, the block-phasor rotation with the caller's shift.
+// geometry of the filtered down-converter bank and its kernel parameters; its integer pieces are
+// ddc_ops.h's.
 #ifndef RTLWS_DDCFIR_BANK_H
 #define RTLWS_DDCFIR_BANK_H
 
@@ -44,15 +44,8 @@ struct FirParams {
     int16_t words[MAX_CH];    // the tuning words travel by value
 };
 
-// (U * conj(e) + 2^(13 + s) (1 + i)) >> (14 + s) with e the block phasor: int64, arithmetic shift.  ddc::rotate is
-// the case s = 14
-__device__ __forceinline__ int2 rotate_shift(int ur, int ui, int2 e, int s)
-{
-    const long r = 1L << (13 + s);
-    const long vr = (long)ur * e.x + (long)ui * e.y + r;
-    const long vi = (long)ui * e.x - (long)ur * e.y + r;
-    return make_int2((int)(vr >> (14 + s)), (int)(vi >> (14 + s)));
-}
+// the shift s of ddc_ops.h's rotation and store: the caller's
+__device__ __forceinline__ int shift_of(const FirParams& p) { return p.shift; }
 
 // ceil(dec_len / TILE_DEC) workgroups of the instantiation of (decim, ntaps); dec_len > 0
 hipError_t launch_bank(const FirParams& p, hipStream_t st);

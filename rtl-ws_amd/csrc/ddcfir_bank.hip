@@ -30,8 +30,7 @@
 namespace rtlws {
 namespace ddcfir {
 
-using ddc::inner_sum;
-using ddc::nt_i2;
+using ddc::emit;
 using ddc::nt_u2;
 using ddc::pack;
 using ddc::phasor;
@@ -57,11 +56,7 @@ __device__ __forceinline__ uint4 filter_operand(const FirParams& p, int ct, int 
             w_re = im_row ? -gs : gc;
             w_im = im_row ? gc : gs;
         }
-        const int re_l = (int8_t)w_re, im_l = (int8_t)w_im;
-        const unsigned pair_l = ((unsigned)re_l & 0xffu) | (((unsigned)im_l & 0xffu) << 8);
-        const unsigned pair_h = ((unsigned)((w_re - re_l) >> 8) & 0xffu) | (((unsigned)((w_im - im_l) >> 8) & 0xffu) << 8);
-        lo[t >> 1] |= pair_l << (16 * (t & 1));
-        hi[t >> 1] |= pair_h << (16 * (t & 1));
+        ddc::split_bytes(hi, lo, t, w_re, w_im);
     }
     return make_uint4(hi[0], hi[1], lo[0], lo[1]);
 }
@@ -86,21 +81,6 @@ __device__ __forceinline__ long load_window(const void* src, long m, int R, int 
 #pragma unroll
         for (int t = 0; t < 4; ++t) v[t] = n0 + t < L ? (unsigned)s[n0 + t] : 0u;
         return pack(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-    }
-}
-
-// The block phasor and the store: this lane's two channels c0, c0 + 1 of decimated sample m.
-__device__ __forceinline__ void emit(const FirParams& p, v4i hi, v4i lo, int c0, unsigned kr0, unsigned kr1, long m)
-{
-    const unsigned g16 = ((unsigned)p.first + (unsigned)m) & 0xffffu;      // only the low 16 bits of k R g matter
-    nt_i2* out = reinterpret_cast<nt_i2*>(p.out);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (c0 + h >= p.nch) continue;
-        const int2 v = rotate_shift(inner_sum(hi[2 * h], lo[2 * h]), inner_sum(hi[2 * h + 1], lo[2 * h + 1]),
-                                    phasor(p.table, (h ? kr1 : kr0) * g16), p.shift);
-        const nt_i2 o = {v.x, v.y};
-        out[(long)(c0 + h) * p.out_stride + m] = o;
     }
 }
 

@@ -1,53 +1,39 @@
-// ddcfir_shim.hip -- extern "C" glue of include/rtlws_ddcfir.h (librtlws_ddcfir.so): the filter design, the taps and
-// the phasor table on the device, argument rules, geometry, the launch.  The engine (device, stream) is
-// librtlws_hip.so's; nothing here reads the environment, and nothing of a run is computed on the host: without a
-// device there is no plan.
+// ddcfir_shim.hip -- extern "C" glue of include/rtlws_ddcfir.h (librtlws_ddcfir.so): the filter design, the taps on
+// the device, argument rules, geometry, the launch.  The plan's base (the phasor table on the device), its open and
+// close and the rules it shares with the other tuned-channel libraries are ddc_plan.h's; decim and
+// ntaps keep its own words.  The engine (device, stream) is librtlws_hip.so's; nothing here reads the environment,
+// and nothing of a run is computed on the host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
-#include "ddc_table.h"
+#include "ddc_plan.h"
 #include "ddcfir.h"
 #include "rtlws_ddc.h"
 #include "rtlws_ddcfir.h"
-#include "shim_common.h"
 
-struct rtlws_ddcfir_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_ddcfir_plan : rtlws::ddc::Plan {
     int decim, ntaps;
-    uint32_t* d_table;
     int16_t* d_taps;
 };
 
 namespace {
 
 using namespace rtlws::ddcfir;
+namespace ddc = rtlws::ddc;
 
 static_assert(rtlws::ddc::LOG2_P == RTLWS_DDC_LOG2_PERIOD && MAX_CH == RTLWS_DDCFIR_MAX_CHANNELS && MAX_R == RTLWS_DDCFIR_MAX_DECIM &&
                   MAX_TAPS == RTLWS_DDCFIR_MAX_TAPS && MAX_TAP == RTLWS_DDCFIR_MAX_TAP && MAX_SHIFT == RTLWS_DDCFIR_MAX_SHIFT,
               "rtlws_ddcfir.h, rtlws_ddc.h and ddcfir.h disagree");
 static_assert(lds_bytes(MAX_TAPS, MAX_CH) == 64 * 1024, "the operands of the largest launch: 64 KiB");
 
-long tiles_of(long dec_len) { return (dec_len + TILE_DEC - 1) / TILE_DEC; }
-
-// the rules, each stated once and returning its text or nullptr
+// the filter's shape, or nullptr
 const char* why_not_filter(int decim, int ntaps)
 {
     if (decim < 1 || decim > MAX_R) return "decim must be 1 .. 128";
     if (ntaps < 1 || ntaps > MAX_TAPS) return "ntaps must be 1 .. 256";
-    return nullptr;
-}
-
-const char* why_not_channels(int nchannels) { return nchannels < 1 || nchannels > MAX_CH ? "nchannels must be 1 .. 32" : nullptr; }
-
-const char* why_not_count(long dec_len)
-{
-    if (dec_len < 0) return "dec_len must be >= 0";
-    if (dec_len > (long)INT_MAX * TILE_DEC) return "more decimated samples than one grid holds";
     return nullptr;
 }
 
@@ -61,7 +47,7 @@ int rtlws_ddcfir_supported(int decim, int ntaps, int nchannels)
 {
     g_err.clear();
     const char* why = why_not_filter(decim, ntaps);
-    if (!why) why = why_not_channels(nchannels);
+    if (!why) why = ddc::why_not_channels(nchannels);
     if (why) fail("rtlws_ddcfir", why, 0);
     return why ? 0 : 1;
 }
@@ -70,7 +56,7 @@ long rtlws_ddcfir_samples_needed(int decim, int ntaps, long dec_len)
 {
     g_err.clear();
     const char* why = why_not_filter(decim, ntaps);
-    if (!why) why = why_not_count(dec_len);
+    if (!why) why = ddc::why_not_dec_len(dec_len);
     if (why) return fail("rtlws_ddcfir_samples_needed", why, -1);
     return dec_len == 0 ? 0 : (dec_len - 1) * decim + ntaps;
 }
@@ -80,10 +66,10 @@ int rtlws_ddcfir_grid(int decim, int ntaps, int nchannels, long dec_len, int* bl
 {
     g_err.clear();
     const char* why = why_not_filter(decim, ntaps);
-    if (!why) why = why_not_channels(nchannels);
-    if (!why) why = why_not_count(dec_len);
+    if (!why) why = ddc::why_not_channels(nchannels);
+    if (!why) why = ddc::why_not_dec_len(dec_len);
     if (why) return fail("rtlws_ddcfir_grid", why, -1);
-    if (blocks) *blocks = (int)tiles_of(dec_len);
+    if (blocks) *blocks = (int)ddc::tiles_of(dec_len);
     if (threads) *threads = THREADS;
     if (lds_bytes_out) *lds_bytes_out = lds_bytes(ntaps, nchannels);
     if (tile_dec) *tile_dec = TILE_DEC;
@@ -133,43 +119,25 @@ rtlws_ddcfir_plan* rtlws_ddcfir_open(rtlws_engine* e, int decim, int ntaps, cons
             if (taps[n] < -MAX_TAP || taps[n] > MAX_TAP)
                 why = "a tap lies outside [-32639, 32639] (the filter is applied as two int8 operands, 256 * high + low: beyond "
                       "the limit the high one leaves int8)";
-    if (!why && !e) why = "null engine (no usable HIP device: there is no CPU path)";
-    if (why) {
-        fail(fn, why, -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "hipSetDevice", err);
-        return nullptr;
-    }
-    std::vector<int16_t> host(2 * (size_t)P);
-    rtlws::ddc::build_table(host.data(), P);
-    uint32_t* d_table = nullptr;
-    int16_t* d_taps = nullptr;
-    err = hipMalloc(reinterpret_cast<void**>(&d_table), host.size() * sizeof(int16_t));
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&d_taps), (size_t)ntaps * sizeof(int16_t));
-    if (err == hipSuccess) err = hipMemcpy(d_table, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d_taps, taps, (size_t)ntaps * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_bank(decim, ntaps, device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "the taps, the table or the kernel", err);
-        if (d_table) (void)hipFree(d_table);
-        if (d_taps) (void)hipFree(d_taps);
-        return nullptr;
-    }
-    return new rtlws_ddcfir_plan{e, device, decim, ntaps, d_table, d_taps};
+    const size_t bytes = (size_t)ntaps * sizeof(int16_t);
+    return ddc::open_plan<rtlws_ddcfir_plan>(
+        fn, why, e,
+        [&](rtlws_ddcfir_plan& p) {
+            p.decim = decim;
+            p.ntaps = ntaps;
+            hipError_t err = hipMalloc(reinterpret_cast<void**>(&p.d_taps), bytes);
+            if (err == hipSuccess) err = hipMemcpy(p.d_taps, taps, bytes, hipMemcpyHostToDevice);
+            if (err == hipSuccess) err = prepare_bank(decim, ntaps, p.device);
+            if (err != hipSuccess) (void)hipFree(p.d_taps);
+            return err;
+        },
+        "the taps, the table or the kernel");
 }
 
 void rtlws_ddcfir_close(rtlws_ddcfir_plan* p)
 {
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) {
-        (void)hipFree(p->d_table);
-        (void)hipFree(p->d_taps);
-    }
-    delete p;
+    if (p && hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_taps);
+    ddc::close_plan(p);
 }
 
 int rtlws_ddcfir_run(rtlws_ddcfir_plan* p, const void* d_iq_cu8, long dec_len, long first_dec_index, int nchannels,
@@ -178,22 +146,16 @@ int rtlws_ddcfir_run(rtlws_ddcfir_plan* p, const void* d_iq_cu8, long dec_len, l
     const char* fn = "rtlws_ddcfir_run";
     g_err.clear();
     // what needs no plan
-    if (const char* why = why_not_channels(nchannels)) return fail(fn, why, -1);
-    if (const char* why = why_not_count(dec_len)) return fail(fn, why, -1);
-    if (first_dec_index < 0) return fail(fn, "first_dec_index must be >= 0", -1);
+    if (const char* why = ddc::why_not_channels(nchannels)) return fail(fn, why, -1);
+    if (const char* why = ddc::why_not_dec_len(dec_len)) return fail(fn, why, -1);
+    if (const char* why = ddc::why_not_first(first_dec_index)) return fail(fn, why, -1);
     if (out_shift < 0 || out_shift > MAX_SHIFT) return fail(fn, "out_shift must be 0 .. 30", -1);
-    if (out_stride < dec_len) return fail(fn, "out_stride must be >= dec_len", -1);
-    if (!tuning_words) return fail(fn, "null tuning_words", -1);
+    if (const char* why = ddc::why_not_out_stride(out_stride, dec_len)) return fail(fn, why, -1);
     FirParams fp;
-    for (int c = 0; c < MAX_CH; ++c) {
-        const int k = c < nchannels ? tuning_words[c] : 0;
-        if (k < -P / 2 || k >= P / 2) return fail(fn, "a tuning word lies outside [-32768, 32768)", -1);
-        fp.words[c] = (int16_t)k;
-    }
-    if (dec_len > 0 && (!d_iq_cu8 || !d_out_cs32)) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_iq_cu8) & 15u) return fail(fn, "d_iq_cu8 must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_out_cs32) & 7u) return fail(fn, "d_out_cs32 must be 8-byte aligned", -1);
-    if (!p) return fail(fn, "null plan (no usable HIP device: there is no CPU path)", -1);
+    if (const char* why = ddc::fill_words(fp.words, tuning_words, nchannels)) return fail(fn, why, -1);
+    if (const char* why = ddc::why_not_capture(dec_len > 0, d_iq_cu8, d_out_cs32)) return fail(fn, why, -1);
+    if (const char* why = ddc::why_not_cs32(d_out_cs32)) return fail(fn, why, -1);
+    if (const char* why = ddc::why_not_plan(p)) return fail(fn, why, -1);
     // the plan's shape decides nothing further: every (decim, ntaps) a plan holds serves every count above
     if (dec_len == 0) return 0;
 

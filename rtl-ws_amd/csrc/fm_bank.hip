@@ -18,6 +18,7 @@
 #include "fm_bank.h"
 #include "fm_maps.h"
 #include "fm_math.h"
+#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace fmbank {
@@ -241,20 +242,18 @@ __global__ __launch_bounds__(THREADS) void fm_bank_state_copy_kernel(const float
     for (int i = threadIdx.x; i < nfloats; i += THREADS) out[i] = in[i];
 }
 
-template <int RT>
-static hipError_t launch_rt(const BankParams& p, hipStream_t st)
+// the launch table: f is handed the instantiation of cic_r (pick) or every instantiation in turn (visit_all)
+template <typename Choice, typename F>
+static hipError_t with_kernel(Choice choose, int cic_r, F&& f)
 {
-    const long nct = (p.nch + COL_CH - 1) / COL_CH;
-    hipLaunchKernelGGL((fm_bank_kernel<RT>), dim3((unsigned)((p.ntiles + 1) * nct)), dim3(THREADS), 0, st, p);
-    return hipGetLastError();
+    return choose(Vals<0, 8, 10, 12>{}, ddc::rt_of(cic_r), [&](auto rt) { return f(&fm_bank_kernel<rt>); });
 }
 
 hipError_t launch_bank(const BankParams& p, hipStream_t st)
 {
-    if (p.cic_r == 8) return launch_rt<8>(p, st);
-    if (p.cic_r == 10) return launch_rt<10>(p, st);
-    if (p.cic_r == 12) return launch_rt<12>(p, st);
-    return launch_rt<0>(p, st);
+    const long nct = (p.nch + COL_CH - 1) / COL_CH;
+    return with_kernel(pick, p.cic_r,
+                       [&](auto kernel) { return launch(kernel, dim3((unsigned)((p.ntiles + 1) * nct)), dim3(THREADS), 0, st, p); });
 }
 
 hipError_t launch_state_copy(const float* state_in, float* state_out, int nfloats, hipStream_t st)
@@ -264,16 +263,14 @@ hipError_t launch_state_copy(const float* state_in, float* state_out, int nfloat
 }
 
 // hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  The LDS of
-// the kernels is static (above 64 KiB, within the CU's 160 KiB): there is no limit to raise.
+// the kernels is static (above 64 KiB, within the CU's 160 KiB): there is no limit to raise.  A plan does not know
+// cic_r: every instantiation, after the state copy
 hipError_t prepare_bank()
 {
     hipFuncAttributes a;
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_state_copy_kernel));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_kernel<0>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_kernel<8>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_kernel<10>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_kernel<12>));
-    return e;
+    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_state_copy_kernel));
+    if (e != hipSuccess) return e;
+    return with_kernel(visit_all, 0, [&](auto kernel) { return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)); });
 }
 
 }  // namespace fmbank

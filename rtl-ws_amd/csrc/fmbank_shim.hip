@@ -1,32 +1,28 @@
-// fmbank_shim.hip -- extern "C" glue of include/rtlws_fmbank.h (librtlws_fmbank.so): the phasor table, argument
-// rules, geometry, the launch.  The engine (device, stream) is librtlws_hip.so's; nothing here reads the
-// environment, and nothing of a run is computed on the host: without a device there is no plan.
+// fmbank_shim.hip -- extern "C" glue of include/rtlws_fmbank.h (librtlws_fmbank.so): argument rules, geometry, the
+// launch.  The plan (the phasor table on the device), its open and close and the rules it shares with the other
+// tuned-channel libraries are ddc_plan.h's; the block rules are its own.  The engine (device,
+// stream) is librtlws_hip.so's; nothing here reads the environment, and nothing of a run is computed on the host:
+// without a device there is no plan.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdint>
-#include <vector>
 
-#include "ddc_table.h"
+#include "ddc_plan.h"
 #include "fm_bank.h"
 #include "rtlws_ddc.h"
 #include "rtlws_fm.h"
 #include "rtlws_fmbank.h"
-#include "shim_common.h"
 
-struct rtlws_fmbank_plan {
-    rtlws_engine* engine;
-    int device;
-    uint32_t* d_table;
-};
+struct rtlws_fmbank_plan : rtlws::ddc::Plan {};
 
 namespace {
 
 using namespace rtlws::fmbank;
-constexpr int P = rtlws::ddc::P;
+namespace ddc = rtlws::ddc;
 
 static_assert(MAX_CH == RTLWS_FMBANK_MAX_CHANNELS && MAX_CH == RTLWS_DDC_MAX_CHANNELS && STATE == RTLWS_FM_STATE_FLOATS &&
-                  rtlws::ddc::LOG2_P == RTLWS_DDC_LOG2_PERIOD,
+                  ddc::LOG2_P == RTLWS_DDC_LOG2_PERIOD,
               "rtlws_fmbank.h, rtlws_ddc.h, rtlws_fm.h and fm_bank.h disagree");
 
 long tiles_of(int block_len, long nblocks)
@@ -42,8 +38,8 @@ const char* why_not(int cic_r, int nchannels, int block_len, long nblocks)
 {
     if (block_len < RTLWS_FM_MIN_BLOCK_LEN) return "block_len must be >= 20 (the reference's half-band keeps ten samples of a block)";
     if (nblocks < 0) return "nblocks must be >= 0";
-    if (cic_r < 1 || cic_r > rtlws::ddc::MAX_R) return "cic_r must be 1 .. 128";
-    if (nchannels < 1 || nchannels > MAX_CH) return "nchannels must be 1 .. 32";
+    if (const char* why = ddc::why_not_cic_r(cic_r)) return why;
+    if (const char* why = ddc::why_not_channels(nchannels)) return why;
     if (nblocks > LONG_MAX / ((long)block_len * 2 * cic_r)) return "nblocks * block_len too large";
     if (tiles_of(block_len, nblocks) + 1 > (long)INT_MAX / col_tiles(nchannels)) return "more tiles than one grid holds";
     return nullptr;
@@ -79,36 +75,10 @@ int rtlws_fmbank_grid(int cic_r, int nchannels, int block_len, long nblocks, int
 rtlws_fmbank_plan* rtlws_fmbank_open(rtlws_engine* e)
 {
     g_err.clear();
-    if (!e) {
-        fail("rtlws_fmbank_open", "null engine (no usable HIP device: there is no CPU path)", -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip("rtlws_fmbank_open", "hipSetDevice", err);
-        return nullptr;
-    }
-    std::vector<int16_t> host(2 * (size_t)P);
-    rtlws::ddc::build_table(host.data(), P);
-    uint32_t* d_table = nullptr;
-    err = hipMalloc(reinterpret_cast<void**>(&d_table), host.size() * sizeof(int16_t));
-    if (err == hipSuccess) err = hipMemcpy(d_table, host.data(), host.size() * sizeof(int16_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_bank();
-    if (err != hipSuccess) {
-        fail_hip("rtlws_fmbank_open", "the table or the kernels", err);
-        if (d_table) (void)hipFree(d_table);
-        return nullptr;
-    }
-    return new rtlws_fmbank_plan{e, device, d_table};
+    return ddc::open_plan<rtlws_fmbank_plan>("rtlws_fmbank_open", nullptr, e, [](ddc::Plan&) { return prepare_bank(); });
 }
 
-void rtlws_fmbank_close(rtlws_fmbank_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_table);
-    delete p;
-}
+void rtlws_fmbank_close(rtlws_fmbank_plan* p) { ddc::close_plan(p); }
 
 int rtlws_fmbank_run(rtlws_fmbank_plan* p, int cic_r, const void* d_iq_cu8, int block_len, long nblocks,
                      long first_dec_index, int nchannels, const int* tuning_words, const float* d_state_in,
@@ -117,24 +87,18 @@ int rtlws_fmbank_run(rtlws_fmbank_plan* p, int cic_r, const void* d_iq_cu8, int 
     const char* fn = "rtlws_fmbank_run";
     g_err.clear();
     if (const char* why = why_not(cic_r, nchannels, block_len, nblocks)) return fail(fn, why, -1);
-    if (first_dec_index < 0) return fail(fn, "first_dec_index must be >= 0", -1);
+    if (const char* why = ddc::why_not_first(first_dec_index)) return fail(fn, why, -1);
     if (audio_stride < nblocks * (long)(block_len / 4)) return fail(fn, "audio_stride must be >= nblocks * quarter", -1);
-    if (!tuning_words) return fail(fn, "null tuning_words", -1);
     BankParams bp;
-    for (int c = 0; c < MAX_CH; ++c) {
-        const int k = c < nchannels ? tuning_words[c] : 0;
-        if (k < -P / 2 || k >= P / 2) return fail(fn, "a tuning word lies outside [-32768, 32768)", -1);
-        bp.words[c] = (int16_t)k;
-    }
+    if (const char* why = ddc::fill_words(bp.words, tuning_words, nchannels)) return fail(fn, why, -1);
     if (!d_state_in || !d_state_out) return fail(fn, "null state pointer", -1);
     const uintptr_t si = reinterpret_cast<uintptr_t>(d_state_in), so = reinterpret_cast<uintptr_t>(d_state_out);
     const uintptr_t state_bytes = (uintptr_t)nchannels * STATE * sizeof(float);
     if (si < so + state_bytes && so < si + state_bytes) return fail(fn, "d_state_in and d_state_out must not overlap", -1);
-    if (nblocks > 0 && (!d_iq_cu8 || !d_audio)) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_iq_cu8) & 15u) return fail(fn, "d_iq_cu8 must be 16-byte aligned", -1);
+    if (const char* why = ddc::why_not_capture(nblocks > 0, d_iq_cu8, d_audio)) return fail(fn, why, -1);
     if ((si | so | reinterpret_cast<uintptr_t>(d_audio)) & 3u)
         return fail(fn, "d_state_in, d_state_out and d_audio must be 4-byte aligned", -1);
-    if (!p) return fail(fn, "null plan (no usable HIP device: there is no CPU path)", -1);
+    if (const char* why = ddc::why_not_plan(p)) return fail(fn, why, -1);
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);

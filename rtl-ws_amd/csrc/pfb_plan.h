@@ -124,20 +124,11 @@ P* open_plan(const char* fn, const char* why, rtlws_engine* e, int k, int taps_p
              const char* what = "the taps, the table or the kernel")
 {
     if (!why && !taps) why = "null taps";
-    if (!why && !e) why = "null engine (no usable HIP device: there is no CPU path)";
-    if (why) {
-        fail(fn, why, -1);
-        return nullptr;
-    }
-    const int device = rtlws_engine_device(e);
-    hipError_t err = hipSetDevice(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "hipSetDevice", err);
-        return nullptr;
-    }
+    const int device = open_device(fn, why, e);
+    if (device < 0) return nullptr;
     int16_t* d_taps = nullptr;
     float2* d_tw = nullptr;
-    err = upload_plan_arrays(k, taps_per_branch, taps, &d_taps, &d_tw);
+    hipError_t err = upload_plan_arrays(k, taps_per_branch, taps, &d_taps, &d_tw);
     if (err == hipSuccess) {
         err = prepare(k);
         if (err != hipSuccess) free_plan_arrays(d_taps, d_tw);

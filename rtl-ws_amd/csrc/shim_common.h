@@ -1,6 +1,6 @@
 // shim_common.h -- what every satellite library's extern "C" glue (*_shim.hip, one per library) says the same way: the
-// library's thread-local error text, how a refusal and a failed runtime call are recorded, and which stream a call
-// runs on.  Everything has internal linkage: a library has one shim, so it has one error slot of its own, and a
+// library's thread-local error text, how a refusal and a failed runtime call are recorded, the head of a plan's open,
+// and which stream a call runs on.  Everything has internal linkage: a library has one shim, so it has one error slot of its own, and a
 // refusal in one library does not touch another's *_last_error().
 #ifndef RTLWS_SHIM_COMMON_H
 #define RTLWS_SHIM_COMMON_H
@@ -30,6 +30,18 @@ thread_local std::string g_err;
     snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
     g_err = buf;
     return -3;
+}
+
+// The head of an rtlws_*_open (pfb_plan.h, ddc_plan.h): `why`, the verdict of the library's own rules, or else the null
+// engine is refused; then the engine's device is made current.  That device, or -1 with the text recorded
+[[maybe_unused]] int open_device(const char* fn, const char* why, rtlws_engine* e)
+{
+    if (!why && !e) why = "null engine (no usable HIP device: there is no CPU path)";
+    if (why) return fail(fn, why, -1);
+    const int device = rtlws_engine_device(e);
+    const hipError_t err = hipSetDevice(device);
+    if (err != hipSuccess) return (void)fail_hip(fn, "hipSetDevice", err), -1;
+    return device;
 }
 
 // include/rtlws_hip.h "Streams": RTLWS_STREAM_DEFAULT is HIP's default stream, null the engine's own, else the caller's

@@ -792,169 +792,15 @@ class DevBuf:
             pass
 
 
-class LongPlan:
-    """rtlws_long_plan* of include/rtlws_long.h: one descriptor, tables and workspace for up to max_frames frames
-    per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
-
-    def __init__(self, eng, desc, max_frames=1):
-        self.eng, self.desc = eng, desc
-        self.h = long_lib().rtlws_long_open(eng.h if eng is not None else None, C.byref(desc), int(max_frames))
-        if not self.h:
-            raise RuntimeError("rtlws_long_open failed: %s" % long_last_error())
-
-    @property
-    def workspace_bytes(self):
-        return long_lib().rtlws_long_workspace_bytes(self.h)
-
-    def run(self, d_in, nframes, d_out, stream=None, check=True):
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = long_lib().rtlws_long_run(self.h, ptr(d_in), int(nframes), ptr(d_out), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_long_run failed (rc=%d): %s" % (rc, long_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            long_lib().rtlws_long_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def long_supported(desc):
-    return long_lib().rtlws_long_supported(C.byref(desc))
-
-
-class AnyLenPlan:
-    """rtlws_anylen_plan* of include/rtlws_anylen.h: one descriptor, tables and workspaces for up to max_frames
-    frames per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
-
-    def __init__(self, eng, desc, max_frames=1):
-        self.eng, self.desc = eng, desc
-        self.h = anylen_lib().rtlws_anylen_open(eng.h if eng is not None else None, C.byref(desc), int(max_frames))
-        if not self.h:
-            raise RuntimeError("rtlws_anylen_open failed: %s" % anylen_last_error())
-
-    @property
-    def workspace_bytes(self):
-        return anylen_lib().rtlws_anylen_workspace_bytes(self.h)
-
-    def run(self, d_in, nframes, d_out, stream=None, check=True):
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = anylen_lib().rtlws_anylen_run(self.h, ptr(d_in), int(nframes), ptr(d_out), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_anylen_run failed (rc=%d): %s" % (rc, anylen_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            anylen_lib().rtlws_anylen_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DdcPlan:
-    """rtlws_ddc_plan* of include/rtlws_ddc.h: the phasor table on the engine's device, the kernels loaded.  eng may
-    be None (as a C caller's NULL engine): open then fails with the library's text."""
-
-    def __init__(self, eng):
-        self.eng = eng
-        self.h = ddc_lib().rtlws_ddc_open(eng.h if eng is not None else None)
-        if not self.h:
-            raise RuntimeError("rtlws_ddc_open failed: %s" % ddc_last_error())
-
-    @classmethod
-    def open(cls, eng):
-        return cls(eng)
-
-    def run(self, cic_r, d_iq, dec_len, tuning_words, d_out, out_stride=None, first_dec_index=0, stream=None, check=True):
-        """One launch: channel c of the bank is the cmplx_s32 stream at d_out + c * out_stride samples."""
-        words = (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = ddc_lib().rtlws_ddc_run(self.h, int(cic_r), ptr(d_iq), int(dec_len), int(first_dec_index), len(tuning_words),
-                                     words, ptr(d_out), int(dec_len if out_stride is None else out_stride), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_ddc_run failed (rc=%d): %s" % (rc, ddc_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            ddc_lib().rtlws_ddc_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DdcFirPlan:
-    """rtlws_ddcfir_plan* of include/rtlws_ddcfir.h: the taps and the phasor table on the engine's device, the kernel of
-    (decim, ntaps) loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
-
-    def __init__(self, eng, decim, taps):
-        self.eng = eng
-        self.decim = int(decim)
-        self.taps = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
-        self.ntaps = 0 if self.taps is None else self.taps.size
-        self.h = ddcfir_lib().rtlws_ddcfir_open(eng.h if eng is not None else None, self.decim, self.ntaps,
-                                                None if self.taps is None else _p(self.taps))
-        if not self.h:
-            raise RuntimeError("rtlws_ddcfir_open failed: %s" % ddcfir_last_error())
-
-    @classmethod
-    def open(cls, eng, decim, taps):
-        return cls(eng, decim, taps)
-
-    def run(self, d_iq, dec_len, tuning_words, d_out, out_shift=14, out_stride=None, first_dec_index=0, stream=None, check=True):
-        """One launch: channel c of the bank is the cmplx_s32 stream at d_out + c * out_stride samples."""
-        words = (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        rc = ddcfir_lib().rtlws_ddcfir_run(self.h, ptr(d_iq), int(dec_len), int(first_dec_index), len(tuning_words), words,
-                                           int(out_shift), ptr(d_out), int(dec_len if out_stride is None else out_stride), stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_ddcfir_run failed (rc=%d): %s" % (rc, ddcfir_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            ddcfir_lib().rtlws_ddcfir_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _PolyphasePlan:
-    """What the plans of the polyphase family share (include/rtlws_pfb.h and the headers on top of it): the prototype
-    (int16 [T * M]) and the transform's table on the engine's device, the kernels loaded.  eng may be None (as a C
-    caller's NULL engine): open then fails with the library's text.  A subclass names its library (_name, _lib), hands
-    __init__ what its open takes behind the taps, and keeps its run signatures."""
+class _Plan:
+    """What every satellite library's plan shares: the library (_name, _lib), the handle h of rtlws_<name>_open, the
+    calls through it, close.  eng may be None (as a C caller's NULL engine): open then fails with the library's text.
+    A subclass names its library, hands _open what its open takes behind the engine, and keeps its run signatures."""
     _name, _lib, h = None, None, None
 
-    def __init__(self, eng, log2_channels, taps, *counts):
-        """counts: what the library's open takes behind the taps (none, ninputs, or ninputs and nbeams)."""
+    def _open(self, eng, *args):
         self.eng = eng
-        self.log2_channels = int(log2_channels)
-        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
-        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
-        if m == 0 or taps.size == 0 or taps.size % m:
-            raise RuntimeError("rtlws_%s_open: the prototype holds taps_per_branch * M taps" % self._name)
-        self.taps_per_branch = taps.size // m
-        self.h = self._fn("open")(eng.h if eng is not None else None, self.log2_channels, self.taps_per_branch, _p(taps), *counts)
+        self.h = self._fn("open")(eng.h if eng is not None else None, *args)
         if not self.h:
             raise RuntimeError("rtlws_%s_open failed: %s" % (self._name, self._fn("last_error")().decode()))
 
@@ -991,6 +837,107 @@ class _PolyphasePlan:
             self.close()
         except Exception:
             pass
+
+
+def _words(tuning_words):
+    """The tuning words as a C array of int (never empty: a NULL array is not what an empty list means)."""
+    return (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
+
+
+class _FramesPlan(_Plan):
+    """The plans of one descriptor (include/rtlws_long.h, include/rtlws_anylen.h): the same open, workspace and run."""
+
+    def __init__(self, eng, desc, max_frames=1):
+        self.desc = desc
+        self._open(eng, C.byref(desc), int(max_frames))
+
+    @property
+    def workspace_bytes(self):
+        return self._fn("workspace_bytes")(self.h)
+
+    def run(self, d_in, nframes, d_out, stream=None, check=True):
+        return self._call("run", check, self._ptr(d_in), int(nframes), self._ptr(d_out), stream)
+
+
+class LongPlan(_FramesPlan):
+    """rtlws_long_plan* of include/rtlws_long.h: one descriptor, tables and workspace for up to max_frames frames
+    per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "long", staticmethod(long_lib)
+
+
+def long_supported(desc):
+    return long_lib().rtlws_long_supported(C.byref(desc))
+
+
+class AnyLenPlan(_FramesPlan):
+    """rtlws_anylen_plan* of include/rtlws_anylen.h: one descriptor, tables and workspaces for up to max_frames
+    frames per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "anylen", staticmethod(anylen_lib)
+
+
+class DdcPlan(_Plan):
+    """rtlws_ddc_plan* of include/rtlws_ddc.h: the phasor table on the engine's device, the kernels loaded.  eng may
+    be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "ddc", staticmethod(ddc_lib)
+
+    def __init__(self, eng):
+        self._open(eng)
+
+    def run(self, cic_r, d_iq, dec_len, tuning_words, d_out, out_stride=None, first_dec_index=0, stream=None, check=True):
+        """One launch: channel c of the bank is the cmplx_s32 stream at d_out + c * out_stride samples."""
+        return self._call("run", check, int(cic_r), self._ptr(d_iq), int(dec_len), int(first_dec_index), len(tuning_words),
+                          _words(tuning_words), self._ptr(d_out), int(dec_len if out_stride is None else out_stride), stream)
+
+
+class DdcFirPlan(_Plan):
+    """rtlws_ddcfir_plan* of include/rtlws_ddcfir.h: the taps and the phasor table on the engine's device, the kernel of
+    (decim, ntaps) loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "ddcfir", staticmethod(ddcfir_lib)
+
+    def __init__(self, eng, decim, taps):
+        self.decim = int(decim)
+        self.taps = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        self.ntaps = 0 if self.taps is None else self.taps.size
+        self._open(eng, self.decim, self.ntaps, None if self.taps is None else _p(self.taps))
+
+    def run(self, d_iq, dec_len, tuning_words, d_out, out_shift=14, out_stride=None, first_dec_index=0, stream=None, check=True):
+        """One launch: channel c of the bank is the cmplx_s32 stream at d_out + c * out_stride samples."""
+        return self._call("run", check, self._ptr(d_iq), int(dec_len), int(first_dec_index), len(tuning_words),
+                          _words(tuning_words), int(out_shift), self._ptr(d_out),
+                          int(dec_len if out_stride is None else out_stride), stream)
+
+
+class FmBankPlan(_Plan):
+    """rtlws_fmbank_plan* of include/rtlws_fmbank.h: the phasor table on the engine's device, the kernels loaded.  eng
+    may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "fmbank", staticmethod(fmbank_lib)
+
+    def __init__(self, eng):
+        self._open(eng)
+
+    def run(self, cic_r, d_iq, block_len, nblocks, tuning_words, d_state_in, d_state_out, d_audio, audio_stride=None,
+            first_dec_index=0, stream=None, check=True):
+        """One launch: audio of channel c at d_audio + c * audio_stride floats, states channel-major [C, 21]."""
+        stride = int(nblocks) * (int(block_len) // 4) if audio_stride is None else int(audio_stride)
+        return self._call("run", check, int(cic_r), self._ptr(d_iq), int(block_len), int(nblocks), int(first_dec_index),
+                          len(tuning_words), _words(tuning_words), self._ptr(d_state_in), self._ptr(d_state_out),
+                          self._ptr(d_audio), stride, stream)
+
+
+class _PolyphasePlan(_Plan):
+    """What the plans of the polyphase family add (include/rtlws_pfb.h and the headers on top of it): the prototype
+    (int16 [T * M]) and the transform's table on the engine's device, the kernels loaded.  A subclass hands __init__
+    what its open takes behind the taps."""
+
+    def __init__(self, eng, log2_channels, taps, *counts):
+        """counts: what the library's open takes behind the taps (none, ninputs, or ninputs and nbeams)."""
+        self.log2_channels = int(log2_channels)
+        taps = np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        m = 1 << self.log2_channels if 0 <= self.log2_channels < 31 else 0
+        if m == 0 or taps.size == 0 or taps.size % m:
+            raise RuntimeError("rtlws_%s_open: the prototype holds taps_per_branch * M taps" % self._name)
+        self.taps_per_branch = taps.size // m
+        self._open(eng, self.log2_channels, self.taps_per_branch, _p(taps), *counts)
 
 
 class PfbSpecPlan(_PolyphasePlan):
@@ -1103,45 +1050,6 @@ class PfbPlan(_PolyphasePlan):
             out_stride = m if lay == PFB_TIME_MAJOR else nframes
         return self._call("run", check, self._ptr(d_iq), int(nframes), int(m if hop is None else hop), int(first_frame_index),
                           int(lay), self._ptr(d_out), int(out_stride), stream)
-
-
-class FmBankPlan:
-    """rtlws_fmbank_plan* of include/rtlws_fmbank.h: the phasor table on the engine's device, the kernels loaded.  eng
-    may be None (as a C caller's NULL engine): open then fails with the library's text."""
-
-    def __init__(self, eng):
-        self.eng = eng
-        self.h = fmbank_lib().rtlws_fmbank_open(eng.h if eng is not None else None)
-        if not self.h:
-            raise RuntimeError("rtlws_fmbank_open failed: %s" % fmbank_last_error())
-
-    @classmethod
-    def open(cls, eng):
-        return cls(eng)
-
-    def run(self, cic_r, d_iq, block_len, nblocks, tuning_words, d_state_in, d_state_out, d_audio, audio_stride=None,
-            first_dec_index=0, stream=None, check=True):
-        """One launch: audio of channel c at d_audio + c * audio_stride floats, states channel-major [C, 21]."""
-        words = (C.c_int * max(len(tuning_words), 1))(*[int(k) for k in tuning_words])
-        ptr = lambda x: None if x is None else Engine._ptr(x)
-        stride = int(nblocks) * (int(block_len) // 4) if audio_stride is None else int(audio_stride)
-        rc = fmbank_lib().rtlws_fmbank_run(self.h, int(cic_r), ptr(d_iq), int(block_len), int(nblocks), int(first_dec_index),
-                                           len(tuning_words), words, ptr(d_state_in), ptr(d_state_out), ptr(d_audio),
-                                           stride, stream)
-        if check and rc != 0:
-            raise RuntimeError("rtlws_fmbank_run failed (rc=%d): %s" % (rc, fmbank_last_error()))
-        return rc
-
-    def close(self):
-        if self.h:
-            fmbank_lib().rtlws_fmbank_close(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def anylen_supported(desc):

@@ -121,11 +121,15 @@ def test_fmbank_refusals_need_no_gpu(built):
 
 
 def test_one_table_builder_and_it_equals_numpy(built, tmp_path):
-    """rtl-ws_amd/csrc/ddc_table.h is the only builder of the phasor table: both libraries' glue calls it, it is
-    compiled here on its own and gives tests/ddc_ref.py's table, as rtlws_ddc_table does."""
+    """rtl-ws_amd/csrc/ddc_table.h is the only builder of the phasor table: both libraries' glue calls it -- through
+    the one open of csrc/ddc_plan.h --, it is compiled here on its own and gives tests/ddc_ref.py's table, as
+    rtlws_ddc_table does."""
+    plan = open(os.path.join(CSRC, "ddc_plan.h")).read()
+    assert '#include "ddc_table.h"' in plan and "build_table(host.data(), P)" in plan
+    assert "lrint" not in plan and "std::cos" not in plan
     for shim in ("ddc_shim.hip", "fmbank_shim.hip"):
         txt = open(os.path.join(CSRC, shim)).read()
-        assert '#include "ddc_table.h"' in txt and "build_table(host.data(), P)" in txt, shim
+        assert '#include "ddc_plan.h"' in txt and "open_plan<rtlws_" in txt, shim
         assert "lrint" not in txt and "std::cos" not in txt, shim
     src = tmp_path / "table.cpp"
     src.write_text('#include "ddc_table.h"\nextern "C" void table(short* t, int p) { rtlws::ddc::build_table(t, p); }\n')
