@@ -201,7 +201,7 @@ typedef struct rtlws_spectra_desc {
  * stream's chunks with rtlws_spectra_batch_f64 -- the reference's own precision for a live
  * sensor (src/signal_source.c:29-35 -> src/cbb_main.c:52-59).  Rows are then doubles, or floats
  * with RTLWS_FLAG_ROWS_F32 as well.  Ignored by rtlws_spectra_batch / rtlws_spectra_batch_f64,
- * where the function called IS the choice. */
+ * where the function called IS the choice; rtlws_spectra_grid reads it the same way (whose grid to report). */
 #define RTLWS_FLAG_F64 2
 
 /* Precision: f32 arithmetic (inputs are exact in f32; twiddles are f64-computed and
@@ -313,7 +313,9 @@ int rtlws_clock_stamp(rtlws_engine* e, unsigned long long* d_out, int slots, voi
 int rtlws_copy_d2d(rtlws_engine* e, void* dst_dev, const void* src_dev, size_t bytes, void* stream);
 
 /* Bytes of LDS, VGPR count etc. are in DESIGN.md; this returns the grid the
- * fused kernel would launch for a descriptor and nframes (for tests). */
+ * fused kernel would launch for a descriptor and nframes (for tests).  With RTLWS_FLAG_F64 in desc->flags:
+ * the grid rtlws_spectra_batch_f64 launches for 16-byte aligned buffers (blocks and threads; *lds_bytes is 0,
+ * the f64 kernels' launch tables hold their LDS sizes). */
 int rtlws_spectra_grid(rtlws_engine* e, const rtlws_spectra_desc* desc, long nframes,
                        int* blocks, int* threads, int* lds_bytes);
 

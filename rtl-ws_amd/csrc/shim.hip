@@ -600,6 +600,14 @@ int rtlws_spectra_grid(rtlws_engine* e, const rtlws_spectra_desc* d, long nframe
                        int* threads, int* lds_bytes)
 {
     if (!e || !desc_ok(d) || nframes < 0 || nframes % d->k_avg) return -1;
+    if (d->flags & RTLWS_FLAG_F64) {   // rtlws_spectra_batch_f64's plan, for 16-byte aligned buffers
+        const long ngroups = nframes / d->k_avg;
+        const PlanF64 k = plan_f64(e, d, ngroups, nullptr, nullptr);
+        if (blocks) *blocks = k.fused ? (k.blocks < 1 ? 1 : k.blocks) : (int)ngroups;
+        if (threads) *threads = !k.fused ? 256 : k.x1024 ? 64 * k.waves : d->n_fft / 16;
+        if (lds_bytes) *lds_bytes = 0;   // held by the kernels' own launch tables
+        return 0;
+    }
     const PlanF32 k = plan_f32(e, d, nframes / d->k_avg);
     if (blocks) *blocks = k.blocks;
     if (threads) *threads = k.threads;

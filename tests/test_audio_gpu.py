@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import persistent_trips as pt
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -60,6 +61,52 @@ def test_fm_demod_kernel_vs_oracle(engine, oracle, built):
     assert carry[1] == np.float32(prev)
     # in == out pointer is refused
     assert built.hip_lib().rtlws_fm_demod(engine.h, d_iq.ptr, n, d_prev.ptr, d_prev.ptr, d_out.ptr, None) == -1
+
+
+def _fm_edge_samples(rng, n):
+    """n samples (n a multiple of 16) of the inputs atan2_approx branches on: full-range int32 (above 2^24 the
+    conversion to f32 rounds; INT32_MIN and INT32_MAX in every pairing), |y| == |x| in the four quadrants, the four
+    half-axes and (0, 0), at small and at full-range magnitudes."""
+    lo, hi = -2 ** 31, 2 ** 31 - 1
+    out = rng.integers(lo, hi, size=(n, 2), dtype=np.int64, endpoint=True)
+    v = np.where(rng.random(n) < 0.5, rng.integers(1, 3000, n), rng.integers(2 ** 24, hi, n, endpoint=True))
+    kind = np.arange(n) % 16
+    for k, (sx, sy) in enumerate([(1, 1), (-1, 1), (-1, -1), (1, -1), (1, 0), (-1, 0), (0, 1), (0, -1), (0, 0)]):
+        out[kind == k] = np.stack([sx * v, sy * v], axis=1)[kind == k]
+    ext = [(lo, lo), (lo, hi), (hi, lo), (hi, hi), (lo, 0), (0, lo), (hi, 0), (0, hi), (lo, -hi), (-hi, lo)]
+    out[9::16][:len(ext)] = ext                         # kinds 9 .. 15 stay full-range random
+    return out.astype(np.int32)
+
+
+def test_fm_demod_kernel_past_the_grid_cap(engine, oracle, built):
+    """fm_demod_kernel's grid-stride loop: two whole trips of its capped grid (cu_count * 8 workgroups of 256), then a
+    ragged third.  A thread recomputes its left neighbour's phase, so stretches of edge inputs lie across both trip
+    borders (indices k * stride - 1 and k * stride belong to different trips of different threads), at the start, in
+    the middle of a trip and at the ragged end."""
+    cus = engine.get_option("cu_count")
+    stride = cus * 8 * 256
+    n = pt.stride_len(cus)
+    assert 2 * stride < n < 3 * stride and n % 256
+    rng = np.random.default_rng(120)
+    iq = rng.integers(-3000, 3000, size=(n, 2), dtype=np.int32)
+    iq[rng.integers(0, n, 2000), 0] = 0                      # x == 0 branches
+    iq[rng.integers(0, n, 2000), 1] = 0
+    for at in (0, stride // 2, stride - 1024, 2 * stride - 1024, n - 2048):
+        iq[at:at + 2048] = _fm_edge_samples(rng, 2048)
+    for k in (1, 2):
+        iq[k * stride - 1], iq[k * stride] = (-2 ** 31, 2 ** 31 - 1), (2 ** 31 - 1, -2 ** 31)
+    d_iq = engine.upload(iq)
+    d_prev = engine.upload(np.array([0.25, 0.0], dtype=np.float32))
+    d_out = engine.alloc(n * 4)
+    rc = built.hip_lib().rtlws_fm_demod(engine.h, d_iq.ptr, n, d_prev.ptr, d_prev.ptr + 4, d_out.ptr, None)
+    assert rc == 0, built.last_error()
+    got = engine.download(d_out, np.float32, (n,))
+    carry = engine.download(d_prev, np.float32, (2,))
+    want, prev = oracle.fm_demod(iq, prev_phase=0.25)
+    bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
+    assert bad.size == 0, "%d outputs differ, first %d (trip %d): %r, want %r, samples %s %s" % (
+        bad.size, bad[0], bad[0] // stride, got[bad[0]], want[bad[0]], iq[max(bad[0] - 1, 0)], iq[bad[0]])
+    assert carry[0] == np.float32(0.25) and carry[1] == np.float32(prev)
 
 
 def test_decimator_to_audio_pipeline(built, oracle):

@@ -9,14 +9,23 @@ the library's code objects.  Here each case runs under the engine options it nam
   2  a pure tone: the widest dynamic range;
   3  tone + noise at K = 1, uniform bytes (full-range int32, Gaussian f32) at K > 1.
 Bounds are the ones the rest of the suite holds each path to (tests/helpers.py).  The test is parametrized by
-kernel family and N; a failure lists the instantiation and descriptor of every case that broke."""
+kernel family and N; a failure lists the instantiation and descriptor of every case that broke.
+
+Four rows are one trip of a persistent kernel's row loop.  test_every_persistent_instantiation_past_its_grid_cap runs
+every persistent case again with its grid pinned at one workgroup per CU and 2 * cu_count + 19 rows (three trips for
+the first 19 workgroups, two for the rest, a ragged end), each row a copy of one of the four above, placed so that a
+workgroup that fetches, keeps or stores a wrong row on a later trip shows (tests/persistent_trips.py).  A row depends on
+its own K frames only and every trip runs the same instructions, so the long batch must repeat the four-row launch
+bit for bit; the four-row launch is held to the oracle as above."""
 import contextlib
+import functools
 import zlib
 
 import numpy as np
 import pytest
 
 import kernel_matrix as km
+import persistent_trips as pt
 from helpers import rel_err, eps_for, f32_db_bad, f32_payload_bad, EPS_K1, EPS_STRICT, TOL, TOL_F64
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +34,16 @@ ONE_F32_ROUNDING = 2.0 ** -24 * 1.001         # half an ulp, relative
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
+@functools.lru_cache(maxsize=None)
 def _frames(c):
-    """The case's input (ROWS * K frames, row-major by row) and the oracle's f64 rows of K-frame sums."""
+    """The case's input (ROWS * K frames, row-major by row) and the oracle's f64 rows of K-frame sums: made once per
+    case, shared by the tests of this module, read-only."""
+    data, ref = _make_frames(c)
+    data.flags.writeable = ref.flags.writeable = False
+    return data, ref
+
+
+def _make_frames(c):
     from oracle import pyoracle as po
     from rtlws import synth
     K, N = c.K, c.N
@@ -196,6 +213,106 @@ def test_every_instantiation_against_the_oracle(engine, built, fam):
         assert got.shape == (ROWS, c.N), c.label()
         bad = _check_f64(engine, c, data, got, ref) if c.f64 else _check_f32(engine, built, c, got, ref)
         failures += ["%s%s [%s]: %s" % (km.instantiation(c)[0], km.instantiation(c)[1], c.label(), b) for b in bad]
+    assert not failures, "\n".join(failures)
+
+
+def _pool(c, P):
+    """_frames(c), and for P > ROWS (spectra_f64_1024x at eight wavefronts per workgroup, cmplx_u8 frames without a
+    CIC factor or window) P - ROWS more row groups, tone + noise and uniform bytes in turn, with the oracle's rows."""
+    data, ref = _frames(c)
+    if P <= ROWS:
+        return data, ref
+    from oracle import pyoracle as po
+    from rtlws import synth
+    assert c.input == "cu8" and c.cic_r <= 1 and c.window == "rect"
+    seed = zlib.crc32((c.label() + " pool").encode()) % (1 << 30)
+    extra = np.concatenate([(synth.uniform_iq if i % 2 else synth.tone_noise_iq)(c.K, c.N, seed=seed + i)
+                            for i in range(P - ROWS)])
+    return np.concatenate([data, extra]), np.concatenate([ref, po.batch_spectra_u8(extra, c.N, K=c.K)])
+
+
+def _out_dtype(c):
+    return np.uint8 if c.output == "payload_u8" else np.float64 if (c.f64 and not c.rows_f32) else np.float32
+
+
+def _desc(built, c, grid=False):
+    """The case's descriptor; grid: as rtlws_spectra_grid takes it (RTLWS_FLAG_F64 names the f64 entry point's plan)."""
+    flags = (built.FLAG_ROWS_F32 if c.f64 and c.rows_f32 else 0) | (built.FLAG_F64 if c.f64 and grid else 0)
+    return built.make_desc(c.N, c.K, c.input, c.window, c.output, c.cic_r, c.gain_db, flags)
+
+
+def _run_gathered(engine, built, c, pool, pm):
+    """The batch whose row g is a copy of the pool's row group pm[g], gathered on the device from the uploaded pool
+    (runs of consecutive pool rows in one copy), launched under the options in force."""
+    pool = np.ascontiguousarray(pool)
+    rows, row_in = len(pm), pool.nbytes // (pool.shape[0] // c.K)
+    dt = _out_dtype(c)
+    d_pool, d_in = engine.upload(pool), engine.alloc(rows * row_in)
+    d_out = engine.alloc(rows * c.N * np.dtype(dt).itemsize)
+    try:
+        g = 0
+        while g < rows:
+            n = 1
+            while g + n < rows and pm[g + n] == pm[g + n - 1] + 1:
+                n += 1
+            rc = built.hip_lib().rtlws_copy_d2d(engine.h, d_in.ptr + g * row_in, d_pool.ptr + pm[g] * row_in, n * row_in,
+                                                None)
+            assert rc == 0, built.last_error()
+            g += n
+        (engine.spectra_batch_f64 if c.f64 else engine.spectra_batch)(_desc(built, c), d_in, rows * c.K, d_out)
+        return engine.download(d_out, dt, (rows, c.N))
+    finally:
+        for b in (d_pool, d_in, d_out):
+            b.free()
+
+
+def _first_difference(big, small, pm, blocks):
+    """None where big[g] is small[pm[g]] bit for bit for every row g, else where it first is not."""
+    u = {1: np.uint8, 4: np.uint32, 8: np.uint64}[big.dtype.itemsize]
+    neq = big.view(u) != small.view(u)[pm]
+    if not neq.any():
+        return None
+    g = int(np.argmax(neq.any(axis=1)))
+    k = int(np.argmax(neq[g]))
+    return "%d of %d rows differ from the one-trip launch; first row %d (trip %d of workgroup %d, pool row %d) at bin %d: " \
+           "%r, one-trip launch %r" % (int(neq.any(axis=1).sum()), len(pm), g, g // blocks, g % blocks, pm[g], k, big[g, k],
+                                       small[pm[g], k])
+
+
+@pytest.mark.parametrize("fam", pt.FAMILIES)
+def test_every_persistent_instantiation_past_its_grid_cap(engine, built, fam):
+    cus = engine.get_option("cu_count")
+    failures, shapes = [], set()
+    cases = [c for c in _cases(fam) if pt.persistent(c)]
+    assert cases and len(cases) == sum(1 for c in pt.CASES if km.family(c) == fam)
+    for c in cases:
+        inst = "%s%s [%s]" % (km.instantiation(c)[0], km.instantiation(c)[1], c.label())
+        x8 = pt.is_x8(c)
+        rows = pt.x8_rows_for(cus) if x8 else pt.rows_for(cus)
+        with contextlib.ExitStack() as st:
+            for name, value in c.opts + (pt.pin_option(c),):
+                st.enter_context(engine.option(name, value))
+            # the grid is what the test says it is: one workgroup per CU, and rows for a second and a third trip
+            rc, blocks, _, _ = engine.grid(_desc(built, c, grid=True), rows * c.K)
+            assert rc == 0 and blocks == cus, (inst, rc, blocks, cus)
+            assert rows >= 2 * blocks + 1 and -(-rows // blocks) >= 3, (inst, rows, blocks)
+            if x8:   # rows are dealt through the LDS counter after the first eight: every workgroup gets there
+                assert rows // blocks > pt.X_STATIC_ROWS, (inst, rows, blocks)
+                pm, P = pt.x8_pool_map(blocks, rows)
+            else:
+                pm, P = pt.pool_map(blocks, rows), ROWS
+            shapes.add((blocks, rows, -(-rows // blocks), rows // blocks))
+            data, ref = _pool(c, P)
+            small = _run(engine, c, data)               # at most one trip per workgroup
+            assert small.shape == (P, c.N), inst
+            bad = _check_f64(engine, c, data, small, ref) if c.f64 else _check_f32(engine, built, c, small, ref)
+            if len({r.tobytes() for r in small}) != P:   # else a row taken for another could go unseen
+                bad.append("the pool's %d output rows are not pairwise different" % P)
+            big = _run_gathered(engine, built, c, data, pm)
+            diff = _first_difference(big, small, pm, blocks)
+        failures += ["%s: %s" % (inst, b) for b in bad + ([diff] if diff else [])]
+    print("%s: %d cases, each at %s (workgroups, rows, most and fewest trips of a workgroup)" % (
+        fam, len(cases), sorted(shapes)))
     assert not failures, "\n".join(failures)
 
 
