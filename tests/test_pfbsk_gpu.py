@@ -4,7 +4,9 @@ The two sums of a sub-integration are held to the bit: S1 to rtlws_pfbspec_run's
 pfbxc_ref.ordered_sums of fl(p p) formed in numpy f32 from rtlws_pfb_run's own download of the same capture.  The
 decision, the clean sum and the counts are held to the bit to their restatement in numpy f32 (tests/pfbsk_ref.py) on the
 device's own S1 and S2 rows.  Against the f64 definition stand the semantic case (flags away from the bounds, the
-derived bound of the clean row) and the dB rows.  Random bytes and random int16 taps unless said otherwise."""
+derived bound of the clean row) and the dB rows.  The walk of a row's L sub-integrations through its tiles is held to
+the same bits at every step geometry of tests/pfbsk_walk_cases.py.  Random bytes and random int16 taps unless said
+otherwise."""
 import ctypes as C
 import math
 
@@ -14,6 +16,7 @@ import pytest
 import pfb_ksum_cases as ksum
 import pfb_ref
 import pfbsk_ref
+import pfbsk_walk_cases as walks
 import pfbspec_ref
 import pfbxc_ref
 from test_pfb_ksum_gpu import Rig, first_difference, u32
@@ -119,6 +122,34 @@ def test_every_sum_geometry_to_the_bit(engine, built, k):
                 f, g = check_sums_and_decisions(rig, built, k, K, NSUB, n, D, y, d_mid)
                 flagged, keptn = flagged + f, keptn + g
             print("pfbsk, M = %d, hop %d: %d sub-integrations flagged, %d kept (K = %s)" % (M, D, flagged, keptn, [K for K, _ in todo]))
+            assert flagged > 0 and keptn > 0, (k, D, flagged, keptn)              # both outcomes occur
+    finally:
+        rig.close()
+
+
+@pytest.mark.parametrize("k", ksum.LOG2_MS)
+def test_every_walk_geometry_to_the_bit(engine, built, k):
+    """Every (K, L) of tests/pfbsk_walk_cases.py, both hops, T = 3, three rows: the same checks at every walk of a row's
+    L sub-integrations through its tiles (one partial step up to the last item short of a full tile, a full step, two
+    and three steps with a full and with a ragged last one; L = 1 and 2 where a step holds one sub-integration).  The
+    capture is as long as the longest case needs at hop M, so that run reads it to its last sample."""
+    M = 1 << k
+    cases, n = walks.walk_cases(k), walks.ROWS
+    for K, L in cases:
+        rc, blocks, _, _, per = built.pfbsk_grid(k, T, M, K, L, 1)
+        assert rc == 0 and per >= 1 and blocks == 1 and built.pfbsk_supported(k, T, M // 2, K, L) == 1
+    longest = max(walks.frames(K, L) for K, L in cases)
+    rig = SkRig(engine, built, k, longest, n, max(n * L for _, L in cases))
+    try:
+        assert any(len(rig.iqs[0]) == pfbsk_ref.samples_needed(M, T, M, K, L, n) for K, L in cases)
+        for D in (M, M // 2):
+            y = rig.frames(0, longest, D)
+            d_mid = rig.upload(np.full((pfb_ref.samples_needed(M, T, D, longest), 2), 128, dtype=np.uint8))
+            flagged = keptn = 0
+            for K, L in cases:
+                f, g = check_sums_and_decisions(rig, built, k, K, L, n, D, y, d_mid)
+                flagged, keptn = flagged + f, keptn + g
+            print("pfbsk walks, M = %d, hop %d: %d (K, L), %d sub-integrations flagged, %d kept" % (M, D, len(cases), flagged, keptn))
             assert flagged > 0 and keptn > 0, (k, D, flagged, keptn)              # both outcomes occur
     finally:
         rig.close()
