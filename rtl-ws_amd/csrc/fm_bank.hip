@@ -11,65 +11,19 @@
 // LDS.  Stages B - D are fm_chain.hip's, with the index arithmetic of a stream position done once for the eight
 // channels.  Per column tile one more workgroup, the last, does the same for the few samples behind the tails of the
 // three streams and writes state_out; state_in and state_out differ, so there is no ordering between workgroups.
+// The pieces that fmfir_bank.hip compiles too are fm_bank_stages.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ddc_ops.h"
 #include "fm_bank.h"
-#include "fm_maps.h"
-#include "fm_math.h"
+#include "fm_bank_stages.h"
 #include "rtlws_internal.h"
 
 namespace rtlws {
 namespace fmbank {
 
-using ddc::v4i;
-
 constexpr int GROUP = 4;                  // row tiles of a wavefront whose loads are in flight together
-
-__device__ __forceinline__ float* phase_of_ch(float* lds, int ch) { return lds + ch * PHASE_CAP; }
-__device__ __forceinline__ float* s1_of_ch(float* lds, int ch) { return lds + COL_CH * PHASE_CAP + ch * S1_CAP; }
-
-// What the workgroup behind the last tile needs: the last ten positions of the stage-2 stream (all in the last
-// block: 2 quarter >= 10), the stage-1 stream from the delay line of the first of them to its end, the samples
-// under that to the last one.  At most 34 stage-1 positions and 40 phases.
-__device__ __forceinline__ fm::TileRange tail_range(const fm::Maps& m)
-{
-    fm::TileRange r;
-    const long n2_all = m.nblocks * m.L2, n1_all = m.nblocks * m.L1;
-    r.a0 = 0;
-    r.na = 0;
-    r.s2lo = n2_all - 10;
-    r.n2 = 10;
-    r.wlo = m.s2_to_w(r.s2lo);
-    r.whi = m.s2_to_w(n2_all - 1);
-    r.s1lo = 2 * r.wlo - 10;
-    r.n1 = (int)(n1_all - r.s1lo);
-    r.glo = m.s1_to_g(r.s1lo < 0 ? 0 : r.s1lo);
-    r.ghi = m.nblocks * m.L - 1;
-    r.np = (int)(r.ghi - r.glo) + 2;
-    return r;
-}
-
-// This lane's two channels c0, c0 + 1 of decimated sample g, phase index idx: the block phasor (its table entry e),
-// the conversion, the phase.  Sample -1 is the carried phase.
-__device__ __forceinline__ void emit_phase(const BankParams& p, float* ph, v4i hi, v4i lo, int c0, const uint32_t (&e)[2],
-                                           long g, int idx)
-{
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (c0 + h >= p.nch) continue;
-        float v;
-        if (g < 0) {
-            v = p.state_in[(c0 + h) * STATE];
-        } else {
-            const int2 ph_blk = make_int2((int)(int16_t)(e[h] & 0xffffu), (int)e[h] >> 16);
-            const int2 s = ddc::rotate(ddc::inner_sum(hi[2 * h], lo[2 * h]), ddc::inner_sum(hi[2 * h + 1], lo[2 * h + 1]), ph_blk);
-            v = atan2_approx_dev((float)s.y, (float)s.x);
-        }
-        ph[h * PHASE_CAP + idx] = v;
-    }
-}
 
 // A. the phases of decimated samples glo - 1 .. glo - 2 + np of the column tile's channels into LDS.
 // RT = 8, 10, 12: that factor, one K step, the phasor operands in registers.  RT = 0: any factor 1 .. 128, the
@@ -163,14 +117,6 @@ __device__ __forceinline__ void stage1(const BankParams& p, const fm::Maps& m, c
     }
 }
 
-// One output of the first half-band from a channel's stage-1 arrays: output w sits at stage-1 position
-// 2 w = s1lo + 2 k with k = w - wlo + 5 (fm_chain.hip, stage C)
-__device__ __forceinline__ float work_at(const float* s1e, int k)
-{
-    const float* s1o = s1e + S1_HALF;
-    return halfband_dev(s1o[k - 3], s1e[k], s1e[k - 1], s1e[k - 2], s1e[k - 3], s1e[k - 4], s1e[k - 5]);
-}
-
 template <int RT>
 __global__ __launch_bounds__(THREADS) void fm_bank_kernel(const BankParams p)
 {
@@ -234,12 +180,6 @@ __global__ __launch_bounds__(THREADS) void fm_bank_kernel(const BankParams p)
                 halfband_dev(s2o[k - 3], s2e[k], s2e[k - 1], s2e[k - 2], s2e[k - 3], s2e[k - 4], s2e[k - 5]);
         }
     }
-}
-
-__global__ __launch_bounds__(THREADS) void fm_bank_state_copy_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                      int nfloats)
-{
-    for (int i = threadIdx.x; i < nfloats; i += THREADS) out[i] = in[i];
 }
 
 // the launch table: f is handed the instantiation of cic_r (pick) or every instantiation in turn (visit_all)

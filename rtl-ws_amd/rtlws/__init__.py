@@ -12,6 +12,7 @@ fail loudly.
   DdcPlan, Engine.ddc  include/rtlws_ddc.h (tuned channels from one capture: integer mixer + CIC in one launch)
   DdcFirPlan, Engine.ddcfir  include/rtlws_ddcfir.h (tuned channels with an int16 FIR of up to 256 taps as the channel filter, one launch)
   FmBankPlan, Engine.fm_bank  include/rtlws_fmbank.h (up to 32 FM stations from one capture in one launch)
+  FmFirPlan, Engine.fm_fir_bank  include/rtlws_fmfir.h (those stations behind an int16 FIR of up to 256 taps, one launch)
   PfbPlan, Engine.pfb  include/rtlws_pfb.h (polyphase channelizer: all 2^k channels of one capture in one launch)
   PfbSpecPlan, Engine.pfbspec  include/rtlws_pfbspec.h (polyphase spectrometer: K-frame power of all 2^k channels in one launch)
   PfbXcPlan, Engine.pfbxc  include/rtlws_pfbxc.h (polyphase cross-correlator: K-frame powers and cross-spectra of 2-4 captures in one launch)
@@ -41,6 +42,7 @@ FM_LIB = os.path.join(LIB_DIR, "librtlws_fm.so")         # include/rtlws_fm.h
 DDC_LIB = os.path.join(LIB_DIR, "librtlws_ddc.so")       # include/rtlws_ddc.h
 FMBANK_LIB = os.path.join(LIB_DIR, "librtlws_fmbank.so") # include/rtlws_fmbank.h
 DDCFIR_LIB = os.path.join(LIB_DIR, "librtlws_ddcfir.so") # include/rtlws_ddcfir.h
+FMFIR_LIB = os.path.join(LIB_DIR, "librtlws_fmfir.so")   # include/rtlws_fmfir.h
 PFB_LIB = os.path.join(LIB_DIR, "librtlws_pfb.so")       # include/rtlws_pfb.h
 PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfbspec.h
 PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
@@ -117,6 +119,9 @@ DDCFIR_SYMBOLS = ["rtlws_ddcfir_supported", "rtlws_ddcfir_samples_needed", "rtlw
 DDCFIR_MAX_TAPS, DDCFIR_MAX_TAP, DDCFIR_MAX_SHIFT = 256, 32639, 30       # rtlws_ddcfir.h
 FMBANK_SYMBOLS = ["rtlws_fmbank_supported", "rtlws_fmbank_grid", "rtlws_fmbank_open", "rtlws_fmbank_run",
                   "rtlws_fmbank_close", "rtlws_fmbank_last_error"]
+FMFIR_SYMBOLS = ["rtlws_fmfir_supported", "rtlws_fmfir_samples_needed", "rtlws_fmfir_grid", "rtlws_fmfir_open",
+                 "rtlws_fmfir_run", "rtlws_fmfir_close", "rtlws_fmfir_last_error"]
+FMFIR_MAX_CHANNELS = 32                                                   # rtlws_fmfir.h
 FMBANK_MAX_CHANNELS = 32
 PFB_SYMBOLS = ["rtlws_pfb_supported", "rtlws_pfb_design", "rtlws_pfb_twiddles", "rtlws_pfb_samples_needed", "rtlws_pfb_grid",
                "rtlws_pfb_open", "rtlws_pfb_run", "rtlws_pfb_close", "rtlws_pfb_last_error"]
@@ -339,6 +344,18 @@ _FMBANK_PROTOTYPES = {
 def fmbank_lib():
     """librtlws_fmbank.so (include/rtlws_fmbank.h); it needs librtlws_hip.so's engine."""
     return _satellite(FMBANK_LIB, _FMBANK_PROTOTYPES)
+
+
+_FMFIR_PROTOTYPES = {
+    "rtlws_fmfir_supported": [_i, _i, _i, _i, _l], "rtlws_fmfir_samples_needed": ([_i, _i, _i, _l], _l),
+    "rtlws_fmfir_grid": [_i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_fmfir_open": ([_vp, _i, _i, _vp], _vp),
+    "rtlws_fmfir_run": [_vp, _vp, _i, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _vp], "rtlws_fmfir_close": ([_vp], None),
+    "rtlws_fmfir_last_error": ([], _str)}
+
+
+def fmfir_lib():
+    """librtlws_fmfir.so (include/rtlws_fmfir.h); it needs librtlws_hip.so's engine."""
+    return _satellite(FMFIR_LIB, _FMFIR_PROTOTYPES)
 
 
 def amd_lib():
@@ -722,6 +739,27 @@ def ddcfir_bound(taps, out_shift):
     return b.value
 
 
+def fmfir_last_error():
+    return fmfir_lib().rtlws_fmfir_last_error().decode()
+
+
+def fmfir_supported(decim, ntaps, nchannels=1, block_len=20, nblocks=1):
+    return fmfir_lib().rtlws_fmfir_supported(int(decim), int(ntaps), int(nchannels), int(block_len), int(nblocks))
+
+
+def fmfir_samples_needed(decim, ntaps, block_len, nblocks):
+    """rtlws_fmfir_samples_needed: (nblocks * block_len - 1) * decim + ntaps, 0 without blocks, or -1.  No GPU needed."""
+    return fmfir_lib().rtlws_fmfir_samples_needed(int(decim), int(ntaps), int(block_len), int(nblocks))
+
+
+def fmfir_grid(decim, ntaps, nchannels, block_len, nblocks):
+    """rtlws_fmfir_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
+    b, t, s, a = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+    rc = fmfir_lib().rtlws_fmfir_grid(int(decim), int(ntaps), int(nchannels), int(block_len), int(nblocks), C.byref(b),
+                                      C.byref(t), C.byref(s), C.byref(a))
+    return rc, b.value, t.value, s.value, a.value
+
+
 def fmbank_last_error():
     return fmbank_lib().rtlws_fmbank_last_error().decode()
 
@@ -922,6 +960,27 @@ class FmBankPlan(_Plan):
         return self._call("run", check, int(cic_r), self._ptr(d_iq), int(block_len), int(nblocks), int(first_dec_index),
                           len(tuning_words), _words(tuning_words), self._ptr(d_state_in), self._ptr(d_state_out),
                           self._ptr(d_audio), stride, stream)
+
+
+class FmFirPlan(_Plan):
+    """rtlws_fmfir_plan* of include/rtlws_fmfir.h: the taps and the phasor table on the engine's device, the kernel of
+    (decim, ntaps) and the state copy loaded.  eng may be None (as a C caller's NULL engine): open then fails with the
+    library's text."""
+    _name, _lib = "fmfir", staticmethod(fmfir_lib)
+
+    def __init__(self, eng, decim, taps):
+        self.decim = int(decim)
+        self.taps = None if taps is None else np.ascontiguousarray(taps, dtype=np.int16).reshape(-1)
+        self.ntaps = 0 if self.taps is None else self.taps.size
+        self._open(eng, self.decim, self.ntaps, None if self.taps is None else _p(self.taps))
+
+    def run(self, d_iq, block_len, nblocks, tuning_words, d_state_in, d_state_out, d_audio, out_shift=14, audio_stride=None,
+            first_dec_index=0, stream=None, check=True):
+        """One launch: audio of channel c at d_audio + c * audio_stride floats, states channel-major [C, 21]."""
+        stride = int(nblocks) * (int(block_len) // 4) if audio_stride is None else int(audio_stride)
+        return self._call("run", check, self._ptr(d_iq), int(block_len), int(nblocks), int(first_dec_index),
+                          len(tuning_words), _words(tuning_words), int(out_shift), self._ptr(d_state_in),
+                          self._ptr(d_state_out), self._ptr(d_audio), stride, stream)
 
 
 class _PolyphasePlan(_Plan):
@@ -1483,6 +1542,35 @@ class Engine:
         d_audio = self.alloc(max(nch * n, 1) * 4)
         try:
             plan.run(cic_r, d_iq, block_len, nblocks, tuning_words, d_in, d_out, d_audio, n, first_dec_index)
+            self.sync()
+            audio = self.download(d_audio, np.float32, (nch, n)) if nch * n else np.zeros((nch, 0), np.float32)
+            new_states = self.download(d_out, np.float32, (nch, FM_STATE_FLOATS))
+        finally:
+            plan.close()
+            for b in (d_iq, d_in, d_out, d_audio):
+                b.free()
+        return audio, new_states
+
+    # -- include/rtlws_fmfir.h: host arrays in, (audio, new states) out ----
+    def fm_fir_bank(self, iq, decim, taps, tuning_words, block_len, states, out_shift=14, first_dec_index=0):
+        """rtlws_fmfir_run: iq uint8 [(nblocks * block_len - 1) * decim + ntaps, 2] (as many blocks as iq holds), taps
+        int16 [ntaps], one tuning word and one state f32[21] per channel -> (audio f32 [C, nblocks * quarter], new states
+        f32 [C, 21]).  The capture is uploaded at exactly the samples needed."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
+        nch = len(tuning_words)
+        states = np.ascontiguousarray(states, dtype=np.float32).reshape(nch, FM_STATE_FLOATS)
+        plan = FmFirPlan(self, decim, taps)
+        dec_len = (iq.shape[0] - plan.ntaps) // plan.decim + 1 if iq.shape[0] >= plan.ntaps else 0
+        nblocks = dec_len // int(block_len) if block_len > 0 else 0
+        need = fmfir_samples_needed(plan.decim, plan.ntaps, block_len, nblocks)
+        assert 0 <= need <= iq.shape[0]
+        n = max(int(nblocks) * (int(block_len) // 4), 0)
+        d_iq = self.upload(iq[:need]) if need else self.alloc(16)
+        d_in = self.upload(states)
+        d_out = self.alloc(states.nbytes)
+        d_audio = self.alloc(max(nch * n, 1) * 4)
+        try:
+            plan.run(d_iq, block_len, nblocks, tuning_words, d_in, d_out, d_audio, out_shift, n, first_dec_index)
             self.sync()
             audio = self.download(d_audio, np.float32, (nch, n)) if nch * n else np.zeros((nch, 0), np.float32)
             new_states = self.download(d_out, np.float32, (nch, FM_STATE_FLOATS))
