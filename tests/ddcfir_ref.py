@@ -9,6 +9,18 @@ P = ddc_ref.P
 MAX_TAP = 32639
 MAX_TAPS = 256
 K_SET = (0, 1, -1, 777, -20001, 32767, -32768)
+# the (decim, ntaps) at which the GPU suites hold the kernels that form a filtered sample to the restatement
+# (tests/test_ddcfir_gpu.py's matrix, tests/fmfir_ref.py's stage-A matrix): every R of R_AXIS with every L of l_axis(R)
+R_AXIS = (1, 3, 8, 10, 12, 16, 17, 128)
+
+
+def l_axis(R):
+    return sorted({1, R, R + 1, 17, 33, min(8 * R, 256), 255, 256})
+
+
+def aligned(R, L):
+    """the kernels' instantiation: decim and ntaps multiples of four (8-byte window loads)"""
+    return R % 4 == 0 and L % 4 == 0
 
 
 def samples_needed(R, L, dec_len):

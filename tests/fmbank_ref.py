@@ -8,7 +8,8 @@ import fm_ref
 P = ddc_ref.P
 SPECIAL_WORDS = (0, 1, -1, -32768, 32767)
 # (cic_r, channels): both sides of a column-tile border (8 | 9) and of a K step (16 | 17), every instantiation
-# (8, 10, 12, generic), one and four column tiles
+# (8, 10, 12, generic); one column tile, two of which the second holds one channel, and four full ones.  Three column
+# tiles, a second one that is full or partly filled and every other C = 1 .. 32 run from tests/ddc_family_channels.py
 BANKS = [(1, 1), (7, 9), (8, 8), (8, 32), (10, 1), (12, 9), (16, 8), (17, 2), (128, 32)]
 
 # the banks of the multi-tile suite (fm_ref.tile_cases): every case at a compile-time factor with two column tiles of

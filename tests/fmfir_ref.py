@@ -79,6 +79,93 @@ def extend(iq, extra, fill_seed=79):
     return np.concatenate([iq, more])
 
 
+# ---- stage A at the window forms of the filtered down-converter ---------------------------------------------------
+# fmfir_bank.hip's phases<ALIGNED> shares the operand builder and the window loader with ddcfir_bank.hip, but the loop
+# around them is its own: the next K step's window loaded ahead of the MFMAs (one step past the last), the block-phasor
+# lookups in front of the K loop, lanes masked by idx < np && g >= 0, row tiles dealt in pairs per wavefront.  This
+# matrix runs it at every (decim, ntaps) at which tests/test_ddcfir_gpu.py holds ddcfir_bank_kernel to the restatement
+# (ddcfir_ref.R_AXIS x l_axis) and at STAGE_A_EXTRA; the other axes are cycled over the pairs of an instantiation.
+# tests/test_fmfir_cpu.py holds it to its conditions.
+
+STAGE_A_EXTRA = ((8, 24),)          # two K steps under the aligned instantiation: the axes' aligned pairs have 1, 4, 6, 8, 16
+STAGE_A_C = (1, 2, 8, 9, 17, 24, 32)
+STAGE_A_SHIFTS = (0, 9, 14)
+STAGE_A_FIRSTS = (0, 123456789, (1 << 40) + 12345)
+STAGE_A_BYTES = ("random", "full scale")
+STAGE_A_TAPS = ("random", "+max", "-max")
+NP_CLASSES = {"1 .. 15": range(1, 16), "16": (16,), "17 .. 31": range(17, 32), "0": (0,)}
+
+
+class StageACase(tuple):
+    """(decim, ntaps, channels, out_shift, first_dec_index, bytes, taps, block_len, nblocks)"""
+    R, L, C = (property(lambda s, i=i: s[i]) for i in range(3))
+    shift, first, bytes, taps, block_len, nblocks = (property(lambda s, i=i: s[i]) for i in range(3, 9))
+    id = property(lambda s: "R%d-L%d-C%d-s%d-%dx%d" % (s[0], s[1], s[2], s[3], s[7], s[8]))
+    aligned = property(lambda s: ddcfir_ref.aligned(s[0], s[1]))
+    product = property(lambda s: s[1] * s[2] * s[7] * s[8])          # what the restatement's time goes with
+
+
+def stage_a_pairs():
+    return [(R, L) for R in ddcfir_ref.R_AXIS for L in ddcfir_ref.l_axis(R)] + list(STAGE_A_EXTRA)
+
+
+def stage_a_shapes(tile):
+    """(block_len, nblocks): fm_ref.tile_cases' a3 (block_len 23, the shape the LDS capacities are derived for) cut to
+    one tile and a part of a second, its b1 and b3 (the stage-1 map skips, borders in front of tiles, four tiles), and
+    three blocks of 20, 22, 23 and 25 inside one tile."""
+    cases = {(c.regime, c.residue): c for c in fm_ref.tile_cases(tile)}
+    a3 = cases["a", 3]
+    cut = tile // (a3.block_len // 4) + 1
+    assert cut < a3.nblocks and tile < cut * (a3.block_len // 4) < 2 * tile
+    return [(a3.block_len, cut), tuple(cases["b", 1][2:]), tuple(cases["b", 3][2:]), (20, 3), (22, 3), (23, 3), (25, 3)]
+
+
+def stage_a_matrix(tile):
+    """Every (decim, ntaps) of stage_a_pairs(); per instantiation the other axes cycle over its pairs: the channel
+    counts with stride 1, the block shapes with stride 1 from the fourth on and one more step per round of the channel
+    counts (two axes of seven: a channel count meets another shape in every round, and in the first round 17, 24 and
+    32 channels meet the shapes of several tiles), the others with strides 2, 4, 3 and 5, none of which shares a factor
+    with its axis' length."""
+    shapes = stage_a_shapes(tile)
+    count = {True: 0, False: 0}
+    cases = []
+    for R, L in stage_a_pairs():
+        inst = ddcfir_ref.aligned(R, L)
+        i = count[inst]
+        count[inst] += 1
+        cases.append(StageACase((R, L, STAGE_A_C[i % 7], STAGE_A_SHIFTS[(i // 2) % 3], STAGE_A_FIRSTS[(i // 4) % 3],
+                                 STAGE_A_BYTES[(i // 3) % 2], STAGE_A_TAPS[(i // 5) % 3]) + shapes[(i + 3 + i // 7) % len(shapes)]))
+    return cases
+
+
+def np_residues(case, tile):
+    """np mod 32 of every ordinary tile of a case's launch (fm_ref.tile_bounds): how the last pair of row tiles of
+    stage A is masked"""
+    nt = -(-case.nblocks * (case.block_len // 4) // tile)
+    return [int(fm_ref.tile_bounds(t, case.block_len, case.nblocks, tile)["np"]) % 32 for t in range(nt)]
+
+
+def stage_a_inputs(case, seed):
+    """(capture of exactly the samples needed, taps, words, states) of a case"""
+    R, L = case.R, case.L
+    iq, words, states = inputs(R, L, case.C, case.block_len, case.nblocks, seed)
+    if case.bytes == "full scale":
+        iq = ddcfir_ref.full_scale_iq(iq.shape[0], seed + 2)
+    if case.taps == "random":
+        taps = taps_for(R, L, seed + 3)
+    else:
+        taps = np.full(L, ddcfir_ref.MAX_TAP if case.taps == "+max" else -ddcfir_ref.MAX_TAP, dtype=np.int16)
+    return iq, taps, words, states
+
+
+def composition_cases(tile):
+    """One case per instantiation for the comparison with rtlws_ddcfir_run followed by rtlws_fm_audio_blocks on the
+    device: the first with more than one tile and more than one column tile."""
+    matrix = stage_a_matrix(tile)
+    return [next(i for i, c in enumerate(matrix) if c.aligned == inst and c.C > 8 and c.nblocks * (c.block_len // 4) > tile)
+            for inst in (True, False)]
+
+
 # ---- why the filter matters, end to end (on the restatement, not the device) ------------------------------------
 
 FM_R = ddcfir_ref.SELECTIVITY_R

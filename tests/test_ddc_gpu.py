@@ -4,6 +4,7 @@ integer is defined."""
 import numpy as np
 import pytest
 
+import ddc_family_channels as channels
 import ddc_ref
 import fm_ref
 
@@ -11,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 P = ddc_ref.P
 SPECIAL_WORDS = (0, 1, -1, -32768, 32767)
+SENTINEL = np.int32(-0x12345678)
 
 
 @pytest.fixture(scope="module")
@@ -74,6 +76,35 @@ def test_bank_matrix(engine, tile, R, C):
     mid = np.full((longest * R, 2), 128, dtype=np.uint8)
     for n in (1, t - 1, t, t + 1, longest):
         assert not engine.ddc(mid[:n * R], R, words).any(), n
+
+
+@pytest.mark.parametrize("R", channels.paths("ddc"), ids=channels.path_id)
+def test_every_channel_count(engine, built, tile, R):
+    """tests/ddc_family_channels.py: C = 1 .. 32 of one set of 32 words over one capture, tile + 17 decimated samples.
+    Every launch goes through the plan's run into 32 rows of out_stride > dec_len and a tail, all sentinels: rows
+    0 .. C - 1 are the first C of the 32-channel restatement, every other word is untouched -- a ninth "channel" of a
+    partly filled column tile would land in row C."""
+    n = channels.stream_len(tile)
+    stride, tail = n + 7, 64
+    rows = channels.MAX_CH
+    want = channels.stream_expected("ddc", R, tile)
+    fill = np.full((rows * stride + tail, 2), SENTINEL, dtype=np.int32)
+    plan = built.DdcPlan.open(engine)
+    d_iq = engine.upload(channels.stream_inputs("ddc", R, tile))
+    for C in channels.channels("ddc", R):
+        rc, blocks, _, _, t = built.ddc_grid(R, C, n)
+        assert rc == 0 and t == tile and blocks == -(-n // tile) * 1
+        d_out = engine.upload(fill)
+        plan.run(R, d_iq, n, channels.WORDS[:C], d_out, out_stride=stride, first_dec_index=channels.FIRST)
+        engine.sync()
+        out = engine.download(d_out, np.int32, fill.shape)
+        d_out.free()
+        body = out[:rows * stride].reshape(rows, stride, 2)
+        bad = np.argwhere(body[:C, :n] != want[:C])
+        assert bad.size == 0, (C, len(bad), bad[:4])
+        assert np.all(body[:C, n:] == SENTINEL) and np.all(body[C:] == SENTINEL) and np.all(out[rows * stride:] == SENTINEL), C
+    plan.close()
+    d_iq.free()
 
 
 @pytest.mark.parametrize("first", [0, (1 << 40) + 12345])

@@ -5,6 +5,7 @@ run here is also a run against the end of its allocation."""
 import numpy as np
 import pytest
 
+import ddc_family_channels as channels
 import ddc_ref
 import ddcfir_ref as ref
 import fm_ref
@@ -14,19 +15,12 @@ pytestmark = pytest.mark.gpu
 P = ref.P
 SPECIAL_WORDS = (0, 1, -1, 777, -20001, 32767, -32768)
 FIRST = 123456789
-R_AXIS = (1, 3, 8, 10, 12, 16, 17, 128)
+SENTINEL = np.int32(-0x12345678)
+R_AXIS, l_axis, aligned = ref.R_AXIS, ref.l_axis, ref.aligned          # shared with tests/fmfir_ref.py's stage-A matrix
 C_AXIS = (1, 2, 7, 8, 9, 32)
 S_AXIS = (0, 14, 30)
 BYTES = ("random", "full scale", "all 0", "all 255")
 TAPS = ("random", "+max", "-max")
-
-
-def l_axis(R):
-    return sorted({1, R, R + 1, 17, 33, min(8 * R, 256), 255, 256})
-
-
-def aligned(R, L):
-    return R % 4 == 0 and L % 4 == 0
 
 
 def matrix():
@@ -106,6 +100,39 @@ def test_bank_matrix(engine, tile, case):
         assert bad.size == 0, (n, bad[:4], got[tuple(bad[0])], want[tuple(bad[0])])
     mid = np.full_like(iq, 128)
     assert not engine.ddcfir(mid, R, taps, words, out_shift=s, first_dec_index=first).any()
+
+
+@pytest.mark.parametrize("path", channels.paths("ddcfir"), ids=channels.path_id)
+def test_every_channel_count(engine, built, tile, path):
+    """tests/ddc_family_channels.py: C = 1 .. 32 of one set of 32 words over one capture of exactly samples_needed,
+    tile + 17 decimated samples, at the three load forms of a window (bank_tile<ALIGNED, 1 .. 4> each); ntaps = 1 and 256
+    at both sides of the third column tile's borders (48 KiB of dynamic LDS at 256 taps and three column tiles).
+    Every launch goes through the plan's run into 32 rows of out_stride > dec_len and a tail, all sentinels: rows
+    0 .. C - 1 are the first C of the 32-channel restatement, every other word is untouched."""
+    R, L = path
+    n = channels.stream_len(tile)
+    stride, tail = n + 7, 64
+    rows = channels.MAX_CH
+    want = channels.stream_expected("ddcfir", path, tile)
+    fill = np.full((rows * stride + tail, 2), SENTINEL, dtype=np.int32)
+    iq = channels.stream_inputs("ddcfir", path, tile)
+    assert iq.shape[0] == built.ddcfir_samples_needed(R, L, n)
+    plan = built.DdcFirPlan.open(engine, R, channels.taps_of(path))
+    d_iq = engine.upload(iq)
+    for C in channels.channels("ddcfir", path):
+        rc, blocks, _, lds, t = built.ddcfir_grid(R, L, C, n)
+        assert rc == 0 and t == tile and blocks == -(-n // tile) * 1 and lds == -(-C // 8) * -(-L // 16) * 1024
+        d_out = engine.upload(fill)
+        plan.run(d_iq, n, channels.WORDS[:C], d_out, out_shift=14, out_stride=stride, first_dec_index=channels.FIRST)
+        engine.sync()
+        out = engine.download(d_out, np.int32, fill.shape)
+        d_out.free()
+        body = out[:rows * stride].reshape(rows, stride, 2)
+        bad = np.argwhere(body[:C, :n] != want[:C])
+        assert bad.size == 0, (C, len(bad), bad[:4])
+        assert np.all(body[:C, n:] == SENTINEL) and np.all(body[C:] == SENTINEL) and np.all(out[rows * stride:] == SENTINEL), C
+    plan.close()
+    d_iq.free()
 
 
 @pytest.mark.parametrize("R", [8, 10, 12, 7])

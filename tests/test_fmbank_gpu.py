@@ -3,6 +3,7 @@ per channel fed to the oracle's per-block chain.  Every comparison is np.array_e
 import numpy as np
 import pytest
 
+import ddc_family_channels as channels
 import ddc_ref
 import fm_ref
 import fmbank_ref
@@ -11,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 P = ddc_ref.P
 STATE = fm_ref.STATE
+SENTINEL = np.float32(-12345.678)
 
 
 @pytest.fixture(scope="module")
@@ -51,6 +53,53 @@ def test_bank_matrix(engine, oracle, built, tile, R, C):
         assert np.array_equal(got[0][0], got[0][C - 1]) and np.array_equal(got[1][0], got[1][C - 1])
     if C >= 3:
         assert not np.array_equal(got[0][0], got[0][1])
+
+
+def check_rows(audio, st, want, C, n, stride, what):
+    """audio f32 [32 * stride + tail] and state_out f32 [32 * 21 + tail] of a launch of C channels into sentinels:
+    rows 0 .. C - 1 hold the first C expected rows, every other word its sentinel (compared as bit patterns)."""
+    rows = channels.MAX_CH
+    want_audio, want_st = want
+    mark = SENTINEL.view(np.uint32)
+    body = audio[:rows * stride].reshape(rows, stride)
+    bad = np.argwhere(body[:C, :n] != want_audio[:C])
+    assert bad.size == 0, (what, "audio", len(bad), bad[:4])
+    bad = np.argwhere(st[:C * STATE].reshape(C, STATE) != want_st[:C])
+    assert bad.size == 0, (what, "state", bad[:8])
+    assert np.all(body[:C, n:].view(np.uint32) == mark) and np.all(body[C:].view(np.uint32) == mark), (what, "audio rows")
+    assert np.all(audio[rows * stride:].view(np.uint32) == mark) and np.all(st[C * STATE:].view(np.uint32) == mark), (what, "tails")
+
+
+@pytest.mark.parametrize("R", channels.paths("fmbank"), ids=channels.path_id)
+def test_every_channel_count(engine, oracle, built, tile, R):
+    """tests/ddc_family_channels.py: C = 1 .. 32 of one set of 32 words and 32 carried states over one capture of two
+    full tiles and a remainder: 4 ceil(C / 8) workgroups, so that with three column tiles blockIdx.x = 0 .. 11 passes
+    through the division by nct and meets every (tile, column tile).  Every launch goes through the plan's run into 32
+    audio rows of audio_stride > the run's length and 32 x 21 floats of state_out, each with a tail, all sentinels."""
+    iq, L, nb = channels.fm_inputs("fmbank", R, tile)
+    n = nb * (L // 4)
+    ntiles = -(-n // tile)
+    stride, tail = n + 7, 64
+    rows = channels.MAX_CH
+    want = channels.fm_expected(oracle, "fmbank", R, tile)
+    fill_audio = np.full(rows * stride + tail, SENTINEL, dtype=np.float32)
+    fill_st = np.full(rows * STATE + tail, SENTINEL, dtype=np.float32)
+    plan = built.FmBankPlan.open(engine)
+    d_iq = engine.upload(iq)
+    d_in = engine.upload(channels.states())
+    for C in channels.channels("fmbank", R):
+        rc, blocks, _, _, t = built.fmbank_grid(R, C, L, nb)
+        assert rc == 0 and t == tile and ntiles == 3 and blocks == (ntiles + 1) * -(-C // 8)
+        d_out, d_audio = engine.upload(fill_st), engine.upload(fill_audio)
+        plan.run(R, d_iq, L, nb, channels.WORDS[:C], d_in, d_out, d_audio, audio_stride=stride)
+        engine.sync()
+        audio = engine.download(d_audio, np.float32, fill_audio.shape)
+        st = engine.download(d_out, np.float32, fill_st.shape)
+        d_out.free(), d_audio.free()
+        check_rows(audio, st, want, C, n, stride, (R, C))
+    assert np.array_equal(engine.download(d_in, np.float32, (rows, STATE)), channels.states())
+    plan.close()
+    d_iq.free(), d_in.free()
 
 
 @pytest.mark.parametrize("nb", [1, 3])

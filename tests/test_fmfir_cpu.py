@@ -241,6 +241,68 @@ def test_the_inputs_of_the_gpu_suite_are_what_it_says(built):
         assert rc == 0 and t == tile and blocks == (case.ntiles(tile) + 1) * -(-c // 8), (case.id, r, l, c)
 
 
+# ---- stage A at the window forms of the filtered down-converter (tests/fmfir_ref.py's stage_a_matrix) ----------------
+# The restatement and the oracle's chain take about 5.4 ns per unit of ntaps * channels * nblocks * block_len (0.18 s at
+# the largest product of the matrix, 33 390 592); three seconds are 5.5e8 units.  No case comes near it, so no channel
+# count had to be moved to a shorter block shape.
+PRODUCT_BOUND = 550_000_000
+
+
+def _stage_a_conditions(matrix, tile):
+    """What the stage-A matrix has to meet, per instantiation: raises AssertionError."""
+    pairs = fmfir_ref.stage_a_pairs()
+    assert sorted((c.R, c.L) for c in matrix) == sorted(pairs) and len(set(pairs)) == len(pairs)
+    assert set(pairs) >= {(R, L) for R in ddcfir_ref.R_AXIS for L in ddcfir_ref.l_axis(R)}
+    shapes = set(fmfir_ref.stage_a_shapes(tile))
+    for inst in (True, False):
+        mine = [c for c in matrix if c.aligned == inst]
+        assert {c.C for c in mine} == set(fmfir_ref.STAGE_A_C) == {1, 2, 8, 9, 17, 24, 32}, inst
+        assert {c.shift for c in mine} == {0, 9, 14} and {c.first for c in mine} == {0, 123456789, (1 << 40) + 12345}, inst
+        assert {c.bytes for c in mine} == {"random", "full scale"} and {c.taps for c in mine} == {"random", "+max", "-max"}, inst
+        assert {(c.block_len, c.nblocks) for c in mine} == shapes, inst
+        assert {c.L % 16 for c in mine} == {L % 16 for R, L in pairs if ddcfir_ref.aligned(R, L) == inst}, inst
+        assert {-(-c.L // 16) for c in mine} >= {1, 2, 16}, inst
+        reached = {r for c in mine for r in fmfir_ref.np_residues(c, tile)}
+        for name, residues in fmfir_ref.NP_CLASSES.items():
+            assert reached & set(residues), (inst, name)
+        # more than one column tile over more than one tile, and a first_dec_index whose upper bits the lookup drops
+        assert any(c.C > 8 and c.nblocks * (c.block_len // 4) > tile for c in mine), inst
+        assert any(c.first >> 16 and c.nblocks * (c.block_len // 4) > tile for c in mine), inst
+
+
+def test_the_stage_a_matrix_meets_its_conditions(built):
+    """Per instantiation: every value of every axis, every ntaps mod 16 of the pairs, 1, 2 and 16 K steps, and ordinary
+    tiles whose np mod 32 lies in each of 1 .. 15, 16, 17 .. 31 and 0 (the last pair of row tiles: one partly live; one
+    full and one dead; one full and one partly live; both full).  Deleting any one (decim, ntaps), and taking away
+    the launches that reach any one class of np, fails.  The restatement's cost stays under its bound."""
+    tile = built.fmfir_grid(8, 8, 1, 20, 1)[4]
+    matrix = fmfir_ref.stage_a_matrix(tile)
+    _stage_a_conditions(matrix, tile)
+    assert len(matrix) == 61 and sum(c.aligned for c in matrix) == 12
+    assert len({c.id for c in matrix}) == len(matrix)
+    for i in range(len(matrix)):
+        with pytest.raises(AssertionError):
+            _stage_a_conditions(matrix[:i] + matrix[i + 1:], tile)
+    for name, residues in fmfir_ref.NP_CLASSES.items():
+        without = [c for c in matrix if not set(fmfir_ref.np_residues(c, tile)) & set(residues)]
+        assert len(without) < len(matrix)
+        with pytest.raises(AssertionError):
+            _stage_a_conditions(without, tile)
+    # what the axes of the ddcfir suite alone would leave out under the aligned instantiation
+    assert {-(-L // 16) for R in ddcfir_ref.R_AXIS for L in ddcfir_ref.l_axis(R) if ddcfir_ref.aligned(R, L)} == {1, 4, 6, 8, 16}
+    assert [(R, L, ddcfir_ref.aligned(R, L), -(-L // 16)) for R, L in fmfir_ref.STAGE_A_EXTRA] == [(8, 24, True, 2)]
+    # L = 255, L = R + 1 and L = 1 at every R; a launch per shape of fm_ref.tile_cases that the issue names
+    for R in ddcfir_ref.R_AXIS:
+        assert {1, R + 1, 255} <= {c.L for c in matrix if c.R == R}, R
+    largest = max(matrix, key=lambda c: c.product)
+    print("largest ntaps * channels * nblocks * block_len: %d at %s; bound %d" % (largest.product, largest.id, PRODUCT_BOUND))
+    assert largest.product <= PRODUCT_BOUND and largest.product == 33390592, largest.product
+    for c in matrix:
+        assert built.fmfir_supported(c.R, c.L, c.C, c.block_len, c.nblocks) == 1, c.id
+    comp = fmfir_ref.composition_cases(tile)
+    assert [matrix[i].aligned for i in comp] == [True, False]
+
+
 # ---- why the filter matters, end to end: measured on tests/fmfir_ref.py's restatement (DESIGN.md 4.13c) --------------
 # measured: boxcar -0.17 dB (the error is as strong as the wanted tone), designed 8R = 96-tap filter -44.69 dB; each is
 # asserted with 6 dB of margin on its own side

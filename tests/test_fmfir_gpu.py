@@ -4,10 +4,12 @@ np.array_equal, on audio and on state."""
 import numpy as np
 import pytest
 
+import ddc_family_channels as channels
 import ddcfir_ref
 import fm_ref
 import fmbank_ref
 import fmfir_ref
+from test_fmbank_gpu import SENTINEL, check_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -53,6 +55,41 @@ def test_bank_matrix(engine, oracle, built, tile, R, L, C, designed):
         assert not np.array_equal(got[0][0], got[0][1])
 
 
+@pytest.mark.parametrize("path", channels.paths("fmfir"), ids=channels.path_id)
+def test_every_channel_count(engine, oracle, built, tile, path):
+    """tests/ddc_family_channels.py: C = 1 .. 32 of one set of 32 words and 32 carried states over one capture of exactly
+    samples_needed, two full tiles and a remainder, at the three load forms of a window: 4 ceil(C / 8) workgroups, so
+    that with three column tiles blockIdx.x = 0 .. 11 passes through the division by nct and meets every (tile, column
+    tile).  Every launch goes through the plan's run into 32 audio rows of audio_stride > the run's length and 32 x 21
+    floats of state_out, each with a tail, all sentinels (tests/test_fmbank_gpu.py's check_rows)."""
+    R, L = path
+    iq, bl, nb = channels.fm_inputs("fmfir", path, tile)
+    assert iq.shape[0] == built.fmfir_samples_needed(R, L, bl, nb)
+    n = nb * (bl // 4)
+    ntiles = -(-n // tile)
+    stride, tail = n + 7, 64
+    rows = channels.MAX_CH
+    want = channels.fm_expected(oracle, "fmfir", path, tile)
+    fill_audio = np.full(rows * stride + tail, SENTINEL, dtype=np.float32)
+    fill_st = np.full(rows * STATE + tail, SENTINEL, dtype=np.float32)
+    plan = built.FmFirPlan.open(engine, R, channels.taps_of(path))
+    d_iq = engine.upload(iq)
+    d_in = engine.upload(channels.states())
+    for C in channels.channels("fmfir", path):
+        rc, blocks, _, _, t = built.fmfir_grid(R, L, C, bl, nb)
+        assert rc == 0 and t == tile and ntiles == 3 and blocks == (ntiles + 1) * -(-C // 8)
+        d_out, d_audio = engine.upload(fill_st), engine.upload(fill_audio)
+        plan.run(d_iq, bl, nb, channels.WORDS[:C], d_in, d_out, d_audio, audio_stride=stride)
+        engine.sync()
+        audio = engine.download(d_audio, np.float32, fill_audio.shape)
+        st = engine.download(d_out, np.float32, fill_st.shape)
+        d_out.free(), d_audio.free()
+        check_rows(audio, st, want, C, n, stride, (path, C))
+    assert np.array_equal(engine.download(d_in, np.float32, (rows, STATE)), channels.states())
+    plan.close()
+    d_iq.free(), d_in.free()
+
+
 @pytest.mark.parametrize("shift", [0, 30])
 def test_shifts(engine, oracle, tile, shift):
     """Both ends of out_shift: at 30 most integers are 0, the atan2(0, 0) branch."""
@@ -65,6 +102,46 @@ def test_shifts(engine, oracle, tile, shift):
         assert np.mean(streams == 0) > 0.5 and np.any(np.all(streams == 0, axis=2))
     check(engine.fm_fir_bank(iq, R, taps, words, bl, states, out_shift=shift),
           fmfir_ref.expected(oracle, iq, R, taps, words, bl, states, shift), shift)
+
+
+STAGE_A_PAIRS = fmfir_ref.stage_a_pairs()
+
+
+def _stage_a_run(engine, case, seed):
+    iq, taps, words, states = fmfir_ref.stage_a_inputs(case, seed)
+    got = engine.fm_fir_bank(iq, case.R, taps, words, case.block_len, states, out_shift=case.shift, first_dec_index=case.first)
+    return (iq, taps, words, states), got
+
+
+@pytest.mark.parametrize("index", range(len(STAGE_A_PAIRS)), ids=["R%d-L%d" % p for p in STAGE_A_PAIRS])
+def test_stage_a_at_every_window_form(engine, oracle, built, tile, index):
+    """fmfir_ref.stage_a_matrix: phases<ALIGNED> at every (decim, ntaps) of the filtered down-converter's matrix, the
+    channel counts, out_shift, first_dec_index, byte kinds, tap kinds and block shapes cycled over them
+    (tests/test_fmfir_cpu.py holds the matrix to its conditions: every np mod 32 class of the last pair of row tiles,
+    1, 2 and 16 K steps, every ntaps mod 16, per instantiation)."""
+    case = fmfir_ref.stage_a_matrix(tile)[index]
+    assert (case.R, case.L) == STAGE_A_PAIRS[index]
+    (iq, taps, words, states), got = _stage_a_run(engine, case, seed=5000 + index)
+    assert iq.shape[0] == built.fmfir_samples_needed(case.R, case.L, case.block_len, case.nblocks)
+    want = fmfir_ref.expected(oracle, iq, case.R, taps, words, case.block_len, states, case.shift, case.first)
+    check(got, want, case.id)
+    assert np.any(got[0] != 0)
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["aligned", "generic"])
+def test_stage_a_device_composition(engine, tile, which):
+    """Once per instantiation, a case of the stage-A matrix with several tiles and column tiles: Engine.ddcfir followed
+    by Engine.fm_audio_blocks per channel, on the device, equals the fused launch (test_device_composition's form)."""
+    index = fmfir_ref.composition_cases(tile)[which]
+    case = fmfir_ref.stage_a_matrix(tile)[index]
+    assert case.aligned == (which == 0)
+    (iq, taps, words, states), (audio, st) = _stage_a_run(engine, case, seed=5000 + index)
+    streams = engine.ddcfir(iq, case.R, taps, words, out_shift=case.shift, first_dec_index=case.first)
+    assert streams.shape == (case.C, case.nblocks * case.block_len, 2)
+    for c in range(case.C):
+        want_audio, want_st = engine.fm_audio_blocks(streams[c], case.block_len, states[c])
+        assert np.array_equal(audio[c], want_audio) and np.array_equal(st[c], want_st), (case.id, c)
+    assert np.any(audio != 0)
 
 
 @pytest.mark.parametrize("R", [8, 10, 7])
