@@ -18,6 +18,7 @@ fail loudly.
   PfbXcPlan, Engine.pfbxc  include/rtlws_pfbxc.h (polyphase cross-correlator: K-frame powers and cross-spectra of 2-4 captures in one launch)
   PfbBfPlan, Engine.pfbbf, Engine.pfbbf_power  include/rtlws_pfbbf.h (polyphase beamformer: 1-4 weighted beams of 1-8 captures in one launch)
   PfbSkPlan, Engine.pfbsk  include/rtlws_pfbsk.h (polyphase spectrometer with spectral-kurtosis excision: the power over the kept ones of L sub-integrations, one launch)
+  DedispPlan, Engine.dedisp  include/rtlws_dedisp.h (incoherent dedispersion of f32 rows: every trial of a delay table in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -48,6 +49,7 @@ PFBSPEC_LIB = os.path.join(LIB_DIR, "librtlws_pfbspec.so")   # include/rtlws_pfb
 PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
 PFBBF_LIB = os.path.join(LIB_DIR, "librtlws_pfbbf.so")   # include/rtlws_pfbbf.h
 PFBSK_LIB = os.path.join(LIB_DIR, "librtlws_pfbsk.so")   # include/rtlws_pfbsk.h
+DEDISP_LIB = os.path.join(LIB_DIR, "librtlws_dedisp.so") # include/rtlws_dedisp.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -145,6 +147,9 @@ PFBBF_MIN_BEAMS, PFBBF_MAX_BEAMS = 1, 4
 PFBSK_SYMBOLS = ["rtlws_pfbsk_supported", "rtlws_pfbsk_samples_needed", "rtlws_pfbsk_grid", "rtlws_pfbsk_power_scale",
                  "rtlws_pfbsk_bounds", "rtlws_pfbsk_open", "rtlws_pfbsk_run", "rtlws_pfbsk_close", "rtlws_pfbsk_last_error"]
 PFBSK_MAX_K_AVG, PFBSK_MAX_NSUB = 65536, 65535
+DEDISP_SYMBOLS = ["rtlws_dedisp_supported", "rtlws_dedisp_delays", "rtlws_dedisp_geometry", "rtlws_dedisp_open",
+                  "rtlws_dedisp_rows_needed", "rtlws_dedisp_run", "rtlws_dedisp_close", "rtlws_dedisp_last_error"]
+DEDISP_MIN_NCHAN, DEDISP_MAX_NCHAN, DEDISP_MAX_TRIALS, DEDISP_MAX_DELAY = 4, 4096, 4096, 65535
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -668,6 +673,60 @@ def pfbsk_bounds(k_avg, sk_lo, sk_hi):
     return lo.value, hi.value
 
 
+_DEDISP_PROTOTYPES = {
+    "rtlws_dedisp_supported": [_i, _i], "rtlws_dedisp_delays": [_i, _i, C.c_double, C.c_double, C.c_double, _i, C.c_double, C.c_double, _vp],
+    "rtlws_dedisp_geometry": [_i, _i, _vp, _vp, _l, _ip, _ip, _ip, _ip, _ip, _ip], "rtlws_dedisp_open": ([_vp, _i, _i, _vp, _vp], _vp),
+    "rtlws_dedisp_rows_needed": ([_vp, _l], _l), "rtlws_dedisp_run": [_vp, _vp, _l, _l, _vp, _l, _vp],
+    "rtlws_dedisp_close": ([_vp], None), "rtlws_dedisp_last_error": ([], _str)}
+
+
+def dedisp_lib():
+    """librtlws_dedisp.so (include/rtlws_dedisp.h); it needs librtlws_hip.so's engine."""
+    return _satellite(DEDISP_LIB, _DEDISP_PROTOTYPES)
+
+
+def dedisp_last_error():
+    return dedisp_lib().rtlws_dedisp_last_error().decode()
+
+
+def dedisp_supported(nchan, ntrials):
+    """rtlws_dedisp_supported.  No GPU needed."""
+    return dedisp_lib().rtlws_dedisp_supported(int(nchan), int(ntrials))
+
+
+def dedisp_delays(nchan, shifted, f_centre_hz, bandwidth_hz, row_seconds, ntrials, dm0, dm_step):
+    """rtlws_dedisp_delays: the delays in rows of ntrials dispersion measures dm0 + t dm_step, int32 [ntrials, nchan].  No
+    GPU needed."""
+    out = np.zeros((max(int(ntrials), 0), max(int(nchan), 0)), np.int32)
+    rc = dedisp_lib().rtlws_dedisp_delays(int(nchan), int(shifted), float(f_centre_hz), float(bandwidth_hz), float(row_seconds),
+                                          int(ntrials), float(dm0), float(dm_step), _p(out))
+    if rc != 0:
+        raise RuntimeError("rtlws_dedisp_delays failed (rc=%d): %s" % (rc, dedisp_last_error()))
+    return out
+
+
+def _dedisp_table(delays, mask):
+    """The table int32 [ntrials, nchan] and the mask (uint8 [nchan] or None) as the library reads them."""
+    delays = np.ascontiguousarray(delays, dtype=np.int32)
+    if delays.ndim != 2:
+        raise RuntimeError("rtlws_dedisp: the table is [ntrials, nchan]")
+    if mask is not None:
+        mask = np.ascontiguousarray(mask, dtype=np.uint8).reshape(-1)
+        if mask.size != delays.shape[1]:
+            raise RuntimeError("rtlws_dedisp: the mask holds nchan bytes")
+    return delays, mask
+
+
+def dedisp_geometry(delays, mask=None, nout=0):
+    """rtlws_dedisp_geometry of a table int32 [ntrials, nchan]: (rc, workgroups, threads, LDS bytes, outputs per
+    workgroup, trials per workgroup, largest delay over the kept positions).  No GPU needed."""
+    delays, mask = _dedisp_table(delays, mask)
+    v = [C.c_int(0) for _ in range(6)]
+    rc = dedisp_lib().rtlws_dedisp_geometry(delays.shape[1], delays.shape[0], _p(delays), None if mask is None else _p(mask),
+                                            int(nout), *[C.byref(x) for x in v])
+    return (rc,) + tuple(x.value for x in v)
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -1034,6 +1093,26 @@ class PfbSkPlan(_PolyphasePlan):
                           int(shifted), float(scale), self._ptr(d_clean), int(m if clean_stride is None else clean_stride),
                           self._ptr(d_kept), int(m if kept_stride is None else kept_stride), self._ptr(d_s1), self._ptr(d_s2),
                           int(m if sub_stride is None else sub_stride), stream)
+
+
+class DedispPlan(_Plan):
+    """rtlws_dedisp_plan* of include/rtlws_dedisp.h: the table (int32 [ntrials, nchan]) and the mask (uint8 [nchan] or
+    None) on the engine's device in the kernel's form, the kernel loaded.  eng may be None (as a C caller's NULL engine):
+    open then fails with the library's text."""
+    _name, _lib = "dedisp", staticmethod(dedisp_lib)
+
+    def __init__(self, eng, delays, mask=None):
+        delays, mask = _dedisp_table(delays, mask)
+        self.ntrials, self.nchan = delays.shape
+        self._open(eng, self.nchan, self.ntrials, _p(delays), None if mask is None else _p(mask))
+
+    def rows_needed(self, nout):
+        return self._fn("rows_needed")(self.h, int(nout))
+
+    def run(self, d_rows, nout, d_out, in_stride=None, out_stride=None, stream=None, check=True):
+        """One launch: trial t at d_out + t * out_stride elements (f32), row j of the input at d_rows + j * in_stride."""
+        return self._call("run", check, self._ptr(d_rows), int(self.nchan if in_stride is None else in_stride), int(nout),
+                          self._ptr(d_out), int(nout if out_stride is None else out_stride), stream)
 
 
 class PfbXcPlan(_PolyphasePlan):
@@ -1419,6 +1498,33 @@ class Engine:
             for b in bufs:
                 b.free()
         return out
+
+    # -- include/rtlws_dedisp.h: host rows in, one time series per trial out ----
+    def dedisp(self, rows, delays, mask=None, nout=None, in_stride=None, out_stride=None, fill=None):
+        """rtlws_dedisp_run: rows float32 [nrows, nchan] (with in_stride: [nrows, in_stride], the padding as the caller
+        left it), delays int32 [ntrials, nchan], mask uint8 [nchan] or None -> float32 [ntrials, nout].  nout None: as
+        many as the rows hold.  With out_stride the whole buffer [ntrials, out_stride] comes back, every element preset
+        to `fill` (a float32; None: zeros), so that a caller sees what the run left untouched."""
+        plan = DedispPlan(self, delays, mask)
+        width = plan.nchan if in_stride is None else int(in_stride)
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, width)
+        if nout is None:
+            nout = max(rows.shape[0] - (plan.rows_needed(1) - 1), 0)
+        nout = int(nout)
+        assert rows.shape[0] >= plan.rows_needed(nout), "fewer rows than rtlws_dedisp_rows_needed"
+        stride = nout if out_stride is None else int(out_stride)
+        host = np.full((plan.ntrials, max(stride, 0)), 0.0 if fill is None else fill, np.float32)
+        d_rows = self.upload(rows) if rows.nbytes else self.alloc(16)
+        d_out = self.upload(host) if host.nbytes else self.alloc(16)
+        try:
+            plan.run(d_rows, nout, d_out, width, stride)
+            self.sync()
+            out = self.download(d_out, np.float32, host.shape) if host.nbytes else host
+        finally:
+            plan.close()
+            d_rows.free()
+            d_out.free()
+        return out if out_stride is not None else out[:, :nout]
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
     def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):

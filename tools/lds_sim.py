@@ -309,3 +309,50 @@ if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "f64":
     analyse_f64(64, 16)
     analyse_f64_n(2048)
     analyse_f64_n(4096)
+
+
+def cycles_b32(addrs_dw, modulo=32):
+    """ds_read_b32 / ds_write_b32: two groups of 32 lanes, bank = dword address % 32; addrs_dw per lane, in dwords."""
+    tot = 0
+    for grp in R64:
+        banks = {}
+        for l in grp:
+            banks.setdefault(addrs_dw[l] % modulo, set()).add(addrs_dw[l])
+        tot += max(len(v) for v in banks.values())
+    return tot
+
+
+def dedisp_stride(height, quads):
+    """rtl-ws_amd/csrc/dedisp.h fit_stride: the smallest stride >= height that is (8 / quads) times an odd number"""
+    unit = 8 // quads if quads > 1 else 1
+    s = -(-height // unit)
+    if quads > 1 and s % 2 == 0:
+        s += 1
+    return s * unit
+
+
+def analyse_dedisp(heights=(256, 257, 260, 279, 300, 503), verbose=True):
+    """The dedispersion kernel's tile (rtl-ws_amd/csrc/dedisp.hip): column il of a chunk at il * stride.  Per wavefront and
+    instruction: the transposing ds_write_b32 (lane -> quad tid % quads, row tid / quads, value h of the quad in column
+    4 quad + h), the lone form's (lane -> position tid % 32, row tid / 32) and the sums' ds_read_b32 (lane -> row tid +
+    offset of one column).  Returns {(form, height): (write cycles, read cycles)}; ideal is 2 and 2."""
+    res = {}
+    for height in heights:
+        for quads in (8, 4, 2, 1):
+            stride = dedisp_stride(height, quads)
+            w = max(cycles_b32([(4 * (t % quads) + h) * stride + (wave * 64 + t) // quads + r0 for t in range(64)])
+                    for wave in range(4) for h in range(4) for r0 in (0, 1, 37))
+            r = max(cycles_b32([il * stride + wave * 64 + t + off for t in range(64)])
+                    for wave in range(4) for il in (0, 1, 4 * quads - 1) for off in (0, 1, 2, 3, 17, height - 256))
+            res[("%d quads" % quads, height)] = (w, r)
+        stride = dedisp_stride(256, 8)
+        w = max(cycles_b32([(t % 32) * stride + (wave * 64 + t) // 32 + r0 for t in range(64)]) for wave in range(4) for r0 in (0, 8, 255))
+        res[("lone", 256)] = (w, 2)
+    if verbose:
+        for (form, height), (w, r) in sorted(res.items()):
+            print("dedisp %-8s height %3d: ds_write_b32 %d cycles (ideal 2), ds_read_b32 %d (ideal 2)" % (form, height, w, r))
+    return res
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "dedisp":
+    analyse_dedisp()
