@@ -35,6 +35,7 @@
  * 64 KiB); where one trial alone spreads four neighbours further apart it stages narrower pieces (down to 16 bytes of a
  * row, spreads up to 3776 rows), and beyond that each position by itself, which reads every row four times.  A
  * dispersion sweep (rtlws_dedisp_delays) is far inside the first case; rtlws_dedisp_geometry says what a table gets.
+ * (The figures 23, 247 and 3776 follow from the tile's rule; tests/test_dedisp_forms_cpu.py holds them to it.)
  *
  * Refused with -1 (rtlws_dedisp_last_error() says why): nchan outside 4 .. 4096 or not a multiple of 4, ntrials
  * outside 1 .. 4096, a null table, a delay outside 0 .. 65535, nout < 0, in_stride < nchan or not a multiple of 4,

@@ -84,12 +84,58 @@ def delays(*args):
 
 # ---- what the suites share ----
 
+def _hashed_bits(nrows, width, seed):
+    """(the bit patterns of hashed_rows, the one hash bit they leave unused), uint32 [nrows, width] each"""
+    b = hash_bytes(4 * nrows * width, seed).astype(np.uint32).reshape(nrows, width, 4)
+    mant = (b[..., 0] << np.uint32(15)) | (b[..., 1] << np.uint32(7)) | (b[..., 2] >> np.uint32(1))
+    return ((np.uint32(117) + b[..., 3] % np.uint32(20)) << np.uint32(23)) | mant, b[..., 2] & np.uint32(1)
+
+
 def hashed_rows(nrows, width, seed):
     """float32 [nrows, width], non-negative, from the counter hash: 23 bits of mantissa and one of 20 binades each, so
     that the order of a sum's additions shows in its bits"""
-    b = hash_bytes(4 * nrows * width, seed).astype(np.uint32).reshape(nrows, width, 4)
-    mant = (b[..., 0] << np.uint32(15)) | (b[..., 1] << np.uint32(7)) | (b[..., 2] >> np.uint32(1))
-    bits = ((np.uint32(117) + b[..., 3] % np.uint32(20)) << np.uint32(23)) | mant
+    return _hashed_bits(nrows, width, seed)[0].view(np.float32)
+
+
+def signed_rows(nrows, width, seed):
+    """hashed_rows with the sign from a further bit of the hash: terms cancel, and the f64 bound is on the magnitudes"""
+    bits, sign = _hashed_bits(nrows, width, seed)
+    return (bits | (sign << np.uint32(31))).view(np.float32)
+
+
+NEG_ZERO, POS_INF, NEG_INF, QUIET_NAN = (np.uint32(x) for x in (0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000))
+
+
+def special_rows(nrows, width, seed):
+    """signed_rows (width even, at least 8) with what a sum of ordinary floats never meets, planted by the row: row j
+    draws a hash h and two different even positions a < b, and by h % 16 becomes
+      0   a cancelling row: every odd position holds the negative of the even one before it, so that the row's sum in
+          the header's order is +0 exactly;
+      1   subnormal throughout: every value keeps its sign and mantissa (bit patterns 1 .. 0x7FFFFF) and loses its exponent;
+      2   a cancelling row before a and subnormal from a on: the row's sum is the sum of its subnormals;
+      3   zeros throughout, -0.0 where the value was negative;
+      4   a cancelling row whose pair at a is -0.0 twice;
+      5   +Inf at a;    6  -Inf at b;    7  +Inf at a and -Inf at b;    8  a quiet NaN at a;
+      9   -0.0 at a and a subnormal at b among ordinary values (neither shows in a sum: they must not);
+      10 .. 15 as signed_rows left it.
+    A table that delays one position further than the rest of the row mixes the rows: an output takes that position
+    from another row than the rest, so that a subnormal row shows only where the other row is subnormal or zero there."""
+    assert width % 2 == 0 and width >= 8
+    bits = signed_rows(nrows, width, seed).view(np.uint32).copy()
+    h = hashed_ints(2 * nrows, (1 << 24) - 1, seed + 4099).astype(np.int64).reshape(nrows, 2)
+    kind = h[:, 0] % 16
+    pa = 2 * (h[:, 1] % (width // 2 - 1))                                          # even, below width - 2
+    pb = pa + 2 + 2 * ((h[:, 1] >> 12) % ((width - 2 - pa) // 2))                  # even, pa < pb <= width - 2
+    i = np.arange(width)[None, :]
+    subnormal = (bits & np.uint32(0x807FFFFF)) | np.uint32(1)
+    pairs = bits.copy()
+    pairs[:, 1::2] = pairs[:, 0::2] ^ NEG_ZERO
+    at_a, at_b = i == pa[:, None], i == pb[:, None]
+    for k, where, values in ((0, i >= 0, pairs), (1, i >= 0, subnormal), (2, i >= 0, np.where(i < pa[:, None], pairs, subnormal)),
+                             (3, i >= 0, bits & NEG_ZERO), (4, i >= 0, pairs), (4, at_a | (i == pa[:, None] + 1), NEG_ZERO),
+                             (5, at_a, POS_INF), (6, at_b, NEG_INF), (7, at_a, POS_INF), (7, at_b, NEG_INF), (8, at_a, QUIET_NAN),
+                             (9, at_a, NEG_ZERO), (9, at_b, subnormal)):
+        bits = np.where((kind == k)[:, None] & where, values, bits)
     return bits.view(np.float32)
 
 

@@ -270,7 +270,8 @@ def test_reference_on_itself():
     for i in reversed(range(nchan)):
         back = back + rows[:nout, i]
     assert not np.array_equal(back, dedisp_ref.dedisp_ref(rows, z, None, nout)[0])
-    # one kept position: that column, delayed, bit for bit
+    # one kept position: that column, delayed, bit for bit -- for non-negative data, as here: a kept -0.0 comes out +0.0
+    # (test_reference_on_signed_and_special_rows)
     d = dedisp_ref.random_table(ntrials, nchan, 250, seed=3)
     for i in (0, 7, nchan - 1):
         got = dedisp_ref.dedisp_ref(rows, d, dedisp_ref.one_kept(nchan, i), nout)
@@ -290,6 +291,51 @@ def test_reference_on_itself():
         err = np.abs(dedisp_ref.dedisp_ref(rows, d, m, nout).astype(np.float64) - dedisp_ref.dedisp_f64(rows, d, m, nout))
         b = dedisp_ref.bound(rows, d, m, nout)
         assert np.all(err <= b) and 0 < (err / b).max() < 1
+
+
+def _classes(out):
+    """(subnormal and not zero, +Inf, -Inf, NaN, +0.0, -0.0) of a float32 array, as boolean arrays"""
+    u = out.view(np.uint32)
+    return (((u & 0x7F800000) == 0) & ((u & 0x007FFFFF) != 0), u == 0x7F800000, u == 0xFF800000, np.isnan(out), u == 0, u == 0x80000000)
+
+
+def test_reference_on_signed_and_special_rows():
+    """The inputs of tests/test_dedisp_gpu.py::test_signed_and_special_rows, through the restatement alone: signed_rows
+    is hashed_rows with a sign, its sums cancel and keep the bound on the magnitudes; special_rows holds every class it
+    says, and on each of the six tables the restatement's outputs hold subnormals, both infinities, NaN of Inf - Inf
+    where no term is NaN, +0 of terms that are not zero, and never the bits of -0.0."""
+    import dedisp_form_cases as forms
+    plain, signed = dedisp_ref.hashed_rows(300, 36, seed=5), dedisp_ref.signed_rows(300, 36, seed=5)
+    assert signed.dtype == np.float32 and np.array_equal(np.abs(signed).view(np.uint32), plain.view(np.uint32))
+    assert 0.4 < np.signbit(signed).mean() < 0.6
+    for which, case in enumerate(forms.SIX_FORMS):
+        delays = forms.table(case)
+        need = dedisp_ref.rows_needed(delays, None, forms.NOUT)
+        rows = dedisp_ref.signed_rows(need, forms.NCHAN, seed=which + 1)
+        got, got64 = dedisp_ref.dedisp_both(rows, delays, None, forms.NOUT)
+        err, b = np.abs(got.astype(np.float64) - got64), dedisp_ref.bound(np.abs(rows), delays, None, forms.NOUT)
+        assert np.all(err <= b) and 0 < (err / b).max() < 1
+        assert (np.abs(got64) < 0.05 * b * 2.0 ** 24 / forms.NCHAN).any()         # cancellation: a sum far below its terms
+
+        rows = dedisp_ref.special_rows(need, forms.NCHAN, seed=which + 1)
+        assert rows.shape == (need, forms.NCHAN) and rows.dtype == np.float32
+        assert all(c.any() for c in _classes(rows)), forms.case_id(case)
+        assert np.array_equal(rows.view(np.uint32)[np.isnan(rows)], np.full(np.isnan(rows).sum(), 0x7FC00000, np.uint32))
+        with np.errstate(invalid="ignore"):
+            out = dedisp_ref.dedisp_ref(rows, delays, None, forms.NOUT)
+        sub, pinf, ninf, nan, pzero, nzero = _classes(out)
+        read_nan = dedisp_ref.dedisp_f64(np.isnan(rows).astype(np.float32), delays, None, forms.NOUT) > 0
+        not_zero = dedisp_ref.dedisp_f64((rows != 0).astype(np.float32), delays, None, forms.NOUT) > 0
+        counts = tuple(int(c.sum()) for c in (sub, pinf, ninf, nan & ~read_nan, pzero & not_zero, nzero))
+        print("%s: subnormal %d, +Inf %d, -Inf %d, NaN of Inf - Inf %d, +0 of cancellation %d, -0 %d of %d outputs"
+              % ((forms.case_id(case),) + counts + (out.size,)))
+        # one trial a workgroup delays a position of every output: a row's pairs then cancel only by chance
+        assert all(counts[:4]) and (counts[4] or case.plan_per == 1) and counts[5] == 0, (forms.case_id(case), counts)
+        assert read_nan.any() and np.all(nan[read_nan]) and np.isfinite(out).mean() > 0.5
+    # the header's acc = +0.0f start: one kept position holding -0.0 gives +0.0, not that column bit for bit
+    rows = np.full((5, 4), -0.0, np.float32)
+    out = dedisp_ref.dedisp_ref(rows, np.zeros((2, 4), np.int32), dedisp_ref.one_kept(4, 2), 5)
+    assert np.signbit(rows).all() and not out.view(np.uint32).any()
 
 
 def test_tables_of_the_suites():

@@ -1,9 +1,13 @@
 """GPU suite of include/rtlws_dedisp.h (librtlws_dedisp.so) against its numpy restatement (tests/dedisp_ref.py): every
 comparison with it bit for bit on uint32 views, the f64 bound on every case, padding columns, rows behind rows_needed
-and the output's padding untouched, runs from a later row, the spectrometer's rows end to end, and graph capture."""
+and the output's padding untouched, runs from a later row, the spectrometer's rows end to end, and graph capture; then
+the plan on both sides of every border of its forms (tests/dedisp_form_cases.py), signed rows, rows that hold -0.0,
+subnormals, infinities and NaN, NaN and -Inf under the mask, the limits of the table, and one plan run many times, over
+a sub-band of a wider waterfall and beside another plan on another stream."""
 import numpy as np
 import pytest
 
+import dedisp_form_cases as forms
 import dedisp_ref
 from dedisp_ref import DELAY_SETS
 
@@ -230,3 +234,190 @@ def test_capture_and_replay(built):
     assert torch.equal(eager, first)
     plan.close()
     eng.close()
+
+
+# ---- the borders of the plan, signed and special values, the limits, one plan many times ------------------------------
+
+def _bits_differ(got, want):
+    """where two float32 arrays differ: bit for bit, but NaN by place and not by payload (the default NaN of the host's
+    additions and of the device's differ in the sign bit)"""
+    nan = np.isnan(want)
+    return np.argwhere((np.isnan(got) != nan) | (~nan & (got.view(np.uint32) != want.view(np.uint32))))
+
+
+def _assert_bits(got, want, what=None):
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (what, np.argwhere(got.view(np.uint32) != want.view(np.uint32))[:5])
+
+
+def _plan_of(built, case, delays, mask=None):
+    """The geometry of a table of tests/dedisp_form_cases.py is the form its case names (tests/test_dedisp_forms_cpu.py
+    says the same without a GPU); -> rows needed"""
+    rc, blocks, threads, lds, tile, per, most = built.dedisp_geometry(delays, mask, forms.NOUT)
+    want = forms.form(case.plan_spread, case.plan_per)
+    assert (rc, threads, tile, per, lds, most) == (0, 256, TILE, case.plan_per, want[1], int(delays.max())), (per, lds, most)
+    assert blocks == -(-forms.NOUT // TILE) * -(-case.ntrials // per)
+    return forms.NOUT + most
+
+
+@pytest.mark.parametrize("case", forms.CASES, ids=[forms.case_id(c) for c in forms.CASES])
+def test_every_border_of_the_plan(built, engine, case):
+    """A table whose plan stands on one side of a border of its forms, 36 positions (a last chunk of one quad behind
+    every chunk width), tile_out + 1 outputs: with no mask and with one that keeps the delayed position, bit for bit;
+    NaN in the padding columns and behind rows_needed"""
+    delays = forms.table(case)
+    need = _plan_of(built, case, delays)
+    seed = forms.CASES.index(case) + 1
+    rows = np.full((need + 3, forms.NCHAN + 4), np.nan, np.float32)
+    rows[:need, :forms.NCHAN] = dedisp_ref.pooled_rows(need, forms.NCHAN, seed)
+    mask = forms.masks(case)[0][1]
+    assert _plan_of(built, case, delays, mask) == need
+    for m in (None, mask):
+        got = engine.dedisp(rows, delays, m, nout=forms.NOUT, in_stride=forms.NCHAN + 4)
+        _assert_bits(got, dedisp_ref.dedisp_ref(rows, delays, m, forms.NOUT), "no mask" if m is None else "masked")
+
+
+SIX = pytest.mark.parametrize("case", forms.SIX_FORMS, ids=[forms.case_id(c) for c in forms.SIX_FORMS])
+
+
+@SIX
+def test_signed_and_special_rows(built, engine, case):
+    """Terms of both signs: bit for bit, and within the bound on the magnitudes of the f64 sum.  Rows that hold -0.0,
+    subnormals, +Inf, -Inf and a quiet NaN (tests/test_dedisp_cpu.py::test_reference_on_signed_and_special_rows says what
+    the sums then hold): NaN exactly where the restatement has NaN, every other output bit for bit, so a planted value
+    reaches the (t, n) that read it and no other"""
+    which = forms.SIX_FORMS.index(case)
+    delays = forms.table(case)
+    need = _plan_of(built, case, delays)
+    rows = dedisp_ref.signed_rows(need, forms.NCHAN, seed=which + 1)
+    got = engine.dedisp(rows, delays, nout=forms.NOUT)
+    want, want64 = dedisp_ref.dedisp_both(rows, delays, None, forms.NOUT)
+    _assert_bits(got, want)
+    assert np.all(np.abs(got.astype(np.float64) - want64) <= dedisp_ref.bound(np.abs(rows), delays, None, forms.NOUT))
+
+    rows = dedisp_ref.special_rows(need, forms.NCHAN, seed=which + 1)
+    got = engine.dedisp(rows, delays, nout=forms.NOUT)
+    with np.errstate(invalid="ignore"):
+        want = dedisp_ref.dedisp_ref(rows, delays, None, forms.NOUT)
+    differ = _bits_differ(got, want)
+    assert not len(differ), (differ[:5], got[tuple(differ[0])], want[tuple(differ[0])])
+    assert np.array_equal(np.isfinite(got), np.isfinite(want)) and np.array_equal(np.isnan(got), np.isnan(want))
+    assert not (got.view(np.uint32) == 0x80000000).any()
+
+
+@SIX
+def test_masked_positions_are_never_added(built, engine, case):
+    """What the mask leaves out may hold anything: with NaN and with -Inf in those columns the outputs are finite and
+    bit for bit the restatement of the rows without them, under a random mask, one that leaves out a position of every
+    quad and one that leaves out whole quads"""
+    which = forms.SIX_FORMS.index(case)
+    delays = forms.table(case)
+    need = _plan_of(built, case, delays)
+    clean = dedisp_ref.signed_rows(need, forms.NCHAN, seed=which + 11)
+    for name, mask in forms.masks(case):
+        assert _plan_of(built, case, delays, mask) == need
+        want = dedisp_ref.dedisp_ref(clean, delays, mask, forms.NOUT)
+        assert np.isfinite(want).all()
+        for fill in (np.nan, -np.inf):
+            rows = clean.copy()
+            rows[:, mask == 0] = fill
+            got = engine.dedisp(rows, delays, mask, nout=forms.NOUT)
+            assert np.isfinite(got).all(), (name, fill)
+            _assert_bits(got, want, (name, fill))
+
+
+def _limit(name):
+    """(table, trials a workgroup, LDS bytes, nout) at a limit of the header"""
+    t, i = np.arange(4096)[:, None], np.arange(4096)[None, :]
+    if name == "every-delay-65535":              # groups of 8 with a base of 65535
+        return np.full((9, 8), 65535, np.int32), 8, forms.SMALL_LDS, forms.NOUT
+    if name == "0-and-65535-in-one-quad":        # every position by itself
+        return np.array([[0, 65535, 0, 65535], [65535, 0, 65535, 65535]], np.int32), 1, forms.SMALL_LDS, forms.NOUT
+    if name in ("4096-trials", "4093-trials"):   # 512 groups of 8 that spread 23, the last one of five trials
+        return ((t[:int(name[:4])] + i[:, :4]) % 24).astype(np.int32), 8, forms.SMALL_LDS, forms.NOUT
+    assert name == "4096-trials-of-4096"
+    return ((t + i) % 7).astype(np.int32), 8, forms.SMALL_LDS, 1
+
+
+@pytest.mark.parametrize("name", ["every-delay-65535", "0-and-65535-in-one-quad", "4096-trials", "4093-trials", "4096-trials-of-4096"])
+def test_the_limits(built, engine, name):
+    """The largest delay, the most trials and the largest table of the header, launched: bit for bit"""
+    delays, per, lds, nout = _limit(name)
+    ntrials, nchan = delays.shape
+    geo = built.dedisp_geometry(delays, None, nout)
+    assert geo == (0, -(-nout // TILE) * -(-ntrials // per), 256, lds, TILE, per, int(delays.max())), geo
+    need = dedisp_ref.rows_needed(delays, None, nout)
+    assert need * nchan * 4 <= (9 << 18) and (nchan < 4096 or need <= 8)          # about 2 MB of rows at the most
+    rows = dedisp_ref.pooled_rows(need, nchan, seed=len(name))
+    got = engine.dedisp(rows, delays, nout=nout)
+    want = dedisp_ref.dedisp_ref(rows, delays, None, nout)
+    assert got.shape == (ntrials, nout)
+    _assert_bits(got[-1:], want[-1:], "the last trial")
+    _assert_bits(got[8 * ((ntrials - 1) // 8):], want[8 * ((ntrials - 1) // 8):], "the last group")
+    _assert_bits(got, want)
+
+
+def _on_device(torch, host):
+    return torch.from_numpy(np.ascontiguousarray(host)).to(torch.device("cuda", 0))
+
+
+@pytest.mark.parametrize("what", ["every-nout", "a-sub-band", "two-plans-two-streams"])
+def test_one_plan_many_runs(built, engine, what):
+    """rtlws_dedisp_plan directly, on torch buffers.  One plan at nout 1, tile_out and 2 tile_out + 3 in turn into one
+    preset buffer of a wider out_stride: each run is the restatement and leaves the padding as it was.  A plan of 16
+    positions over columns 16 .. 31 and 48 .. 63 of a waterfall 64 wide whose other columns hold NaN: the restatement of
+    the slice.  Two plans of different tables, shapes and masks alive at once, their runs interleaved on two streams."""
+    import torch
+    handle = built.torch_stream_handle
+    if what == "every-nout":
+        case = forms.SIX_FORMS[2]
+        delays, mask = forms.table(case), forms.masks(case)[1][1]
+        nouts, width = (1, TILE, 2 * TILE + 3), 2 * TILE + 8
+        rows_host = dedisp_ref.pooled_rows(dedisp_ref.rows_needed(delays, mask, nouts[-1]), forms.NCHAN, seed=21)
+        rows, out = _on_device(torch, rows_host), _on_device(torch, np.full((case.ntrials, width), FILL, np.float32))
+        plan = built.DedispPlan(engine, delays, mask)
+        for nout in nouts:
+            assert plan.rows_needed(nout) == dedisp_ref.rows_needed(delays, mask, nout) <= rows_host.shape[0]
+            plan.run(rows.data_ptr(), nout, out.data_ptr(), out_stride=width, stream=handle())
+            torch.cuda.synchronize()
+            got = out.cpu().numpy()
+            _assert_bits(np.ascontiguousarray(got[:, :nout]), dedisp_ref.dedisp_ref(rows_host, delays, mask, nout), nout)
+            assert np.all(got[:, nout:].view(np.uint32) == FILL.view(np.uint32)), nout
+        plan.close()
+    elif what == "a-sub-band":
+        delays, mask, nout = dedisp_ref.random_table(9, 16, 30, seed=6), dedisp_ref.random_mask(16, 6), TILE + 1
+        assert built.dedisp_geometry(delays, mask, nout)[5] == 8
+        need = dedisp_ref.rows_needed(delays, mask, nout)
+        wide = np.full((need, 64), np.nan, np.float32)
+        for k in (1, 3):
+            wide[:, 16 * k:16 * k + 16] = dedisp_ref.pooled_rows(need, 16, seed=30 + k)
+        rows, out = _on_device(torch, wide), _on_device(torch, np.zeros((9, nout), np.float32))
+        plan = built.DedispPlan(engine, delays, mask)
+        for k in (1, 3):
+            out.fill_(float(FILL))
+            plan.run(rows.data_ptr() + 4 * 16 * k, nout, out.data_ptr(), in_stride=64, stream=handle())
+            torch.cuda.synchronize()
+            _assert_bits(out.cpu().numpy(), dedisp_ref.dedisp_ref(wide[:, 16 * k:16 * k + 16], delays, mask, nout), k)
+        plan.close()
+    else:
+        nout, reps = TILE + 1, 3
+        case = forms.SIX_FORMS[0]
+        tables = ((forms.table(case), forms.masks(case)[0][1]), (dedisp_ref.random_table(5, 20, 300, seed=8), None))
+        assert [built.dedisp_geometry(d, m, nout)[5] for d, m in tables] == [8, 1]
+        hosts = [dedisp_ref.pooled_rows(dedisp_ref.rows_needed(d, m, nout), d.shape[1], seed=40 + j) for j, (d, m) in enumerate(tables)]
+        rows = [_on_device(torch, h) for h in hosts]
+        outs = [[_on_device(torch, np.full((d.shape[0], nout), FILL, np.float32)) for _ in range(reps)] for d, _ in tables]
+        plans = [built.DedispPlan(engine, d, m) for d, m in tables]
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        for s in streams:
+            s.wait_stream(torch.cuda.current_stream())
+        for rep in range(reps):
+            for j in (0, 1):
+                plans[j].run(rows[j].data_ptr(), nout, outs[j][rep].data_ptr(), stream=handle(streams[j]))
+        torch.cuda.synchronize()
+        for j, (d, m) in enumerate(tables):
+            want = dedisp_ref.dedisp_ref(hosts[j], d, m, nout)
+            for rep in range(reps):
+                _assert_bits(outs[j][rep].cpu().numpy(), want, (j, rep))
+        for plan in plans:
+            plan.close()
