@@ -111,12 +111,13 @@ def _roots(n, step, count):
     return (np.cos(a).astype(np.float64) + 1j * np.sin(a).astype(np.float64))
 
 
-def four_step(x):
-    """N = N1 N2, n = N2 n1 + n2, k = k1 + N1 k2, W_N^j = twh[j >> 10] * twl[j & 1023] (spectrum_long.hip)."""
+def four_step(x, twl=None):
+    """N = N1 N2, n = N2 n1 + n2, k = k1 + N1 k2, W_N^j = twh[j >> 10] * twl[j & 1023] (spectrum_long.hip).
+    twl: another low table than the library's (tests/test_long_borders_cpu.py puts a defect there)."""
     N = x.size
     m = N.bit_length() - 1
     N1, N2 = 1 << lk.log2_n1(m), 1 << lk.log2_n2(m)
-    twl, twh = _roots(N, 1, 1024), _roots(N, 1024, N // 1024)
+    twl, twh = _roots(N, 1, 1024) if twl is None else twl, _roots(N, 1024, N // 1024)
     a = np.fft.fft(x.reshape(N1, N2), axis=0)                          # [k1, n2]: the N1-point transforms over n1
     j = np.arange(N1)[:, None] * np.arange(N2)[None, :]                # n2 k1 < N
     ws = a * (twh[j >> 10] * twl[j & 1023])                            # the workspace, element (k1, n2)
