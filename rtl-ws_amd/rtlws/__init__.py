@@ -19,6 +19,7 @@ fail loudly.
   PfbBfPlan, Engine.pfbbf, Engine.pfbbf_power  include/rtlws_pfbbf.h (polyphase beamformer: 1-4 weighted beams of 1-8 captures in one launch)
   PfbSkPlan, Engine.pfbsk  include/rtlws_pfbsk.h (polyphase spectrometer with spectral-kurtosis excision: the power over the kept ones of L sub-integrations, one launch)
   DedispPlan, Engine.dedisp  include/rtlws_dedisp.h (incoherent dedispersion of f32 rows: every trial of a delay table in one launch)
+  PulsePlan, Engine.pulse  include/rtlws_pulse.h (single-pulse search: boxcar peaks of a table of widths and the moments per segment, one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -50,6 +51,7 @@ PFBXC_LIB = os.path.join(LIB_DIR, "librtlws_pfbxc.so")   # include/rtlws_pfbxc.h
 PFBBF_LIB = os.path.join(LIB_DIR, "librtlws_pfbbf.so")   # include/rtlws_pfbbf.h
 PFBSK_LIB = os.path.join(LIB_DIR, "librtlws_pfbsk.so")   # include/rtlws_pfbsk.h
 DEDISP_LIB = os.path.join(LIB_DIR, "librtlws_dedisp.so") # include/rtlws_dedisp.h
+PULSE_LIB = os.path.join(LIB_DIR, "librtlws_pulse.so")   # include/rtlws_pulse.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -150,6 +152,10 @@ PFBSK_MAX_K_AVG, PFBSK_MAX_NSUB = 65536, 65535
 DEDISP_SYMBOLS = ["rtlws_dedisp_supported", "rtlws_dedisp_delays", "rtlws_dedisp_geometry", "rtlws_dedisp_open",
                   "rtlws_dedisp_rows_needed", "rtlws_dedisp_run", "rtlws_dedisp_close", "rtlws_dedisp_last_error"]
 DEDISP_MIN_NCHAN, DEDISP_MAX_NCHAN, DEDISP_MAX_TRIALS, DEDISP_MAX_DELAY = 4, 4096, 4096, 65535
+PULSE_SYMBOLS = ["rtlws_pulse_supported", "rtlws_pulse_geometry", "rtlws_pulse_open", "rtlws_pulse_samples_needed",
+                 "rtlws_pulse_segments", "rtlws_pulse_run", "rtlws_pulse_snr", "rtlws_pulse_close", "rtlws_pulse_last_error"]
+PULSE_MAX_WIDTHS, PULSE_MAX_WIDTH, PULSE_MIN_SEG, PULSE_MAX_SEG, PULSE_MAX_TRIALS, PULSE_MAX_NOUT = 16, 1024, 64, 1 << 20, 65536, 1 << 30
+PULSE_GUARD = 8            # Engine.pulse(fill=...): preset elements behind every output array
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -727,6 +733,51 @@ def dedisp_geometry(delays, mask=None, nout=0):
     return (rc,) + tuple(x.value for x in v)
 
 
+_lp = C.POINTER(C.c_long)
+_PULSE_PROTOTYPES = {
+    "rtlws_pulse_supported": [_i, _vp, _l], "rtlws_pulse_geometry": [_i, _vp, _l, _i, _l, _ip, _ip, _ip, _ip, _ip, _lp],
+    "rtlws_pulse_open": ([_vp, _i, _vp, _l], _vp), "rtlws_pulse_samples_needed": ([_vp, _l], _l),
+    "rtlws_pulse_segments": ([_vp, _l], _l), "rtlws_pulse_run": [_vp, _vp, _l, _i, _l, _vp, _vp, _vp, _vp],
+    "rtlws_pulse_snr": ([C.c_double, _i, C.c_double, C.c_double, _l], C.c_double),
+    "rtlws_pulse_close": ([_vp], None), "rtlws_pulse_last_error": ([], _str)}
+
+
+def pulse_lib():
+    """librtlws_pulse.so (include/rtlws_pulse.h); it needs librtlws_hip.so's engine."""
+    return _satellite(PULSE_LIB, _PULSE_PROTOTYPES)
+
+
+def pulse_last_error():
+    return pulse_lib().rtlws_pulse_last_error().decode()
+
+
+def _pulse_widths(widths):
+    """The table as the library reads it: int32 [nwidths], or None (a NULL table)."""
+    return None if widths is None else np.ascontiguousarray(widths, dtype=np.int32).reshape(-1)
+
+
+def pulse_supported(widths, seg):
+    """rtlws_pulse_supported.  No GPU needed."""
+    widths = _pulse_widths(widths)
+    return pulse_lib().rtlws_pulse_supported(0 if widths is None else widths.size, None if widths is None else _p(widths), int(seg))
+
+
+def pulse_geometry(widths, seg, ntrials=1, nout=0):
+    """rtlws_pulse_geometry: (rc, workgroups, threads, LDS bytes, outputs per tile, levels kept, segments).  No GPU
+    needed."""
+    widths = _pulse_widths(widths)
+    v = [C.c_int(0) for _ in range(5)]
+    nseg = C.c_long(0)
+    rc = pulse_lib().rtlws_pulse_geometry(0 if widths is None else widths.size, None if widths is None else _p(widths), int(seg),
+                                          int(ntrials), int(nout), *([C.byref(x) for x in v] + [C.byref(nseg)]))
+    return (rc,) + tuple(x.value for x in v) + (nseg.value,)
+
+
+def pulse_snr(peak, width, sum1, sum2, count):
+    """rtlws_pulse_snr: (peak - width mean) / sqrt(width var) in double, NaN where it is not defined.  No GPU needed."""
+    return pulse_lib().rtlws_pulse_snr(float(peak), int(width), float(sum1), float(sum2), int(count))
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -1113,6 +1164,30 @@ class DedispPlan(_Plan):
         """One launch: trial t at d_out + t * out_stride elements (f32), row j of the input at d_rows + j * in_stride."""
         return self._call("run", check, self._ptr(d_rows), int(self.nchan if in_stride is None else in_stride), int(nout),
                           self._ptr(d_out), int(nout if out_stride is None else out_stride), stream)
+
+
+class PulsePlan(_Plan):
+    """rtlws_pulse_plan* of include/rtlws_pulse.h: the table of widths (int32 [nwidths]) on the engine's device in the
+    kernel's form, the kernel loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's
+    text."""
+    _name, _lib = "pulse", staticmethod(pulse_lib)
+
+    def __init__(self, eng, widths, seg):
+        widths = _pulse_widths(widths)
+        self.nwidths, self.seg = widths.size, int(seg)
+        self._open(eng, self.nwidths, _p(widths), self.seg)
+
+    def samples_needed(self, nout):
+        return self._fn("samples_needed")(self.h, int(nout))
+
+    def segments(self, nout):
+        return self._fn("segments")(self.h, int(nout))
+
+    def run(self, d_in, in_stride, ntrials, nout, d_peak, d_at, d_mom=None, stream=None, check=True):
+        """One launch: trial t at d_in + t * in_stride elements; d_peak and d_at [ntrials, nwidths, nseg] (f32, int32),
+        d_mom [ntrials, nseg, 2] (f64) or None."""
+        return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nout), self._ptr(d_peak),
+                          self._ptr(d_at), self._ptr(d_mom), stream)
 
 
 class PfbXcPlan(_PolyphasePlan):
@@ -1525,6 +1600,47 @@ class Engine:
             d_rows.free()
             d_out.free()
         return out if out_stride is not None else out[:, :nout]
+
+    # -- include/rtlws_pulse.h: host series in, (peaks, places, moments) out ----
+    def pulse(self, series, widths, seg, nout=None, in_stride=None, want_moments=True, fill=None):
+        """rtlws_pulse_run: series float32 [ntrials, nsamples] (with in_stride: [ntrials, in_stride], the padding as the
+        caller left it), widths int32 [nwidths] -> (float32 [ntrials, nwidths, nseg] the peaks, int32 of that shape
+        their places, float64 [ntrials, nseg, 2] the moments, or None without want_moments).  nout None: as many as the
+        samples hold.  With `fill` (a float32) the three come back as the whole flat buffers, PULSE_GUARD elements
+        longer than the outputs, every element preset to fill (peaks), to fill's bits (places) and to float64(fill)
+        (moments), so that a caller sees what the run left untouched; without want_moments the run gets a NULL d_mom and
+        the preset moments buffer comes back as it was."""
+        plan = PulsePlan(self, widths, seg)
+        series = np.ascontiguousarray(series, dtype=np.float32)
+        if in_stride is not None:
+            series = series.reshape(-1, int(in_stride))
+        assert series.ndim == 2, "the series are [ntrials, nsamples]"
+        samples = series.shape[1]
+        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
+            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        ntrials, width = series.shape
+        if nout is None:
+            nout = max(samples - (plan.samples_needed(1) - 1), 0)
+        nout = int(nout)
+        assert samples >= plan.samples_needed(nout), "fewer samples than rtlws_pulse_samples_needed"
+        nseg, guard = plan.segments(nout), 0 if fill is None else PULSE_GUARD
+        preset = np.float32(0.0 if fill is None else fill)
+        hosts = [np.full(ntrials * plan.nwidths * nseg + guard, preset, np.float32),
+                 np.full(ntrials * plan.nwidths * nseg + guard, preset.view(np.int32), np.int32),
+                 np.full(ntrials * nseg * 2 + guard, np.float64(preset), np.float64)]
+        bufs = [self.upload(series) if series.nbytes else self.alloc(16)] + [self.upload(h) if h.nbytes else self.alloc(16) for h in hosts]
+        try:
+            plan.run(bufs[0], width, ntrials, nout, bufs[1], bufs[2], bufs[3] if want_moments else None)
+            self.sync()
+            peak, at, mom = [self.download(b, h.dtype, h.shape) if h.nbytes else h for b, h in zip(bufs[1:], hosts)]
+        finally:
+            plan.close()
+            for b in bufs:
+                b.free()
+        if fill is not None:
+            return peak, at, mom
+        return (peak.reshape(ntrials, plan.nwidths, nseg), at.reshape(ntrials, plan.nwidths, nseg),
+                mom.reshape(ntrials, nseg, 2) if want_moments else None)
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
     def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
