@@ -20,6 +20,7 @@ fail loudly.
   PfbSkPlan, Engine.pfbsk  include/rtlws_pfbsk.h (polyphase spectrometer with spectral-kurtosis excision: the power over the kept ones of L sub-integrations, one launch)
   DedispPlan, Engine.dedisp  include/rtlws_dedisp.h (incoherent dedispersion of f32 rows: every trial of a delay table in one launch)
   PulsePlan, Engine.pulse  include/rtlws_pulse.h (single-pulse search: boxcar peaks of a table of widths and the moments per segment, one launch)
+  FoldPlan, Engine.fold  include/rtlws_fold.h (epoch folding: the profiles of every trial at a table of periods, per sub-integration, one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -52,6 +53,7 @@ PFBBF_LIB = os.path.join(LIB_DIR, "librtlws_pfbbf.so")   # include/rtlws_pfbbf.h
 PFBSK_LIB = os.path.join(LIB_DIR, "librtlws_pfbsk.so")   # include/rtlws_pfbsk.h
 DEDISP_LIB = os.path.join(LIB_DIR, "librtlws_dedisp.so") # include/rtlws_dedisp.h
 PULSE_LIB = os.path.join(LIB_DIR, "librtlws_pulse.so")   # include/rtlws_pulse.h
+FOLD_LIB = os.path.join(LIB_DIR, "librtlws_fold.so")     # include/rtlws_fold.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -156,6 +158,10 @@ PULSE_SYMBOLS = ["rtlws_pulse_supported", "rtlws_pulse_geometry", "rtlws_pulse_o
                  "rtlws_pulse_segments", "rtlws_pulse_run", "rtlws_pulse_snr", "rtlws_pulse_close", "rtlws_pulse_last_error"]
 PULSE_MAX_WIDTHS, PULSE_MAX_WIDTH, PULSE_MIN_SEG, PULSE_MAX_SEG, PULSE_MAX_TRIALS, PULSE_MAX_NOUT = 16, 1024, 64, 1 << 20, 65536, 1 << 30
 PULSE_GUARD = 8            # Engine.pulse(fill=...): preset elements behind every output array
+FOLD_SYMBOLS = ["rtlws_fold_supported", "rtlws_fold_geometry", "rtlws_fold_open", "rtlws_fold_subints", "rtlws_fold_run",
+                "rtlws_fold_step", "rtlws_fold_phase_at", "rtlws_fold_chi2", "rtlws_fold_close", "rtlws_fold_last_error"]
+FOLD_MAX_PERIODS, FOLD_MIN_BINS, FOLD_MAX_BINS, FOLD_MIN_SUB, FOLD_MAX_SUB, FOLD_MAX_TRIALS, FOLD_MAX_NSAMP = 4096, 2, 256, 64, 1 << 24, 65536, 1 << 30
+FOLD_GUARD = 8             # Engine.fold(fill=...): preset elements behind both output arrays
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -778,6 +784,66 @@ def pulse_snr(peak, width, sum1, sum2, count):
     return pulse_lib().rtlws_pulse_snr(float(peak), int(width), float(sum1), float(sum2), int(count))
 
 
+_u64 = C.c_uint64
+_FOLD_PROTOTYPES = {
+    "rtlws_fold_supported": [_i, _vp, _vp, _i, _l], "rtlws_fold_geometry": [_i, _i, _l, _i, _l, _ip, _ip, _ip, _ip, _ip, _lp],
+    "rtlws_fold_open": ([_vp, _i, _vp, _vp, _i, _l], _vp), "rtlws_fold_subints": ([_vp, _l], _l),
+    "rtlws_fold_run": [_vp, _vp, _l, _i, _l, _vp, _vp, _vp], "rtlws_fold_step": ([C.c_double], _u64),
+    "rtlws_fold_phase_at": ([_u64, _u64, _l], _u64),
+    "rtlws_fold_chi2": ([_vp, _vp, _i, C.c_double, C.c_double, _l], C.c_double),
+    "rtlws_fold_close": ([_vp], None), "rtlws_fold_last_error": ([], _str)}
+
+
+def fold_lib():
+    """librtlws_fold.so (include/rtlws_fold.h); it needs librtlws_hip.so's engine."""
+    return _satellite(FOLD_LIB, _FOLD_PROTOTYPES)
+
+
+def fold_last_error():
+    return fold_lib().rtlws_fold_last_error().decode()
+
+
+def _fold_table(values):
+    """A table as the library reads it: uint64 [nperiods], or None (a NULL table)."""
+    return None if values is None else np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+
+
+def fold_supported(steps, phases, nbins, sub):
+    """rtlws_fold_supported of two tables uint64 [nperiods] (nperiods: the steps').  No GPU needed."""
+    steps, phases = _fold_table(steps), _fold_table(phases)
+    return fold_lib().rtlws_fold_supported(0 if steps is None else steps.size, None if steps is None else _p(steps),
+                                           None if phases is None else _p(phases), int(nbins), int(sub))
+
+
+def fold_geometry(nperiods, nbins, sub, ntrials=1, nsamp=0):
+    """rtlws_fold_geometry: (rc, workgroups, threads, LDS bytes, samples per tile, wavefronts per workgroup, sub-integrations).
+    No GPU needed."""
+    v = [C.c_int(0) for _ in range(5)]
+    nsub = C.c_long(0)
+    rc = fold_lib().rtlws_fold_geometry(int(nperiods), int(nbins), int(sub), int(ntrials), int(nsamp),
+                                        *([C.byref(x) for x in v] + [C.byref(nsub)]))
+    return (rc,) + tuple(x.value for x in v) + (nsub.value,)
+
+
+def fold_step(period_in_samples):
+    """rtlws_fold_step: the integer nearest to 2^64 / P, exactly; 0 outside 2 .. 2^32.  No GPU needed."""
+    return int(fold_lib().rtlws_fold_step(float(period_in_samples)))
+
+
+def fold_phase_at(step, phi0, n0):
+    """rtlws_fold_phase_at: (phi0 + n0 step) mod 2^64.  No GPU needed."""
+    return int(fold_lib().rtlws_fold_phase_at(int(step), int(phi0), int(n0)))
+
+
+def fold_chi2(prof, hits, sum1, sum2, count):
+    """rtlws_fold_chi2 of one profile float32 [nbins] and its hits uint32 [nbins], in double; NaN where it is not defined.
+    No GPU needed."""
+    prof, hits = np.ascontiguousarray(prof, dtype=np.float32).reshape(-1), np.ascontiguousarray(hits, dtype=np.uint32).reshape(-1)
+    assert prof.size == hits.size
+    return fold_lib().rtlws_fold_chi2(_p(prof) if prof.size else None, _p(hits) if hits.size else None, prof.size, float(sum1),
+                                      float(sum2), int(count))
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -1188,6 +1254,28 @@ class PulsePlan(_Plan):
         d_mom [ntrials, nseg, 2] (f64) or None."""
         return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nout), self._ptr(d_peak),
                           self._ptr(d_at), self._ptr(d_mom), stream)
+
+
+class FoldPlan(_Plan):
+    """rtlws_fold_plan* of include/rtlws_fold.h: the steps and the phases (uint64 [nperiods] each) on the engine's device,
+    the kernel of nbins' block shape loaded.  eng may be None (as a C caller's NULL engine): open then fails with the
+    library's text."""
+    _name, _lib = "fold", staticmethod(fold_lib)
+
+    def __init__(self, eng, steps, phases, nbins, sub):
+        steps, phases = _fold_table(steps), _fold_table(phases)
+        assert steps.size == phases.size, "a phase for every step"
+        self.nperiods, self.nbins, self.sub = steps.size, int(nbins), int(sub)
+        self._open(eng, self.nperiods, _p(steps), _p(phases), self.nbins, self.sub)
+
+    def subints(self, nsamp):
+        return self._fn("subints")(self.h, int(nsamp))
+
+    def run(self, d_in, in_stride, ntrials, nsamp, d_prof, d_hits=None, stream=None, check=True):
+        """One launch: trial t at d_in + t * in_stride elements; d_prof [ntrials, nperiods, nsub, nbins] (f32), d_hits
+        [nperiods, nsub, nbins] (uint32) or None."""
+        return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_prof),
+                          self._ptr(d_hits), stream)
 
 
 class PfbXcPlan(_PolyphasePlan):
@@ -1641,6 +1729,43 @@ class Engine:
             return peak, at, mom
         return (peak.reshape(ntrials, plan.nwidths, nseg), at.reshape(ntrials, plan.nwidths, nseg),
                 mom.reshape(ntrials, nseg, 2) if want_moments else None)
+
+    # -- include/rtlws_fold.h: host series in, (profiles, hits) out ----
+    def fold(self, series, steps, phases, nbins, sub, nsamp=None, in_stride=None, want_hits=True, fill=None):
+        """rtlws_fold_run: series float32 [ntrials, nsamp] (with in_stride: [ntrials, in_stride], the padding as the caller
+        left it), steps and phases uint64 [nperiods] -> (float32 [ntrials, nperiods, nsub, nbins] the profiles, uint32
+        [nperiods, nsub, nbins] the hits, or None without want_hits).  nsamp None: the samples the series hold.  With
+        `fill` (a float32) the two come back as the whole flat buffers, FOLD_GUARD elements longer than the outputs,
+        every element preset to fill (profiles) and to fill's bits (hits), so that a caller sees what the run left
+        untouched; without want_hits the run gets a NULL d_hits and the preset hits buffer comes back as it was."""
+        plan = FoldPlan(self, steps, phases, nbins, sub)
+        series = np.ascontiguousarray(series, dtype=np.float32)
+        if in_stride is not None:
+            series = series.reshape(-1, int(in_stride))
+        assert series.ndim == 2, "the series are [ntrials, nsamp]"
+        samples = series.shape[1]
+        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
+            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        ntrials, width = series.shape
+        nsamp = samples if nsamp is None else int(nsamp)
+        assert samples >= nsamp, "fewer samples than nsamp"
+        nsub, guard = plan.subints(nsamp), 0 if fill is None else FOLD_GUARD
+        preset = np.float32(0.0 if fill is None else fill)
+        hosts = [np.full(ntrials * plan.nperiods * nsub * plan.nbins + guard, preset, np.float32),
+                 np.full(plan.nperiods * nsub * plan.nbins + guard, preset.view(np.uint32), np.uint32)]
+        bufs = [self.upload(series) if series.nbytes else self.alloc(16)] + [self.upload(h) if h.nbytes else self.alloc(16) for h in hosts]
+        try:
+            plan.run(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2] if want_hits else None)
+            self.sync()
+            prof, hits = [self.download(b, h.dtype, h.shape) if h.nbytes else h for b, h in zip(bufs[1:], hosts)]
+        finally:
+            plan.close()
+            for b in bufs:
+                b.free()
+        if fill is not None:
+            return prof, hits
+        return (prof.reshape(ntrials, plan.nperiods, nsub, plan.nbins),
+                hits.reshape(plan.nperiods, nsub, plan.nbins) if want_hits else None)
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
     def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
