@@ -21,6 +21,7 @@ fail loudly.
   DedispPlan, Engine.dedisp  include/rtlws_dedisp.h (incoherent dedispersion of f32 rows: every trial of a delay table in one launch)
   PulsePlan, Engine.pulse  include/rtlws_pulse.h (single-pulse search: boxcar peaks of a table of widths and the moments per segment, one launch)
   FoldPlan, Engine.fold  include/rtlws_fold.h (epoch folding: the profiles of every trial at a table of periods, per sub-integration, one launch)
+  PeriodPlan, Engine.period  include/rtlws_period.h (periodicity search: whitened power spectra, harmonic sums and their peaks per segment, every trial in one launch)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -54,6 +55,7 @@ PFBSK_LIB = os.path.join(LIB_DIR, "librtlws_pfbsk.so")   # include/rtlws_pfbsk.h
 DEDISP_LIB = os.path.join(LIB_DIR, "librtlws_dedisp.so") # include/rtlws_dedisp.h
 PULSE_LIB = os.path.join(LIB_DIR, "librtlws_pulse.so")   # include/rtlws_pulse.h
 FOLD_LIB = os.path.join(LIB_DIR, "librtlws_fold.so")     # include/rtlws_fold.h
+PERIOD_LIB = os.path.join(LIB_DIR, "librtlws_period.so") # include/rtlws_period.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -162,6 +164,10 @@ FOLD_SYMBOLS = ["rtlws_fold_supported", "rtlws_fold_geometry", "rtlws_fold_open"
                 "rtlws_fold_step", "rtlws_fold_phase_at", "rtlws_fold_chi2", "rtlws_fold_close", "rtlws_fold_last_error"]
 FOLD_MAX_PERIODS, FOLD_MIN_BINS, FOLD_MAX_BINS, FOLD_MIN_SUB, FOLD_MAX_SUB, FOLD_MAX_TRIALS, FOLD_MAX_NSAMP = 4096, 2, 256, 64, 1 << 24, 65536, 1 << 30
 FOLD_GUARD = 8             # Engine.fold(fill=...): preset elements behind both output arrays
+PERIOD_SYMBOLS = ["rtlws_period_supported", "rtlws_period_geometry", "rtlws_period_open", "rtlws_period_run", "rtlws_period_samples",
+                  "rtlws_period_lnq", "rtlws_period_close", "rtlws_period_last_error"]
+PERIOD_MIN_LOG2N, PERIOD_MAX_LOG2N, PERIOD_MAX_LEVELS, PERIOD_MIN_NORM, PERIOD_MIN_SEG, PERIOD_MAX_TRIALS = 10, 15, 5, 16, 64, 65536
+PERIOD_GUARD = 8           # Engine.period(fill=...): preset elements behind every output array
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -844,6 +850,46 @@ def fold_chi2(prof, hits, sum1, sum2, count):
                                       float(sum2), int(count))
 
 
+_PERIOD_PROTOTYPES = {
+    "rtlws_period_supported": [_i, _i, _i, _i, _i], "rtlws_period_geometry": [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip],
+    "rtlws_period_open": ([_vp, _i, _i, _i, _i, _i], _vp), "rtlws_period_run": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
+    "rtlws_period_samples": ([_i, _i, _i], C.c_double), "rtlws_period_lnq": ([C.c_double, _i], C.c_double),
+    "rtlws_period_close": ([_vp], None), "rtlws_period_last_error": ([], _str)}
+
+
+def period_lib():
+    """librtlws_period.so (include/rtlws_period.h); it needs librtlws_hip.so's engine."""
+    return _satellite(PERIOD_LIB, _PERIOD_PROTOTYPES)
+
+
+def period_last_error():
+    return period_lib().rtlws_period_last_error().decode()
+
+
+def period_supported(log2n, levels, norm, seg, klo):
+    """rtlws_period_supported.  No GPU needed."""
+    return period_lib().rtlws_period_supported(int(log2n), int(levels), int(norm), int(seg), int(klo))
+
+
+def period_geometry(log2n, levels, norm, seg, klo, ntrials=1):
+    """rtlws_period_geometry: (rc, workgroups, threads, LDS bytes, segments).  No GPU needed."""
+    v = [C.c_int(0) for _ in range(4)]
+    rc = period_lib().rtlws_period_geometry(int(log2n), int(levels), int(norm), int(seg), int(klo), int(ntrials), *[C.byref(x) for x in v])
+    return (rc,) + tuple(x.value for x in v)
+
+
+def period_samples(log2n, level, k):
+    """rtlws_period_samples: N 2^level / k, the fundamental's period in samples; 0 where an argument is out of range.  No
+    GPU needed."""
+    return period_lib().rtlws_period_samples(int(log2n), int(level), int(k))
+
+
+def period_lnq(s, h):
+    """rtlws_period_lnq: ln of the false-alarm probability of a sum s of h whitened powers; NaN where it is not defined.  No
+    GPU needed."""
+    return period_lib().rtlws_period_lnq(float(s), int(h))
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -1276,6 +1322,24 @@ class FoldPlan(_Plan):
         [nperiods, nsub, nbins] (uint32) or None."""
         return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_prof),
                           self._ptr(d_hits), stream)
+
+
+class PeriodPlan(_Plan):
+    """rtlws_period_plan* of include/rtlws_period.h: the transform's table on the engine's device, the kernel of the frame
+    length loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "period", staticmethod(period_lib)
+
+    def __init__(self, eng, log2n, levels, norm, seg, klo):
+        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
+        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo)
+        self.nbins = 1 << (self.log2n - 1)
+        self.nseg = self.nbins // self.seg
+
+    def run(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
+        """One launch: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials, levels, nseg] (f32, int32),
+        d_power and d_white [ntrials, M] (f32) or None."""
+        return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
+                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
 
 
 class PfbXcPlan(_PolyphasePlan):
@@ -1766,6 +1830,46 @@ class Engine:
             return prof, hits
         return (prof.reshape(ntrials, plan.nperiods, nsub, plan.nbins),
                 hits.reshape(plan.nperiods, nsub, plan.nbins) if want_hits else None)
+
+    # -- include/rtlws_period.h: host series in, (best, at, power, white) out ----
+    def period(self, series, log2n, levels, norm, seg, klo, nsamp=None, in_stride=None, want_rows=True, fill=None):
+        """rtlws_period_run: series float32 [ntrials, nsamp] (with in_stride: [ntrials, in_stride], the padding as the
+        caller left it) -> (float32 [ntrials, levels, nseg] the peaks, int32 of that shape their bins, float32
+        [ntrials, M] the power spectra and the whitened ones, or None for both without want_rows).  nsamp None: the
+        samples the series hold.  With `fill` (a float32) the four come back as the whole flat buffers, PERIOD_GUARD
+        elements longer than the outputs, every element preset to fill (to fill's bits: the bins), so that a caller sees
+        what the run left untouched; without want_rows the run gets NULL rows and the preset buffers come back as they
+        were."""
+        plan = PeriodPlan(self, log2n, levels, norm, seg, klo)
+        series = np.ascontiguousarray(series, dtype=np.float32)
+        if in_stride is not None:
+            series = series.reshape(-1, int(in_stride))
+        assert series.ndim == 2, "the series are [ntrials, nsamp]"
+        samples = series.shape[1]
+        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
+            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        ntrials, width = series.shape
+        nsamp = samples if nsamp is None else int(nsamp)
+        assert samples >= nsamp, "fewer samples than nsamp"
+        guard = 0 if fill is None else PERIOD_GUARD
+        preset = np.float32(0.0 if fill is None else fill)
+        npeaks, nrows = ntrials * plan.levels * plan.nseg, ntrials * plan.nbins
+        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
+                 np.full(nrows + guard, preset, np.float32), np.full(nrows + guard, preset, np.float32)]
+        bufs = [self.upload(series)] + [self.upload(h) for h in hosts]
+        try:
+            plan.run(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_rows else None, bufs[4] if want_rows else None)
+            self.sync()
+            best, at, power, white = [self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
+        finally:
+            plan.close()
+            for b in bufs:
+                b.free()
+        if fill is not None:
+            return best, at, power, white
+        shape = (ntrials, plan.levels, plan.nseg)
+        return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, plan.nbins) if want_rows else None,
+                white.reshape(ntrials, plan.nbins) if want_rows else None)
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
     def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
