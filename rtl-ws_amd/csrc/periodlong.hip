@@ -1,0 +1,421 @@
+// periodlong.hip -- the kernels of include/rtlws_periodlong.h (librtlws_periodlong.so): the search of
+// rtlws_period.h for frames of 2^16 .. 2^22 samples, a four-step transform of the packed series through device memory.
+// M = N / 2 = M1 M2 complex points z[j] = y[2 j] + i y[2 j + 1], j = j1 M2 + j2, k = k1 + M1 k2.  Six launches a group
+// of trials, a trial at blockIdx.y:
+//
+//   mean      64 stretches of a trial's samples, one f64 sum each, in a fixed order
+//   cols      y = x - mean; the M1-point transforms over j1 of every column j2 in registers (M1 = 256: two radix-16
+//             passes around one LDS exchange), the twist e^(-2 pi i k1 j2 / M) from its own once-rounded table, row k1
+//             of the workspace
+//   rows      the M2-point transform of a row in LDS (row_fft.h), written back in the order of k2
+//   untangle  a tile of bins k and the tile of their mirrors M - k through LDS (the rows hold every M1-th bin), the
+//             real-input untangling and the square: P in natural order
+//   whiten    period.hip's stage 4 over spans of 16384 bins: W over P
+//   peaks     period.hip's stage 5 over spans of 16384 bins, W read through the caches
+#include <hip/hip_runtime.h>
+
+#include "periodlong.h"
+#include "row_fft.h"
+#include "rtlws_internal.h"
+
+namespace rtlws {
+namespace periodlong {
+
+namespace {
+
+// period.hip's rule of the peaks between two partial results (best, at): the strict maximum, ties to the smaller k; a
+// partial that took nothing is (-Inf, -1) and never wins
+__device__ __forceinline__ void meet(float& best, int& at, float ob, int oa)
+{
+    if (ob > best || (ob == best && oa < at)) best = ob, at = oa;
+}
+
+__device__ __forceinline__ void meet_lanes(float& best, int& at)
+{
+#pragma unroll
+    for (int off = 1; off < LANES; off <<= 1) {
+        const float ob = __shfl_xor(best, off);
+        const int oa = __shfl_xor(at, off);
+        meet(best, at, ob, oa);
+    }
+}
+
+// the trial's mean from its 64 partial sums: the same additions in every lane, wavefront and workgroup
+__device__ __forceinline__ double mean_of(const double* sums, int nsamp)
+{
+    static_assert(MEAN_PARTS == LANES, "a lane a partial sum");
+    double s = sums[threadIdx.x & (LANES - 1)];
+#pragma unroll
+    for (int off = 1; off < LANES; off <<= 1) s += __shfl_xor(s, off);
+    return s / (double)nsamp;
+}
+
+// the packed point j of a trial: y[2 j] + i y[2 j + 1], nothing at or behind nsamp read, zeros there
+__device__ __forceinline__ f2 point(const float* x, long j, int nsamp, double mean)
+{
+    const long n0 = 2 * j;
+    float a = 0.0f, b = 0.0f;
+    if (n0 + 2 <= nsamp) {
+        const float2 v = *reinterpret_cast<const float2*>(x + n0);
+        a = (float)((double)v.x - mean), b = (float)((double)v.y - mean);
+    } else if (n0 < nsamp) {
+        a = (float)((double)x[n0] - mean);
+    }
+    return mk(a, b);
+}
+
+}  // namespace
+
+// ---- mean: workgroup (q, trial) sums samples q N / 64 .. (q + 1) N / 64 - 1 below nsamp ----
+__global__ __launch_bounds__(MEAN_THREADS) void mean_kernel(const Params p)
+{
+    __shared__ double wsum[MEAN_THREADS / LANES];
+    const int tid = threadIdx.x, lane = tid & (LANES - 1), wave = tid / LANES;
+    const float* const x = p.in + (long)blockIdx.y * p.in_stride;
+    const int nsamp = p.nsamp, per = 1 << (p.log2n - 6), first = (int)blockIdx.x * per;
+    double sum = 0.0;
+    for (int n0 = first + 4 * tid; n0 < first + per; n0 += 4 * MEAN_THREADS) {
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (n0 + 4 <= nsamp) {
+            v = *reinterpret_cast<const float4*>(x + n0);
+        } else if (n0 < nsamp) {                             // the last, partial quad: nothing at or behind nsamp is read
+            v.x = x[n0];
+            if (n0 + 1 < nsamp) v.y = x[n0 + 1];
+            if (n0 + 2 < nsamp) v.z = x[n0 + 2];
+        }
+        sum += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
+    }
+#pragma unroll
+    for (int off = 1; off < LANES; off <<= 1) sum += __shfl_xor(sum, off);
+    if (lane == 0) wsum[wave] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        double total = 0.0;
+#pragma unroll
+        for (int w = 0; w < MEAN_THREADS / LANES; ++w) total += wsum[w];
+        p.sums[(long)blockIdx.y * MEAN_PARTS + blockIdx.x] = total;
+    }
+}
+
+// ---- cols, M1 = 16: a thread a column ----
+__global__ __launch_bounds__(COLS_THREADS) void cols16_kernel(const Params p)
+{
+    const int log2m2 = p.log2n - 5, m2 = 1 << log2m2;
+    const long m = 16L << log2m2;
+    const int j2 = (int)blockIdx.x * COLS_THREADS + (int)threadIdx.x;
+    const float* const x = p.in + (long)blockIdx.y * p.in_stride;
+    const double mean = mean_of(p.sums + (long)blockIdx.y * MEAN_PARTS, p.nsamp);
+    f2 v[16];
+#pragma unroll
+    for (int n = 0; n < 16; ++n) v[n] = point(x, (long)n * m2 + j2, p.nsamp, mean);
+    fft16_fma(v);
+    float2* const z = p.z + (long)blockIdx.y * m + j2;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int k1 = rev16(s);
+        if (s) {
+            const float2 w = p.twist[(long)k1 * m2 + j2];
+            v[s] = cmul(v[s], mk(w.x, w.y));
+        }
+        z[(long)k1 * m2] = make_float2(v[s].x, v[s].y);
+    }
+}
+
+// ---- cols, M1 = 256: a workgroup 16 columns; j1 = a + 16 n, k1 = q + 16 q2 ----
+__global__ __launch_bounds__(COLS_THREADS) void cols256_kernel(const Params p)
+{
+    extern __shared__ float4 lds[];
+    float2* const tile = reinterpret_cast<float2*>(lds);     // [256][17]
+    constexpr int PITCH = COLS256_TILE + 1;
+    const int log2m2 = p.log2n - 9, m2 = 1 << log2m2;
+    const long m = 256L << log2m2;
+    const int tid = threadIdx.x, c = tid & 15, hi = tid >> 4;
+    const int j2 = (int)blockIdx.x * COLS256_TILE + c;
+    const float* const x = p.in + (long)blockIdx.y * p.in_stride;
+    const double mean = mean_of(p.sums + (long)blockIdx.y * MEAN_PARTS, p.nsamp);
+    f2 v[16];
+    {
+        const int a = hi;
+#pragma unroll
+        for (int n = 0; n < 16; ++n) v[n] = point(x, (long)(a + 16 * n) * m2 + j2, p.nsamp, mean);
+        fft16_fma(v);
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int q = rev16(s);
+            if (s) {
+                const float2 w = p.tw256[a * q];             // a q <= 225
+                v[s] = cmul(v[s], mk(w.x, w.y));
+            }
+            tile[(q * 16 + a) * PITCH + c] = make_float2(v[s].x, v[s].y);
+        }
+    }
+    __syncthreads();
+    {
+        const int q = hi;
+#pragma unroll
+        for (int a = 0; a < 16; ++a) v[a] = tile[(q * 16 + a) * PITCH + c];
+        fft16_fma(v);
+        float2* const z = p.z + (long)blockIdx.y * m + j2;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int k1 = q + 16 * rev16(s);
+            const float2 w = p.twist[(long)k1 * m2 + j2];    // row 0 holds ones
+            v[s] = cmul(v[s], mk(w.x, w.y));
+            z[(long)k1 * m2] = make_float2(v[s].x, v[s].y);
+        }
+    }
+}
+
+// ---- rows: workgroup (k1, trial) transforms row k1 in place; afterwards place k2 of the row holds Z[k1 + M1 k2] ----
+template <int LOG2M2>
+__global__ __launch_bounds__(rows_threads(LOG2M2)) void rows_kernel(const Params p)
+{
+    constexpr int M2 = 1 << LOG2M2, T = rows_threads(LOG2M2);
+    extern __shared__ float4 lds[];
+    float2* const tile = reinterpret_cast<float2*>(lds);
+    const int tid = threadIdx.x;
+    float2* const row = p.z + ((long)blockIdx.y << (p.log2n - 1)) + (long)blockIdx.x * M2;
+#pragma unroll 4
+    for (int i = 2 * tid; i < M2; i += 2 * T) {              // i and i + 1 lie in one group of 16
+        const float4 v = *reinterpret_cast<const float4*>(row + i);
+        float2* const at = tile + rowfft::place(i);
+        at[0] = make_float2(v.x, v.y);
+        at[1] = make_float2(v.z, v.w);
+    }
+    __syncthreads();
+    rowfft::forward<LOG2M2>(tile, tid, p.tw_row);
+#pragma unroll 4
+    for (int k2 = tid; k2 < M2; k2 += T) row[k2] = tile[rowfft::place(rowfft::pos<LOG2M2>(k2))];
+}
+
+// ---- untangle: workgroup (i, trial) takes bins k = K0 .. K0 + L - 1, K0 = i L < M / 2, and their mirrors M - k ----
+// X[k] = E - i W^k O, X[M - k] = conj(E) - i conj(W^k O), E, O = (Z[k] +- conj Z[M - k]) / 2, as period.hip does
+template <int LOG2M1>
+__global__ __launch_bounds__(UNTANGLE_THREADS) void untangle_kernel(const Params p)
+{
+    constexpr int M1 = 1 << LOG2M1, C = untangle_cols(LOG2M1), L = M1 * C, PITCH = C + 1, T = UNTANGLE_THREADS;
+    extern __shared__ float4 lds[];
+    float2* const ta = reinterpret_cast<float2*>(lds);       // [M1][C + 1]: columns a .. a + C - 1
+    float2* const tb = ta + M1 * PITCH;                      // [M1][C + 1]: columns M2 - a - C .. M2 - a
+    const int log2m = p.log2n - 1, m2 = 1 << (log2m - LOG2M1), m = 1 << log2m;
+    const int tid = threadIdx.x;
+    const int a = (int)blockIdx.x * C, b0 = m2 - a - C, k0 = a * M1;
+    const long base = (long)blockIdx.y << log2m;
+    const float2* const z = p.z + base;
+    for (int e = tid; e < M1 * C; e += T) {
+        const int r = e / C, c = e - r * C;
+        ta[r * PITCH + c] = z[(long)r * m2 + a + c];
+    }
+    for (int e = tid; e < M1 * (C + 1); e += T) {
+        const int r = e / (C + 1), c = e - r * (C + 1);
+        if (b0 + c < m2) tb[r * PITCH + c] = z[(long)r * m2 + b0 + c];   // column M2 would be bin M + r: only k = 0 mirrors there
+    }
+    __syncthreads();
+    float* const pw = p.pw + base;
+    float* const power = p.power ? p.power + ((long)(p.trial0 + (int)blockIdx.y) << log2m) : nullptr;
+    for (int i = tid; i < L; i += T) {
+        const int k = k0 + i;
+        const f2 za = ta[(i & (M1 - 1)) * PITCH + (i >> LOG2M1)];
+        float pk;
+        if (k == 0) {
+            const float dc = za.x + za.y;
+            pk = dc * dc;
+        } else {
+            const int km = m - k;
+            const f2 zb = tb[(km & (M1 - 1)) * PITCH + ((km >> LOG2M1) - b0)];
+            const float2 w = p.tw[k];
+            const f2 e = mk(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));
+            const f2 o = mk(0.5f * (za.x - zb.x), 0.5f * (za.y + zb.y));
+            const f2 t = cmul(o, mk(w.x, w.y));
+            const float ax = e.x + t.y, ay = e.y - t.x, bx = e.x - t.y, by = e.y + t.x;
+            pk = fmaf(ax, ax, ay * ay);
+            const float pm = fmaf(bx, bx, by * by);
+            pw[km] = pm;
+            if (power) __builtin_nontemporal_store(pm, power + km);
+        }
+        pw[k] = pk;
+        if (power) __builtin_nontemporal_store(pk, power + k);
+    }
+    if (k0 + L == m / 2 && tid == 0) {                       // the bin that is its own mirror: row 0, column M2 / 2
+        const int k = m / 2;
+        const f2 zh = tb[0];
+        const float2 w = p.tw[k];
+        const f2 e = mk(0.5f * (zh.x + zh.x), 0.5f * (zh.y - zh.y));
+        const f2 o = mk(0.5f * (zh.x - zh.x), 0.5f * (zh.y + zh.y));
+        const f2 t = cmul(o, mk(w.x, w.y));
+        const float ax = e.x + t.y, ay = e.y - t.x;
+        const float pk = fmaf(ax, ax, ay * ay);
+        pw[k] = pk;
+        if (power) __builtin_nontemporal_store(pk, power + k);
+    }
+}
+
+// ---- whiten: workgroup (span, trial); thread i owns bins 16 i .. 16 i + 15 of the span, period.hip's stage 4 ----
+__global__ __launch_bounds__(SPAN_THREADS) void whiten_kernel(const Params p)
+{
+    constexpr int WAVES = SPAN_THREADS / LANES;
+    __shared__ float wave_sums[WAVES];
+    const int tid = threadIdx.x, lane = tid & (LANES - 1), wave = tid / LANES;
+    const int log2m = p.log2n - 1;
+    const long off = (long)blockIdx.x * SPAN + 16 * tid;
+    float* const pw = p.pw + ((long)blockIdx.y << log2m) + off;
+    float v[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 f = reinterpret_cast<const float4*>(pw)[q];
+        v[4 * q] = f.x, v[4 * q + 1] = f.y, v[4 * q + 2] = f.z, v[4 * q + 3] = f.w;
+    }
+    // the halving tree: adjacent pairs first, one rounding per addition
+    float s[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s[i] = v[2 * i] + v[2 * i + 1];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] = s[2 * i] + s[2 * i + 1];
+    s[0] = s[0] + s[1];
+    s[1] = s[2] + s[3];
+    float bsum = s[0] + s[1];
+    const int more = p.log2norm - 4;                         // levels behind a thread's 16 bins
+    // a + b = b + a bit for bit: the exchange gives both lanes of a pair the pair's sum
+#pragma unroll
+    for (int lv = 0; lv < 6; ++lv)
+        if (lv < more) bsum = bsum + __shfl_xor(bsum, 1 << lv);
+    if (more > 6) {                                          // a block of 2 .. 16 wavefronts
+        if (lane == 0) wave_sums[wave] = bsum;
+        __syncthreads();
+        const int g = 1 << (more - 6), first = wave & ~(g - 1);
+        float a[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = i < g ? wave_sums[first + i] : 0.0f;
+#pragma unroll
+        for (int w = 2; w <= 16; w <<= 1) {
+            if (w <= g) {
+#pragma unroll
+                for (int i = 0; i < 16 / w; ++i) a[i] = a[2 * i] + a[2 * i + 1];
+            }
+        }
+        bsum = a[0];
+    }
+    const float bmean = bsum * p.norm_scale;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) v[i] = v[i] / bmean;        // IEEE division, correctly rounded
+#pragma unroll
+    for (int q = 0; q < 4; ++q) reinterpret_cast<float4*>(pw)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    if (p.white) {
+        float* const dst = p.white + ((long)(p.trial0 + (int)blockIdx.y) << log2m) + off;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) store_nt<float, 4>(dst + 4 * q, {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]});
+    }
+}
+
+// ---- peaks: workgroup (span, trial); a wavefront walks a chunk of k, a lane every 64th, period.hip's stage 5 ----
+__global__ __launch_bounds__(SPAN_THREADS) void peaks_kernel(const Params p)
+{
+    constexpr int WAVES = SPAN_THREADS / LANES;
+    __shared__ float part_best[MAX_LEVELS * 16];
+    __shared__ int part_at[MAX_LEVELS * 16];
+    const int tid = threadIdx.x, lane = tid & (LANES - 1), wave = tid / LANES;
+    const int log2m = p.log2n - 1;
+    const float* const pw = p.pw + ((long)blockIdx.y << log2m);
+    const long trial = p.trial0 + (int)blockIdx.y;
+    const int levels = p.levels, seg = p.seg, klo = p.klo;
+    const int chunk = chunk_of(seg), nchunks = SPAN / chunk, nseg = (1 << log2m) / seg;
+    const int kb = (int)blockIdx.x * SPAN, segb = kb / seg;  // the span's first bin and segment
+    const float ninf = -__builtin_huge_valf();
+    for (int c = wave; c < nchunks; c += WAVES) {
+        float best[MAX_LEVELS];
+        int at[MAX_LEVELS];
+#pragma unroll
+        for (int l = 0; l < MAX_LEVELS; ++l) best[l] = ninf, at[l] = -1;
+        for (int k = kb + c * chunk + lane; k < kb + (c + 1) * chunk; k += LANES) {
+            const bool in = k >= klo;
+            float acc = pw[k];
+            if (in && acc > best[0]) best[0] = acc, at[0] = k;
+#pragma unroll
+            for (int l = 1; l < MAX_LEVELS; ++l) {
+                if (l < levels) {
+#pragma unroll
+                    for (int h = 1; h < (1 << l); h += 2) acc = acc + pw[((long)k * h + (1 << (l - 1))) >> l];
+                    if (in && acc > best[l]) best[l] = acc, at[l] = k;
+                }
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < MAX_LEVELS; ++l) {
+            if (l < levels) {
+                meet_lanes(best[l], at[l]);
+                if (lane == 0) {
+                    if (chunk == seg) {
+                        const long o = (trial * levels + l) * nseg + segb + c;
+                        p.best[o] = best[l];
+                        p.at[o] = at[l];
+                    } else {                                 // chunks of 1024: c < 16
+                        part_best[l * 16 + c] = best[l];
+                        part_at[l * 16 + c] = at[l];
+                    }
+                }
+            }
+        }
+    }
+    if (chunk != seg) {                                      // segments of 2 .. 16 chunks
+        __syncthreads();
+        const int per = seg / chunk, here = SPAN / seg;
+        for (int o = tid; o < levels * here; o += SPAN_THREADS) {
+            const int l = o / here, s = o - l * here;
+            float best = ninf;
+            int at = -1;
+            for (int c = s * per; c < (s + 1) * per; ++c) meet(best, at, part_best[l * 16 + c], part_at[l * 16 + c]);
+            p.best[(trial * levels + l) * nseg + segb + s] = best;
+            p.at[(trial * levels + l) * nseg + segb + s] = at;
+        }
+    }
+}
+
+using Log2M2s = Vals<11, 12, 13, 14>;
+using Log2M1s = Vals<4, 8>;
+
+hipError_t launch_group(const Params& p, int group, hipStream_t st)
+{
+    const int n = p.log2n, l1 = log2m1_of(n), l2 = log2m2_of(n);
+    const auto grid = [&](int stage) { return dim3((unsigned)stage_blocks(stage, n), (unsigned)group); };
+    const auto block = [&](int stage) { return dim3((unsigned)stage_threads(stage, n)); };
+    hipError_t e = launch(&mean_kernel, grid(STAGE_MEAN), block(STAGE_MEAN), 0, st, p);
+    if (e != hipSuccess) return e;
+    e = launch(l1 == 4 ? &cols16_kernel : &cols256_kernel, grid(STAGE_COLS), block(STAGE_COLS), (size_t)cols_lds(l1), st, p);
+    if (e != hipSuccess) return e;
+    e = pick(Log2M2s{}, l2, [&](auto m) {
+        return launch(&rows_kernel<decltype(m)::value>, grid(STAGE_ROWS), block(STAGE_ROWS), (size_t)rows_lds(decltype(m)::value), st, p);
+    });
+    if (e != hipSuccess) return e;
+    e = pick(Log2M1s{}, l1, [&](auto m) {
+        return launch(&untangle_kernel<decltype(m)::value>, grid(STAGE_UNTANGLE), block(STAGE_UNTANGLE), (size_t)untangle_lds(decltype(m)::value), st, p);
+    });
+    if (e != hipSuccess) return e;
+    e = launch(&whiten_kernel, grid(STAGE_WHITEN), block(STAGE_WHITEN), 0, st, p);
+    if (e != hipSuccess) return e;
+    return launch(&peaks_kernel, grid(STAGE_PEAKS), block(STAGE_PEAKS), 0, st, p);
+}
+
+hipError_t prepare(int log2n, int device)
+{
+    const int l1 = log2m1_of(log2n), l2 = log2m2_of(log2n);
+    hipFuncAttributes a;
+    // asking for a kernel's attributes loads its code object: nothing is left to load under a capture
+    for (const void* k : {reinterpret_cast<const void*>(&mean_kernel), reinterpret_cast<const void*>(&cols16_kernel),
+                          reinterpret_cast<const void*>(&cols256_kernel), reinterpret_cast<const void*>(&whiten_kernel),
+                          reinterpret_cast<const void*>(&peaks_kernel)}) {
+        const hipError_t e = hipFuncGetAttributes(&a, k);
+        if (e != hipSuccess) return e;
+    }
+    hipError_t e = pick(Log2M2s{}, l2, [&](auto m) {
+        const hipError_t g = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&rows_kernel<decltype(m)::value>));
+        return g != hipSuccess ? g : lds_opt_in(&rows_kernel<decltype(m)::value>, device, (size_t)rows_lds(decltype(m)::value));
+    });
+    if (e != hipSuccess) return e;
+    return pick(Log2M1s{}, l1, [&](auto m) {
+        const hipError_t g = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&untangle_kernel<decltype(m)::value>));
+        return g != hipSuccess ? g : lds_opt_in(&untangle_kernel<decltype(m)::value>, device, (size_t)untangle_lds(decltype(m)::value));
+    });
+}
+
+}  // namespace periodlong
+}  // namespace rtlws

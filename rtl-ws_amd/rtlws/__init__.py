@@ -22,6 +22,7 @@ fail loudly.
   PulsePlan, Engine.pulse  include/rtlws_pulse.h (single-pulse search: boxcar peaks of a table of widths and the moments per segment, one launch)
   FoldPlan, Engine.fold  include/rtlws_fold.h (epoch folding: the profiles of every trial at a table of periods, per sub-integration, one launch)
   PeriodPlan, Engine.period  include/rtlws_period.h (periodicity search: whitened power spectra, harmonic sums and their peaks per segment, every trial in one launch)
+  PeriodLongPlan, Engine.periodlong  include/rtlws_periodlong.h (that search for frames of 2^16 .. 2^22 samples: a four-step transform through device memory)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -56,6 +57,7 @@ DEDISP_LIB = os.path.join(LIB_DIR, "librtlws_dedisp.so") # include/rtlws_dedisp.
 PULSE_LIB = os.path.join(LIB_DIR, "librtlws_pulse.so")   # include/rtlws_pulse.h
 FOLD_LIB = os.path.join(LIB_DIR, "librtlws_fold.so")     # include/rtlws_fold.h
 PERIOD_LIB = os.path.join(LIB_DIR, "librtlws_period.so") # include/rtlws_period.h
+PERIODLONG_LIB = os.path.join(LIB_DIR, "librtlws_periodlong.so")  # include/rtlws_periodlong.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -168,6 +170,11 @@ PERIOD_SYMBOLS = ["rtlws_period_supported", "rtlws_period_geometry", "rtlws_peri
                   "rtlws_period_lnq", "rtlws_period_close", "rtlws_period_last_error"]
 PERIOD_MIN_LOG2N, PERIOD_MAX_LOG2N, PERIOD_MAX_LEVELS, PERIOD_MIN_NORM, PERIOD_MIN_SEG, PERIOD_MAX_TRIALS = 10, 15, 5, 16, 64, 65536
 PERIOD_GUARD = 8           # Engine.period(fill=...): preset elements behind every output array
+PERIODLONG_SYMBOLS = ["rtlws_periodlong_supported", "rtlws_periodlong_geometry", "rtlws_periodlong_open", "rtlws_periodlong_workspace_bytes",
+                      "rtlws_periodlong_run", "rtlws_periodlong_samples", "rtlws_periodlong_close", "rtlws_periodlong_last_error"]
+PERIODLONG_MIN_LOG2N, PERIODLONG_MAX_LOG2N, PERIODLONG_MAX_LEVELS, PERIODLONG_MAX_TRIALS, PERIODLONG_STAGES = 16, 22, 5, 65536, 6
+PERIODLONG_MIN_NORM, PERIODLONG_MAX_NORM, PERIODLONG_MIN_SEG, PERIODLONG_MAX_SEG = 16, 16384, 64, 16384
+PERIODLONG_WORKSPACE_CAP = 1 << 30
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -890,6 +897,43 @@ def period_lnq(s, h):
     return period_lib().rtlws_period_lnq(float(s), int(h))
 
 
+_PERIODLONG_PROTOTYPES = {
+    "rtlws_periodlong_supported": [_i, _i, _i, _i, _i], "rtlws_periodlong_geometry": [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip],
+    "rtlws_periodlong_open": ([_vp, _i, _i, _i, _i, _i, _i], _vp), "rtlws_periodlong_workspace_bytes": ([_vp], C.c_size_t),
+    "rtlws_periodlong_run": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp], "rtlws_periodlong_samples": ([_i, _i, _i], C.c_double),
+    "rtlws_periodlong_close": ([_vp], None), "rtlws_periodlong_last_error": ([], _str)}
+
+
+def periodlong_lib():
+    """librtlws_periodlong.so (include/rtlws_periodlong.h); it needs librtlws_hip.so's engine."""
+    return _satellite(PERIODLONG_LIB, _PERIODLONG_PROTOTYPES)
+
+
+def periodlong_last_error():
+    return periodlong_lib().rtlws_periodlong_last_error().decode()
+
+
+def periodlong_supported(log2n, levels, norm, seg, klo):
+    """rtlws_periodlong_supported.  No GPU needed."""
+    return periodlong_lib().rtlws_periodlong_supported(int(log2n), int(levels), int(norm), int(seg), int(klo))
+
+
+def periodlong_geometry(log2n, levels, norm, seg, klo, ntrials=1):
+    """rtlws_periodlong_geometry: (rc, workgroups, threads, LDS bytes -- a tuple of PERIODLONG_STAGES each: mean, columns,
+    rows, untangling, whitening, peaks -- and segments).  No GPU needed."""
+    v = [(C.c_int * PERIODLONG_STAGES)() for _ in range(3)]
+    nseg = C.c_int()
+    rc = periodlong_lib().rtlws_periodlong_geometry(int(log2n), int(levels), int(norm), int(seg), int(klo), int(ntrials), v[0], v[1], v[2],
+                                                    C.byref(nseg))
+    return (rc,) + tuple(tuple(x) for x in v) + (nseg.value,)
+
+
+def periodlong_samples(log2n, level, k):
+    """rtlws_periodlong_samples: N 2^level / k, the fundamental's period in samples; 0 where an argument is out of range.
+    No GPU needed."""
+    return periodlong_lib().rtlws_periodlong_samples(int(log2n), int(level), int(k))
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -1338,6 +1382,28 @@ class PeriodPlan(_Plan):
     def run(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
         """One launch: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials, levels, nseg] (f32, int32),
         d_power and d_white [ntrials, M] (f32) or None."""
+        return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
+                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+
+
+class PeriodLongPlan(_Plan):
+    """rtlws_periodlong_plan* of include/rtlws_periodlong.h: the tables and a workspace for min(max_trials, what fits under
+    the cap) trials in flight on the engine's device, the kernels of the frame length loaded.  eng may be None (as a C
+    caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "periodlong", staticmethod(periodlong_lib)
+
+    def __init__(self, eng, log2n, levels, norm, seg, klo, max_trials=1):
+        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
+        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo, int(max_trials))
+        self.nbins = 1 << (self.log2n - 1)
+        self.nseg = self.nbins // self.seg
+
+    def workspace_bytes(self):
+        return self._fn("workspace_bytes")(self.h)
+
+    def run(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
+        """Six launches a group of trials: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials, levels,
+        nseg] (f32, int32), d_power and d_white [ntrials, M] (f32) or None."""
         return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
                           self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
 
@@ -1870,6 +1936,46 @@ class Engine:
         shape = (ntrials, plan.levels, plan.nseg)
         return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, plan.nbins) if want_rows else None,
                 white.reshape(ntrials, plan.nbins) if want_rows else None)
+
+    # -- include/rtlws_periodlong.h: host series in, (best, at, power, white) out ----
+    def periodlong(self, series, log2n, levels, norm, seg, klo, nsamp=None, in_stride=None, want_rows=True, fill=None, max_trials=None,
+                   want_power=None, want_white=None):
+        """rtlws_periodlong_run with Engine.period's arguments and results.  max_trials: what the plan is opened for (None:
+        the trials given); want_power / want_white: one optional row alone (None: want_rows)."""
+        series = np.ascontiguousarray(series, dtype=np.float32)
+        if in_stride is not None:
+            series = series.reshape(-1, int(in_stride))
+        assert series.ndim == 2, "the series are [ntrials, nsamp]"
+        samples = series.shape[1]
+        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
+            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        ntrials, width = series.shape
+        plan = PeriodLongPlan(self, log2n, levels, norm, seg, klo, ntrials if max_trials is None else max_trials)
+        nsamp = samples if nsamp is None else int(nsamp)
+        assert samples >= nsamp, "fewer samples than nsamp"
+        want_power = want_rows if want_power is None else want_power
+        want_white = want_rows if want_white is None else want_white
+        guard = 0 if fill is None else PERIOD_GUARD
+        preset = np.float32(0.0 if fill is None else fill)
+        npeaks, nrows = ntrials * plan.levels * plan.nseg, ntrials * plan.nbins
+        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
+                 np.full((nrows if want_power or fill is not None else 0) + guard, preset, np.float32),
+                 np.full((nrows if want_white or fill is not None else 0) + guard, preset, np.float32)]
+        bufs = [self.upload(series)] + [self.upload(h) if h.size else None for h in hosts]
+        try:
+            plan.run(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_power else None, bufs[4] if want_white else None)
+            self.sync()
+            best, at, power, white = [h if b is None else self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
+        finally:
+            plan.close()
+            for b in bufs:
+                if b is not None:
+                    b.free()
+        if fill is not None:
+            return best, at, power, white
+        shape = (ntrials, plan.levels, plan.nseg)
+        return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, plan.nbins) if want_power else None,
+                white.reshape(ntrials, plan.nbins) if want_white else None)
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
     def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
