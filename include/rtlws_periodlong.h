@@ -51,7 +51,8 @@
  * The false-alarm probability of a sum is rtlws_period_lnq (rtlws_period.h): it does not depend on the frame length and
  * is not repeated here.
  *
- * Not built: frames of other than a power of two samples, median whitening, interbinning, acceleration search.
+ * Not built: frames of other than a power of two samples, median whitening, interbinning.  (Acceleration search is
+ * rtlws_accel.h's, on top of this library's stages.)
  */
 #ifndef RTLWS_PERIODLONG_H
 #define RTLWS_PERIODLONG_H

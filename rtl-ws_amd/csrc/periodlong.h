@@ -85,7 +85,11 @@ struct Params {
     float norm_scale;      // 2^-log2norm
 };
 
-// the six launches of one group of `group` trials, in the stages' order
+// the six launches of one group of `group` trials, in the stages' order: the head reads the caller's series (mean,
+// columns) and the tail the workspace alone (rows .. peaks), so that a library with a head of its own (accel.hip) runs
+// this tail behind it
+hipError_t launch_head(const Params& p, int group, hipStream_t st);
+hipError_t launch_tail(const Params& p, int group, hipStream_t st);
 hipError_t launch_group(const Params& p, int group, hipStream_t st);
 // loads every kernel of the frame length on `device` (the current one) and raises the LDS limits above 64 KiB
 hipError_t prepare(int log2n, int device);

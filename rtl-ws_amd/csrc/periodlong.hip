@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "periodlong.h"
+#include "periodlong_front.h"
 #include "row_fft.h"
 #include "rtlws_internal.h"
 
@@ -40,131 +41,16 @@ __device__ __forceinline__ void meet_lanes(float& best, int& at)
     }
 }
 
-// the trial's mean from its 64 partial sums: the same additions in every lane, wavefront and workgroup
-__device__ __forceinline__ double mean_of(const double* sums, int nsamp)
-{
-    static_assert(MEAN_PARTS == LANES, "a lane a partial sum");
-    double s = sums[threadIdx.x & (LANES - 1)];
-#pragma unroll
-    for (int off = 1; off < LANES; off <<= 1) s += __shfl_xor(s, off);
-    return s / (double)nsamp;
-}
-
-// the packed point j of a trial: y[2 j] + i y[2 j + 1], nothing at or behind nsamp read, zeros there
-__device__ __forceinline__ f2 point(const float* x, long j, int nsamp, double mean)
-{
-    const long n0 = 2 * j;
-    float a = 0.0f, b = 0.0f;
-    if (n0 + 2 <= nsamp) {
-        const float2 v = *reinterpret_cast<const float2*>(x + n0);
-        a = (float)((double)v.x - mean), b = (float)((double)v.y - mean);
-    } else if (n0 < nsamp) {
-        a = (float)((double)x[n0] - mean);
-    }
-    return mk(a, b);
-}
-
 }  // namespace
 
-// ---- mean: workgroup (q, trial) sums samples q N / 64 .. (q + 1) N / 64 - 1 below nsamp ----
-__global__ __launch_bounds__(MEAN_THREADS) void mean_kernel(const Params p)
-{
-    __shared__ double wsum[MEAN_THREADS / LANES];
-    const int tid = threadIdx.x, lane = tid & (LANES - 1), wave = tid / LANES;
-    const float* const x = p.in + (long)blockIdx.y * p.in_stride;
-    const int nsamp = p.nsamp, per = 1 << (p.log2n - 6), first = (int)blockIdx.x * per;
-    double sum = 0.0;
-    for (int n0 = first + 4 * tid; n0 < first + per; n0 += 4 * MEAN_THREADS) {
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (n0 + 4 <= nsamp) {
-            v = *reinterpret_cast<const float4*>(x + n0);
-        } else if (n0 < nsamp) {                             // the last, partial quad: nothing at or behind nsamp is read
-            v.x = x[n0];
-            if (n0 + 1 < nsamp) v.y = x[n0 + 1];
-            if (n0 + 2 < nsamp) v.z = x[n0 + 2];
-        }
-        sum += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
-    }
-#pragma unroll
-    for (int off = 1; off < LANES; off <<= 1) sum += __shfl_xor(sum, off);
-    if (lane == 0) wsum[wave] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        double total = 0.0;
-#pragma unroll
-        for (int w = 0; w < MEAN_THREADS / LANES; ++w) total += wsum[w];
-        p.sums[(long)blockIdx.y * MEAN_PARTS + blockIdx.x] = total;
-    }
-}
+// ---- mean and cols: periodlong_front.h's text over the series as it lies, the trial of a workgroup at blockIdx.y ----
+__device__ __forceinline__ front::Plain series_of(const Params& p) { return front::Plain{p.in + (long)blockIdx.y * p.in_stride}; }
 
-// ---- cols, M1 = 16: a thread a column ----
-__global__ __launch_bounds__(COLS_THREADS) void cols16_kernel(const Params p)
-{
-    const int log2m2 = p.log2n - 5, m2 = 1 << log2m2;
-    const long m = 16L << log2m2;
-    const int j2 = (int)blockIdx.x * COLS_THREADS + (int)threadIdx.x;
-    const float* const x = p.in + (long)blockIdx.y * p.in_stride;
-    const double mean = mean_of(p.sums + (long)blockIdx.y * MEAN_PARTS, p.nsamp);
-    f2 v[16];
-#pragma unroll
-    for (int n = 0; n < 16; ++n) v[n] = point(x, (long)n * m2 + j2, p.nsamp, mean);
-    fft16_fma(v);
-    float2* const z = p.z + (long)blockIdx.y * m + j2;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        const int k1 = rev16(s);
-        if (s) {
-            const float2 w = p.twist[(long)k1 * m2 + j2];
-            v[s] = cmul(v[s], mk(w.x, w.y));
-        }
-        z[(long)k1 * m2] = make_float2(v[s].x, v[s].y);
-    }
-}
+__global__ __launch_bounds__(MEAN_THREADS) void mean_kernel(const Params p) { front::mean(p, series_of(p)); }
 
-// ---- cols, M1 = 256: a workgroup 16 columns; j1 = a + 16 n, k1 = q + 16 q2 ----
-__global__ __launch_bounds__(COLS_THREADS) void cols256_kernel(const Params p)
-{
-    extern __shared__ float4 lds[];
-    float2* const tile = reinterpret_cast<float2*>(lds);     // [256][17]
-    constexpr int PITCH = COLS256_TILE + 1;
-    const int log2m2 = p.log2n - 9, m2 = 1 << log2m2;
-    const long m = 256L << log2m2;
-    const int tid = threadIdx.x, c = tid & 15, hi = tid >> 4;
-    const int j2 = (int)blockIdx.x * COLS256_TILE + c;
-    const float* const x = p.in + (long)blockIdx.y * p.in_stride;
-    const double mean = mean_of(p.sums + (long)blockIdx.y * MEAN_PARTS, p.nsamp);
-    f2 v[16];
-    {
-        const int a = hi;
-#pragma unroll
-        for (int n = 0; n < 16; ++n) v[n] = point(x, (long)(a + 16 * n) * m2 + j2, p.nsamp, mean);
-        fft16_fma(v);
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int q = rev16(s);
-            if (s) {
-                const float2 w = p.tw256[a * q];             // a q <= 225
-                v[s] = cmul(v[s], mk(w.x, w.y));
-            }
-            tile[(q * 16 + a) * PITCH + c] = make_float2(v[s].x, v[s].y);
-        }
-    }
-    __syncthreads();
-    {
-        const int q = hi;
-#pragma unroll
-        for (int a = 0; a < 16; ++a) v[a] = tile[(q * 16 + a) * PITCH + c];
-        fft16_fma(v);
-        float2* const z = p.z + (long)blockIdx.y * m + j2;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int k1 = q + 16 * rev16(s);
-            const float2 w = p.twist[(long)k1 * m2 + j2];    // row 0 holds ones
-            v[s] = cmul(v[s], mk(w.x, w.y));
-            z[(long)k1 * m2] = make_float2(v[s].x, v[s].y);
-        }
-    }
-}
+__global__ __launch_bounds__(COLS_THREADS) void cols16_kernel(const Params p) { front::cols16(p, series_of(p)); }
+
+__global__ __launch_bounds__(COLS_THREADS) void cols256_kernel(const Params p) { front::cols256(p, series_of(p)); }
 
 // ---- rows: workgroup (k1, trial) transforms row k1 in place; afterwards place k2 of the row holds Z[k1 + M1 k2] ----
 template <int LOG2M2>
@@ -373,16 +259,21 @@ __global__ __launch_bounds__(SPAN_THREADS) void peaks_kernel(const Params p)
 using Log2M2s = Vals<11, 12, 13, 14>;
 using Log2M1s = Vals<4, 8>;
 
-hipError_t launch_group(const Params& p, int group, hipStream_t st)
+hipError_t launch_head(const Params& p, int group, hipStream_t st)
+{
+    const int n = p.log2n, l1 = log2m1_of(n);
+    const hipError_t e = launch(&mean_kernel, dim3((unsigned)stage_blocks(STAGE_MEAN, n), (unsigned)group), dim3((unsigned)stage_threads(STAGE_MEAN, n)), 0, st, p);
+    if (e != hipSuccess) return e;
+    return launch(l1 == 4 ? &cols16_kernel : &cols256_kernel, dim3((unsigned)stage_blocks(STAGE_COLS, n), (unsigned)group),
+                  dim3((unsigned)stage_threads(STAGE_COLS, n)), (size_t)cols_lds(l1), st, p);
+}
+
+hipError_t launch_tail(const Params& p, int group, hipStream_t st)
 {
     const int n = p.log2n, l1 = log2m1_of(n), l2 = log2m2_of(n);
     const auto grid = [&](int stage) { return dim3((unsigned)stage_blocks(stage, n), (unsigned)group); };
     const auto block = [&](int stage) { return dim3((unsigned)stage_threads(stage, n)); };
-    hipError_t e = launch(&mean_kernel, grid(STAGE_MEAN), block(STAGE_MEAN), 0, st, p);
-    if (e != hipSuccess) return e;
-    e = launch(l1 == 4 ? &cols16_kernel : &cols256_kernel, grid(STAGE_COLS), block(STAGE_COLS), (size_t)cols_lds(l1), st, p);
-    if (e != hipSuccess) return e;
-    e = pick(Log2M2s{}, l2, [&](auto m) {
+    hipError_t e = pick(Log2M2s{}, l2, [&](auto m) {
         return launch(&rows_kernel<decltype(m)::value>, grid(STAGE_ROWS), block(STAGE_ROWS), (size_t)rows_lds(decltype(m)::value), st, p);
     });
     if (e != hipSuccess) return e;
@@ -393,6 +284,12 @@ hipError_t launch_group(const Params& p, int group, hipStream_t st)
     e = launch(&whiten_kernel, grid(STAGE_WHITEN), block(STAGE_WHITEN), 0, st, p);
     if (e != hipSuccess) return e;
     return launch(&peaks_kernel, grid(STAGE_PEAKS), block(STAGE_PEAKS), 0, st, p);
+}
+
+hipError_t launch_group(const Params& p, int group, hipStream_t st)
+{
+    const hipError_t e = launch_head(p, group, st);
+    return e != hipSuccess ? e : launch_tail(p, group, st);
 }
 
 hipError_t prepare(int log2n, int device)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "periodlong.h"
+#include "periodlong_plan.h"
 #include "rtlws_periodlong.h"
 #include "shim_common.h"
 
@@ -23,61 +24,7 @@ struct rtlws_periodlong_plan {
     char* d_ws;                // z [group][M] float2, pw [group][M] float, sums [group][64] double
 };
 
-namespace {
-
 using namespace rtlws::periodlong;
-
-static_assert(MIN_LOG2N == RTLWS_PERIODLONG_MIN_LOG2N && MAX_LOG2N == RTLWS_PERIODLONG_MAX_LOG2N && MAX_LEVELS == RTLWS_PERIODLONG_MAX_LEVELS &&
-                  MIN_NORM == RTLWS_PERIODLONG_MIN_NORM && MAX_NORM == RTLWS_PERIODLONG_MAX_NORM && MIN_SEG == RTLWS_PERIODLONG_MIN_SEG &&
-                  MAX_SEG == RTLWS_PERIODLONG_MAX_SEG && MAX_TRIALS == RTLWS_PERIODLONG_MAX_TRIALS && STAGES == RTLWS_PERIODLONG_STAGES,
-              "rtlws_periodlong.h and periodlong.h disagree");
-static_assert(trial_bytes(MAX_LOG2N) <= RTLWS_PERIODLONG_WORKSPACE_CAP, "the cap holds a trial of every frame length");
-
-const char* const NULL_PLAN = "null plan (no usable HIP device: there is no CPU path)";
-
-bool power_of_two(int v) { return v > 0 && !(v & (v - 1)); }
-
-int log2_of(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
-// ---- the rules, each worded once ----
-const char* why_not_plan(int log2n, int levels, int norm, int seg, int klo)
-{
-    if (log2n < MIN_LOG2N || log2n > MAX_LOG2N) return "log2n must be 16 .. 22";
-    const int m = 1 << (log2n - 1);
-    if (levels < 1 || levels > MAX_LEVELS) return "levels must be 1 .. 5";
-    if (norm < MIN_NORM || norm > MAX_NORM || !power_of_two(norm)) return "norm must be a power of two 16 .. 16384";
-    if (seg < MIN_SEG || seg > MAX_SEG || !power_of_two(seg)) return "seg must be a power of two 64 .. 16384";
-    if (klo < 1 || klo > m - 1) return "klo must be 1 .. N / 2 - 1";
-    return nullptr;
-}
-
-const char* why_not_ntrials(int ntrials) { return ntrials < 1 || ntrials > MAX_TRIALS ? "ntrials must be 1 .. 65536" : nullptr; }
-
-// e^(-2 pi i k / N), k < N, every entry the exact root rounded once to f32: one octant evaluated in long double, the
-// rest by the circle's symmetries, so that the axis values are exact and mirrored entries agree bit for bit
-struct Roots {
-    int n;
-    std::vector<float> c, s;   // cos, sin (2 pi r / N), r <= N / 8
-    explicit Roots(int n_) : n(n_), c((size_t)n_ / 8 + 1), s((size_t)n_ / 8 + 1)
-    {
-        const long double step = 6.283185307179586476925286766559L / (long double)n;
-        for (int r = 0; r <= n / 8; ++r) c[r] = (float)cosl(step * r), s[r] = (float)sinl(step * r);
-    }
-    float2 operator()(long k) const
-    {
-        const int quarter = n / 4, q = (int)(k / quarter), r = (int)(k % quarter);
-        const float co = r <= n / 8 ? c[r] : s[quarter - r], si = r <= n / 8 ? s[r] : c[quarter - r];
-        // e^(-i theta) = (co, -si), times (-i)^q
-        return q == 0 ? make_float2(co, -si) : q == 1 ? make_float2(-si, -co) : q == 2 ? make_float2(-co, si) : make_float2(si, co);
-    }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -115,25 +62,9 @@ rtlws_periodlong_plan* rtlws_periodlong_open(rtlws_engine* e, int log2n, int lev
     if (!why && max_trials < 1) why = "max_trials must be >= 1";
     const int device = open_device(fn, why, e);
     if (device < 0) return nullptr;
-    const int n = 1 << log2n, m = n / 2, l1 = log2m1_of(log2n), m1 = 1 << l1, m2 = m >> l1;
-    std::vector<float2> t((size_t)2 * m + m2 + 256);
-    {
-        const Roots root(n);
-        float2* const tw = t.data();
-        float2* const twist = tw + m;
-        float2* const tw_row = twist + m;
-        float2* const tw256 = tw_row + m2;
-        for (int j = 0; j < m; ++j) tw[j] = root(j);
-        for (int k1 = 0; k1 < m1; ++k1)
-            for (int j2 = 0; j2 < m2; ++j2) twist[(size_t)k1 * m2 + j2] = root(2L * k1 * j2);      // k1 j2 < M
-        for (int j = 0; j < m2; ++j) tw_row[j] = root((long)j * m1);
-        for (int j = 0; j < 256; ++j) tw256[j] = root((long)j * (n / 256));
-    }
-    // the trials in flight: what the caller expects, what the cap holds, what a launch's second grid axis takes
-    size_t group = RTLWS_PERIODLONG_WORKSPACE_CAP / trial_bytes(log2n);
-    if (group > 65535) group = 65535;
-    if (group > (size_t)max_trials) group = (size_t)max_trials;
-    const size_t ws_bytes = group * trial_bytes(log2n);
+    const std::vector<float2> t = host_tables(log2n);
+    const int group = in_flight(log2n, max_trials);
+    const size_t ws_bytes = (size_t)group * trial_bytes(log2n);
     float2* d_tables = nullptr;
     char* d_ws = nullptr;
     hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_tables), t.size() * sizeof(float2));
@@ -146,7 +77,7 @@ rtlws_periodlong_plan* rtlws_periodlong_open(rtlws_engine* e, int log2n, int lev
         fail_hip(fn, "the tables, the workspace or the kernels", err);
         return nullptr;
     }
-    return new rtlws_periodlong_plan{e, device, log2n, levels, log2_of(norm), seg, klo, (int)group, ws_bytes, d_tables, d_ws};
+    return new rtlws_periodlong_plan{e, device, log2n, levels, log2_of(norm), seg, klo, group, ws_bytes, d_tables, d_ws};
 }
 
 size_t rtlws_periodlong_workspace_bytes(const rtlws_periodlong_plan* p) { return p ? p->ws_bytes : 0; }
@@ -183,27 +114,13 @@ int rtlws_periodlong_run(rtlws_periodlong_plan* p, const float* d_in, long in_st
 
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
-    const size_t m = (size_t)1 << (p->log2n - 1), m2 = m >> log2m1_of(p->log2n);
-    Params kp;
+    Params kp = plan_params(p->log2n, p->levels, p->log2norm, p->seg, p->klo, p->group, p->d_tables, p->d_ws);
     kp.best = d_best;
     kp.at = d_at;
     kp.power = d_power;
     kp.white = d_white;
-    kp.z = reinterpret_cast<float2*>(p->d_ws);
-    kp.pw = reinterpret_cast<float*>(p->d_ws + (size_t)p->group * m * sizeof(float2));
-    kp.sums = reinterpret_cast<double*>(p->d_ws + (size_t)p->group * m * (sizeof(float2) + sizeof(float)));
-    kp.tw = p->d_tables;
-    kp.twist = p->d_tables + m;
-    kp.tw_row = p->d_tables + 2 * m;
-    kp.tw256 = p->d_tables + 2 * m + m2;
     kp.in_stride = in_stride;
-    kp.log2n = p->log2n;
     kp.nsamp = nsamp;
-    kp.levels = p->levels;
-    kp.log2norm = p->log2norm;
-    kp.seg = p->seg;
-    kp.klo = p->klo;
-    kp.norm_scale = std::ldexp(1.0f, -p->log2norm);
     const hipStream_t st = stream_of(p->engine, stream);
     // groups of trials that fit the workspace, one after the other on the stream
     for (int t0 = 0; t0 < ntrials; t0 += p->group) {

@@ -23,6 +23,7 @@ fail loudly.
   FoldPlan, Engine.fold  include/rtlws_fold.h (epoch folding: the profiles of every trial at a table of periods, per sub-integration, one launch)
   PeriodPlan, Engine.period  include/rtlws_period.h (periodicity search: whitened power spectra, harmonic sums and their peaks per segment, every trial in one launch)
   PeriodLongPlan, Engine.periodlong  include/rtlws_periodlong.h (that search for frames of 2^16 .. 2^22 samples: a four-step transform through device memory)
+  AccelPlan, Engine.accel_search, Engine.accel_resample  include/rtlws_accel.h (acceleration search: that long-frame search of every series read through a table of quadratic index maps, no resampled copy in memory)
   Spectrum .......... include/spectrum.h      (reference src/spectrum.h:7-17)
   cic_decimate ...... include/resample.h      (reference src/resample.h:14)
   halfband_decimate . include/resample.h      (reference src/resample.h:17)
@@ -58,6 +59,7 @@ PULSE_LIB = os.path.join(LIB_DIR, "librtlws_pulse.so")   # include/rtlws_pulse.h
 FOLD_LIB = os.path.join(LIB_DIR, "librtlws_fold.so")     # include/rtlws_fold.h
 PERIOD_LIB = os.path.join(LIB_DIR, "librtlws_period.so") # include/rtlws_period.h
 PERIODLONG_LIB = os.path.join(LIB_DIR, "librtlws_periodlong.so")  # include/rtlws_periodlong.h
+ACCEL_LIB = os.path.join(LIB_DIR, "librtlws_accel.so")   # include/rtlws_accel.h
 CBB_LIB = os.path.join(LIB_DIR, "librtlws_cbb.so")       # include/cbb_main.h
 SYNTH_LIB = os.path.join(LIB_DIR, "librtlws_synth.so")   # synthetic rtl_sensor.h + signal_source.h
 
@@ -175,6 +177,10 @@ PERIODLONG_SYMBOLS = ["rtlws_periodlong_supported", "rtlws_periodlong_geometry",
 PERIODLONG_MIN_LOG2N, PERIODLONG_MAX_LOG2N, PERIODLONG_MAX_LEVELS, PERIODLONG_MAX_TRIALS, PERIODLONG_STAGES = 16, 22, 5, 65536, 6
 PERIODLONG_MIN_NORM, PERIODLONG_MAX_NORM, PERIODLONG_MIN_SEG, PERIODLONG_MAX_SEG = 16, 16384, 64, 16384
 PERIODLONG_WORKSPACE_CAP = 1 << 30
+ACCEL_SYMBOLS = ["rtlws_accel_supported", "rtlws_accel_geometry", "rtlws_accel_open", "rtlws_accel_workspace_bytes", "rtlws_accel_search",
+                 "rtlws_accel_resample", "rtlws_accel_coef", "rtlws_accel_coef_from_shift", "rtlws_accel_shift", "rtlws_accel_close",
+                 "rtlws_accel_last_error"]
+ACCEL_MAX_NACCEL, ACCEL_MAX_COEF, ACCEL_MAX_VIRTUAL, ACCEL_STAGES = 1024, 1 << 40, 65536, 6
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -934,6 +940,66 @@ def periodlong_samples(log2n, level, k):
     return periodlong_lib().rtlws_periodlong_samples(int(log2n), int(level), int(k))
 
 
+_i64p = C.POINTER(C.c_int64)
+_ACCEL_PROTOTYPES = {
+    "rtlws_accel_supported": [_i, _i, _i, _i, _i, _i, _i64p], "rtlws_accel_geometry": [_i, _i, _i, _i, _i, _i, _i64p, _i, _ip, _ip, _ip, _ip],
+    "rtlws_accel_open": ([_vp, _i, _i, _i, _i, _i, _i, _i64p, _i], _vp), "rtlws_accel_workspace_bytes": ([_vp], C.c_size_t),
+    "rtlws_accel_search": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp], "rtlws_accel_resample": [_vp, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp],
+    "rtlws_accel_coef": ([C.c_double, C.c_double], C.c_int64), "rtlws_accel_coef_from_shift": ([C.c_double, _i], C.c_int64),
+    "rtlws_accel_shift": ([C.c_int64, _i, _i], C.c_long), "rtlws_accel_close": ([_vp], None), "rtlws_accel_last_error": ([], _str)}
+
+
+def accel_lib():
+    """librtlws_accel.so (include/rtlws_accel.h); it needs librtlws_hip.so's engine."""
+    return _satellite(ACCEL_LIB, _ACCEL_PROTOTYPES)
+
+
+def accel_last_error():
+    return accel_lib().rtlws_accel_last_error().decode()
+
+
+def _accel_table(coefs):
+    """A table as the library reads it: (naccel, int64 [naccel] or None for a NULL table, its pointer or None)."""
+    if coefs is None:
+        return 0, None, None
+    table = np.ascontiguousarray(coefs, dtype=np.int64).reshape(-1)
+    return table.size, table, table.ctypes.data_as(_i64p) if table.size else None
+
+
+def accel_supported(log2n, levels, norm, seg, klo, coefs, naccel=None):
+    """rtlws_accel_supported of a table int64 [naccel] (naccel: the table's size unless given; None: a NULL table).  No
+    GPU needed."""
+    n, _table, ptr = _accel_table(coefs)
+    return accel_lib().rtlws_accel_supported(int(log2n), int(levels), int(norm), int(seg), int(klo), n if naccel is None else int(naccel), ptr)
+
+
+def accel_geometry(log2n, levels, norm, seg, klo, coefs, ntrials=1, naccel=None):
+    """rtlws_accel_geometry: (rc, workgroups over all ntrials * naccel virtual trials, threads, LDS bytes -- a tuple of
+    ACCEL_STAGES each -- and segments).  No GPU needed."""
+    n, _table, ptr = _accel_table(coefs)
+    v = [(C.c_int * ACCEL_STAGES)() for _ in range(3)]
+    nseg = C.c_int()
+    rc = accel_lib().rtlws_accel_geometry(int(log2n), int(levels), int(norm), int(seg), int(klo), n if naccel is None else int(naccel), ptr,
+                                          int(ntrials), v[0], v[1], v[2], C.byref(nseg))
+    return (rc,) + tuple(tuple(x) for x in v) + (nseg.value,)
+
+
+def accel_coef(accel_m_s2, tsamp_s):
+    """rtlws_accel_coef: the integer nearest accel * tsamp / (2 c) * 2^64; 0 where it is refused.  No GPU needed."""
+    return int(accel_lib().rtlws_accel_coef(float(accel_m_s2), float(tsamp_s)))
+
+
+def accel_coef_from_shift(mid_shift_samples, nsamp):
+    """rtlws_accel_coef_from_shift: the integer nearest shift * 4 / (nsamp - 1)^2 * 2^64; 0 where it is refused.  No GPU
+    needed."""
+    return int(accel_lib().rtlws_accel_coef_from_shift(float(mid_shift_samples), int(nsamp)))
+
+
+def accel_shift(coef, nsamp, n):
+    """rtlws_accel_shift: s_c(n), exactly; 0 where an argument is out of range.  No GPU needed."""
+    return int(accel_lib().rtlws_accel_shift(int(coef), int(nsamp), int(n)))
+
+
 def ddc_last_error():
     return ddc_lib().rtlws_ddc_last_error().decode()
 
@@ -1406,6 +1472,35 @@ class PeriodLongPlan(_Plan):
         nseg] (f32, int32), d_power and d_white [ntrials, M] (f32) or None."""
         return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
                           self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+
+
+class AccelPlan(_Plan):
+    """rtlws_accel_plan* of include/rtlws_accel.h: rtlws_periodlong.h's tables, the coefficients (int64 [naccel]) and a
+    workspace for min(max_trials, what fits under the cap) virtual trials in flight on the engine's device, the kernels of
+    the frame length loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    _name, _lib = "accel", staticmethod(accel_lib)
+
+    def __init__(self, eng, log2n, levels, norm, seg, klo, coefs, max_trials=1):
+        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
+        self.naccel, self.coefs, ptr = _accel_table(coefs)
+        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo, self.naccel, ptr, int(max_trials))
+        self.nbins = 1 << (self.log2n - 1)
+        self.nseg = self.nbins // self.seg
+
+    def workspace_bytes(self):
+        return self._fn("workspace_bytes")(self.h)
+
+    def search(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
+        """Six launches a group of virtual trials: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials,
+        naccel, levels, nseg] (f32, int32), d_power and d_white [ntrials, naccel, M] (f32) or None."""
+        return self._call("search", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
+                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+
+    def resample(self, d_in, in_stride, ntrials, nsamp, a_first, a_count, d_out, out_stride, stream=None, check=True):
+        """One launch: the series of (t, a), a = a_first .. a_first + a_count - 1, at d_out + (t * a_count + a - a_first) *
+        out_stride elements."""
+        return self._call("resample", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), int(a_first), int(a_count),
+                          self._ptr(d_out), int(out_stride), stream)
 
 
 class PfbXcPlan(_PolyphasePlan):
@@ -1976,6 +2071,80 @@ class Engine:
         shape = (ntrials, plan.levels, plan.nseg)
         return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, plan.nbins) if want_power else None,
                 white.reshape(ntrials, plan.nbins) if want_white else None)
+
+    # -- include/rtlws_accel.h: host series in, (best, at, power, white) out with a leading [ntrials, naccel] ----
+    def _accel_series(self, series, nsamp, in_stride):
+        series = np.ascontiguousarray(series, dtype=np.float32)
+        if in_stride is not None:
+            series = series.reshape(-1, int(in_stride))
+        assert series.ndim == 2, "the series are [ntrials, nsamp]"
+        samples = series.shape[1]
+        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
+            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        nsamp = samples if nsamp is None else int(nsamp)
+        assert samples >= nsamp, "fewer samples than nsamp"
+        return series, nsamp
+
+    def accel_search(self, series, log2n, levels, norm, seg, klo, coefs, nsamp=None, in_stride=None, want_rows=True, fill=None,
+                     max_trials=None, want_power=None, want_white=None):
+        """rtlws_accel_search with Engine.periodlong's arguments and, over the ntrials * naccel virtual trials, its
+        results: (float32 [ntrials, naccel, levels, nseg] the peaks, int32 of that shape their bins, float32 [ntrials,
+        naccel, M] the power spectra and the whitened ones, or None).  max_trials counts virtual trials (None: all of
+        them).  With `fill` the four come back as the whole flat buffers, PERIOD_GUARD elements longer than the outputs."""
+        series, nsamp = self._accel_series(series, nsamp, in_stride)
+        ntrials, width = series.shape
+        naccel = np.asarray(coefs).size
+        nv = ntrials * naccel
+        plan = AccelPlan(self, log2n, levels, norm, seg, klo, coefs, nv if max_trials is None else max_trials)
+        want_power = want_rows if want_power is None else want_power
+        want_white = want_rows if want_white is None else want_white
+        guard = 0 if fill is None else PERIOD_GUARD
+        preset = np.float32(0.0 if fill is None else fill)
+        npeaks, nrows = nv * plan.levels * plan.nseg, nv * plan.nbins
+        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
+                 np.full((nrows if want_power or fill is not None else 0) + guard, preset, np.float32),
+                 np.full((nrows if want_white or fill is not None else 0) + guard, preset, np.float32)]
+        bufs = [self.upload(series)] + [self.upload(h) if h.size else None for h in hosts]
+        try:
+            plan.search(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_power else None, bufs[4] if want_white else None)
+            self.sync()
+            best, at, power, white = [h if b is None else self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
+        finally:
+            plan.close()
+            for b in bufs:
+                if b is not None:
+                    b.free()
+        if fill is not None:
+            return best, at, power, white
+        shape = (ntrials, naccel, plan.levels, plan.nseg)
+        return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, naccel, plan.nbins) if want_power else None,
+                white.reshape(ntrials, naccel, plan.nbins) if want_white else None)
+
+    def accel_resample(self, series, log2n, coefs, a_first=0, a_count=None, nsamp=None, in_stride=None, out_stride=None, fill=None):
+        """rtlws_accel_resample: series float32 [ntrials, nsamp] (with in_stride: [ntrials, in_stride], the padding as the
+        caller left it), coefs int64 [naccel] -> float32 [ntrials, a_count, nsamp], the series read through the maps of
+        accelerations a_first .. a_first + a_count - 1 (a_count None: the rest of the table).  out_stride None: nsamp
+        rounded up to a multiple of 4.  With `fill` (a float32) the whole flat buffer comes back, [ntrials * a_count *
+        out_stride + PERIOD_GUARD] elements preset to fill, so that a caller sees what the run left untouched."""
+        series, nsamp = self._accel_series(series, nsamp, in_stride)
+        ntrials, width = series.shape
+        naccel = np.asarray(coefs).size
+        a_count = naccel - int(a_first) if a_count is None else int(a_count)
+        out_stride = (nsamp + 3) // 4 * 4 if out_stride is None else int(out_stride)
+        plan = AccelPlan(self, log2n, 1, PERIODLONG_MIN_NORM, PERIODLONG_MIN_SEG, 1, coefs)
+        host = np.full(ntrials * a_count * out_stride + PERIOD_GUARD, np.float32(0.0 if fill is None else fill), np.float32)
+        bufs = [self.upload(series), self.upload(host)]
+        try:
+            plan.resample(bufs[0], width, ntrials, nsamp, a_first, a_count, bufs[1], out_stride)
+            self.sync()
+            out = self.download(bufs[1], np.float32, host.shape)
+        finally:
+            plan.close()
+            for b in bufs:
+                b.free()
+        if fill is not None:
+            return out
+        return out[:ntrials * a_count * out_stride].reshape(ntrials, a_count, out_stride)[:, :, :nsamp]
 
     # -- include/rtlws_pfbxc.h: host arrays in, (auto rows, cross rows) out ----
     def pfbxc(self, iqs, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
