@@ -1,6 +1,6 @@
-// accel_shim.hip -- extern "C" glue of include/rtlws_accel.h (librtlws_accel.so): argument rules, the plan with
-// periodlong's tables, the table of coefficients and the workspace, the groups of virtual trials of a run, and the host
-// helpers of the map.  The engine (device, stream) is librtlws_hip.so's; nothing here reads the environment, and
+// accel_shim.hip -- extern "C" glue of include/rtlws_accel.h (librtlws_accel.so) over the family's rules and long-frame
+// plan (period_plan.h): the table's rules, the plan with the table of coefficients added, the groups of virtual trials
+// of a run, and the host helpers of the map.  The engine (device, stream) is librtlws_hip.so's; nothing here reads the environment, and
 // nothing of a run is computed on the host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
@@ -9,19 +9,12 @@
 #include <vector>
 
 #include "accel.h"
-#include "periodlong_plan.h"
+#include "period_plan.h"
 #include "rtlws_accel.h"
-#include "shim_common.h"
 
-// The tables, the coefficients and the workspace on the engine's device
-struct rtlws_accel_plan {
-    rtlws_engine* engine;
-    int device;
-    int log2n, levels, log2norm, seg, klo, naccel;
-    int group;                 // virtual trials in flight
-    size_t ws_bytes;
-    float2* d_tables;          // tw [M], twist [M], tw_row [M2], tw256 [256]
-    char* d_ws;                // z [group][M] float2, pw [group][M] float, sums [group][64] double
+// The family's long-frame plan (period_plan.h) and the coefficients on the engine's device
+struct rtlws_accel_plan : rtlws::periodlong::Plan {
+    int naccel;
     int64_t* d_coefs;          // [naccel]
 };
 
@@ -35,26 +28,15 @@ static_assert(MAX_NACCEL == RTLWS_ACCEL_MAX_NACCEL && MAX_COEF == RTLWS_ACCEL_MA
               "rtlws_accel.h and accel.h disagree");
 
 const char* const WHY_VIRTUAL = "ntrials * naccel must be at most 65536";
-const char* const WHY_NSAMP = "nsamp must be 1 .. 4194304";
 
 // periodlong's rules, then naccel, the table, its entries in order
 const char* why_not_table(int log2n, int levels, int norm, int seg, int klo, int naccel, const int64_t* coefs)
 {
-    if (const char* why = why_not_plan(log2n, levels, norm, seg, klo)) return why;
+    if (const char* why = why_not_long_plan(log2n, levels, norm, seg, klo)) return why;
     if (naccel < 1 || naccel > MAX_NACCEL) return "naccel must be 1 .. 1024";
     if (!coefs) return "null table of coefficients";
     for (int a = 0; a < naccel; ++a)
         if (coefs[a] < -MAX_COEF || coefs[a] > MAX_COEF) return "every coefficient must be -2^40 .. 2^40";
-    return nullptr;
-}
-
-// what both runs refuse first, in rtlws_periodlong_run's order and words
-const char* why_not_input(int ntrials, int nsamp, long in_stride)
-{
-    if (const char* why = why_not_ntrials(ntrials)) return why;
-    if (nsamp < 1 || nsamp > (1 << pl::MAX_LOG2N)) return WHY_NSAMP;
-    if (in_stride < nsamp) return "in_stride must be >= nsamp";
-    if (in_stride % 4) return "in_stride must be a multiple of 4";
     return nullptr;
 }
 
@@ -127,49 +109,25 @@ int rtlws_accel_geometry(int log2n, int levels, int norm, int seg, int klo, int 
     return 0;
 }
 
+void rtlws_accel_close(rtlws_accel_plan* p)
+{
+    if (p && hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_coefs);
+    close_plan(p);
+}
+
 rtlws_accel_plan* rtlws_accel_open(rtlws_engine* e, int log2n, int levels, int norm, int seg, int klo, int naccel, const int64_t* coefs,
                                    int max_trials)
 {
-    const char* fn = "rtlws_accel_open";
-    g_err.clear();
-    const char* why = why_not_table(log2n, levels, norm, seg, klo, naccel, coefs);
-    if (!why && max_trials < 1) why = "max_trials must be >= 1";
-    const int device = open_device(fn, why, e);
-    if (device < 0) return nullptr;
-    const std::vector<float2> t = host_tables(log2n);
-    const int group = in_flight(log2n, max_trials);
-    const size_t ws_bytes = (size_t)group * pl::trial_bytes(log2n);
-    float2* d_tables = nullptr;
-    char* d_ws = nullptr;
-    int64_t* d_coefs = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_tables), t.size() * sizeof(float2));
-    if (err == hipSuccess) err = hipMemcpy(d_tables, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&d_coefs), (size_t)naccel * sizeof(int64_t));
-    if (err == hipSuccess) err = hipMemcpy(d_coefs, coefs, (size_t)naccel * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&d_ws), ws_bytes);
-    if (err == hipSuccess) err = prepare(log2n, device);
-    if (err != hipSuccess) {
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_coefs) (void)hipFree(d_coefs);
-        if (d_ws) (void)hipFree(d_ws);
-        fail_hip(fn, "the tables, the workspace or the kernels", err);
-        return nullptr;
-    }
-    return new rtlws_accel_plan{e, device, log2n, levels, log2_of(norm), seg, klo, naccel, group, ws_bytes, d_tables, d_ws, d_coefs};
+    const auto upload = [&](rtlws_accel_plan& p) {
+        p.naccel = naccel;
+        const hipError_t err = hipMalloc(reinterpret_cast<void**>(&p.d_coefs), (size_t)naccel * sizeof(int64_t));
+        return err != hipSuccess ? err : hipMemcpy(p.d_coefs, coefs, (size_t)naccel * sizeof(int64_t), hipMemcpyHostToDevice);
+    };
+    return open_plan<rtlws_accel_plan>("rtlws_accel_open", why_not_table(log2n, levels, norm, seg, klo, naccel, coefs), e, log2n, levels, norm, seg,
+                                       klo, max_trials, upload, rtlws_accel_close);
 }
 
 size_t rtlws_accel_workspace_bytes(const rtlws_accel_plan* p) { return p ? p->ws_bytes : 0; }
-
-void rtlws_accel_close(rtlws_accel_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) {
-        (void)hipFree(p->d_tables);
-        (void)hipFree(p->d_coefs);
-        (void)hipFree(p->d_ws);
-    }
-    delete p;
-}
 
 int rtlws_accel_search(rtlws_accel_plan* p, const float* d_in, long in_stride, int ntrials, int nsamp, float* d_best, int32_t* d_at,
                        float* d_power, float* d_white, void* stream)
@@ -177,13 +135,7 @@ int rtlws_accel_search(rtlws_accel_plan* p, const float* d_in, long in_stride, i
     const char* fn = "rtlws_accel_search";
     g_err.clear();
     // what needs no plan
-    if (const char* why = why_not_input(ntrials, nsamp, in_stride)) return fail(fn, why, -1);
-    if (!d_in || !d_best || !d_at) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_in) & 15u) return fail(fn, "d_in must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_best) & 3u) return fail(fn, "d_best must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_at) & 3u) return fail(fn, "d_at must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_power) & 3u) return fail(fn, "d_power must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_white) & 3u) return fail(fn, "d_white must be 4-byte aligned", -1);
+    if (const char* why = why_not_run(ntrials, nsamp, pl::MAX_LOG2N, WHY_LONG_NSAMP, in_stride, d_in, d_best, d_at, d_power, d_white)) return fail(fn, why, -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     if ((long)ntrials * p->naccel > MAX_VIRTUAL) return fail(fn, WHY_VIRTUAL, -1);
@@ -192,24 +144,16 @@ int rtlws_accel_search(rtlws_accel_plan* p, const float* d_in, long in_stride, i
     hipError_t err = hipSetDevice(p->device);
     if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
     Params kp;
-    kp.s = plan_params(p->log2n, p->levels, p->log2norm, p->seg, p->klo, p->group, p->d_tables, p->d_ws);
-    kp.s.in = d_in;
-    kp.s.best = d_best;
-    kp.s.at = d_at;
-    kp.s.power = d_power;
-    kp.s.white = d_white;
-    kp.s.in_stride = in_stride;
-    kp.s.nsamp = nsamp;
+    kp.s = run_params(*p, d_in, in_stride, nsamp, d_best, d_at, d_power, d_white);
     kp.coefs = p->d_coefs;
     kp.naccel = p->naccel;
     const hipStream_t st = stream_of(p->engine, stream);
-    // groups of virtual trials that fit the workspace, one after the other on the stream
-    const int nvirtual = ntrials * p->naccel;
-    for (int v0 = 0; v0 < nvirtual; v0 += p->group) {
+    // the groups are of virtual trials: every one reads the caller's series from its first trial on
+    err = for_groups(*p, ntrials * p->naccel, [&](int v0, int g) {
         kp.s.trial0 = v0;
-        err = launch_group(kp, nvirtual - v0 < p->group ? nvirtual - v0 : p->group, st);
-        if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
-    }
+        return launch_group(kp, g, st);
+    });
+    if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }
 
@@ -219,7 +163,7 @@ int rtlws_accel_resample(rtlws_accel_plan* p, const float* d_in, long in_stride,
     const char* fn = "rtlws_accel_resample";
     g_err.clear();
     // what needs no plan
-    if (const char* why = why_not_input(ntrials, nsamp, in_stride)) return fail(fn, why, -1);
+    if (const char* why = why_not_input(ntrials, nsamp, pl::MAX_LOG2N, WHY_LONG_NSAMP, in_stride)) return fail(fn, why, -1);
     if (out_stride < nsamp) return fail(fn, "out_stride must be >= nsamp", -1);
     if (out_stride % 4) return fail(fn, "out_stride must be a multiple of 4", -1);
     if (a_count < 1) return fail(fn, "a_count must be >= 1", -1);
@@ -271,7 +215,7 @@ long rtlws_accel_shift(int64_t coef, int nsamp, int n)
     const char* fn = "rtlws_accel_shift";
     g_err.clear();
     if (coef < -MAX_COEF || coef > MAX_COEF) return fail(fn, "the coefficient must be -2^40 .. 2^40", 0);
-    if (nsamp < 1 || nsamp > (1 << pl::MAX_LOG2N)) return fail(fn, WHY_NSAMP, 0);
+    if (nsamp < 1 || nsamp > (1 << pl::MAX_LOG2N)) return fail(fn, WHY_LONG_NSAMP, 0);
     if (n < 0 || n >= nsamp) return fail(fn, "n must be 0 .. nsamp - 1", 0);
     return shift(coef, n, nsamp - 1);
 }

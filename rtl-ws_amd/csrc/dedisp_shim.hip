@@ -261,7 +261,7 @@ long rtlws_dedisp_rows_needed(const rtlws_dedisp_plan* p, long nout)
     const char* fn = "rtlws_dedisp_rows_needed";
     g_err.clear();
     if (const char* why = why_not_nout(nout)) return fail(fn, why, -1);
-    if (!p) return fail(fn, "null plan (no usable HIP device: there is no CPU path)", -1);
+    if (!p) return fail(fn, NULL_PLAN, -1);
     return nout ? nout + p->max_delay : 0;
 }
 
@@ -277,7 +277,7 @@ int rtlws_dedisp_run(rtlws_dedisp_plan* p, const float* d_rows, long in_stride, 
     if (nout > 0 && (!d_rows || !d_out)) return fail(fn, "null pointer", -1);
     if (reinterpret_cast<uintptr_t>(d_rows) & 15u) return fail(fn, "d_rows must be 16-byte aligned", -1);
     if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(fn, "d_out must be 4-byte aligned", -1);
-    if (!p) return fail(fn, "null plan (no usable HIP device: there is no CPU path)", -1);
+    if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     if (in_stride < p->nchan) return fail(fn, "in_stride must be >= nchan", -1);
     if (const char* why = why_not_grid(nout, p->ntrials, p->layout)) return fail(fn, why, -1);

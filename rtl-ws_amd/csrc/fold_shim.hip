@@ -31,8 +31,6 @@ static_assert(MAX_PERIODS == RTLWS_FOLD_MAX_PERIODS && MIN_BINS == RTLWS_FOLD_MI
                   MAX_NSAMP == RTLWS_FOLD_MAX_NSAMP,
               "rtlws_fold.h and fold.h disagree");
 
-const char* const NULL_PLAN = "null plan (no usable HIP device: there is no CPU path)";
-
 // ---- the rules, each worded once ----
 const char* why_not_nperiods(int nperiods) { return nperiods < 1 || nperiods > MAX_PERIODS ? "nperiods must be 1 .. 4096" : nullptr; }
 

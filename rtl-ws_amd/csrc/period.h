@@ -1,5 +1,6 @@
 // period.h -- shared between period.hip (the kernel) and period_shim.hip (rtlws_period.h's host glue): the limits, the
-// workgroup a frame length takes and the kernel's arguments.
+// workgroup a frame length takes and the kernel's arguments; and what the whole periodicity-search family
+// takes from here (periodlong.h includes it): LANES, MAX_LEVELS, MIN_NORM, MIN_SEG and chunk_of.
 #ifndef RTLWS_CSRC_PERIOD_H
 #define RTLWS_CSRC_PERIOD_H
 
@@ -20,9 +21,10 @@ constexpr int lds_bytes(int log2n) { return 8 * ((1 << (log2n - 1)) + (1 << (log
 static_assert(threads_of(10) == 64 && threads_of(11) == 64 && threads_of(12) == 128 && threads_of(15) == 1024, "a workgroup's threads");
 static_assert(lds_bytes(15) == 136 * 1024 && lds_bytes(10) == 4352, "a workgroup's LDS");
 
-// The k a wavefront walks before it reduces its lanes' peaks: a segment, but never more than 1024 (so that every
-// wavefront of a workgroup has a chunk), the partial peaks of a longer segment meeting in LDS
-constexpr int chunk_of(int log2n, int seg) { return seg < 1024 ? seg : (1 << (log2n - 1)) < 1024 ? (1 << (log2n - 1)) : 1024; }
+// The k a wavefront walks before it reduces its lanes' peaks, of the `bins` bins a workgroup has in view (a trial's M
+// here, a span of 16384 in periodlong.h): a segment, but never more than 1024 (so that every wavefront of a workgroup
+// has a chunk), the partial peaks of a longer segment meeting in LDS
+constexpr int chunk_of(int bins, int seg) { return seg < 1024 ? seg : bins < 1024 ? bins : 1024; }
 
 struct Params {
     const float* in;

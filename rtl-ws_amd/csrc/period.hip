@@ -7,35 +7,20 @@
 //   3  the real-input untangling and the square: P[k] over the tile as f32, k < M
 //   4  the whitening blocks' halving trees (registers, then lanes, then wavefronts), W = P / mean over P
 //   5  the harmonic sums, lanes along k, and the peaks of every level and segment
+// meet and meet_lanes are period_stages.h's.  Stages 3, 4 and 5 are written out here; periodlong.hip restates 4 and 5 over
+// spans of a row in device memory and takes 3 from period_stages.h (DESIGN.md 4.24a says why the text is not one).
 #include <hip/hip_runtime.h>
 
 #include "period.h"
+#include "period_stages.h"
 #include "row_fft.h"
 #include "rtlws_internal.h"
 
 namespace rtlws {
 namespace period {
 
-namespace {
-
-// the rule of the peaks between two partial results (best, at): the strict maximum, ties to the smaller k; a partial
-// that took nothing is (-Inf, -1) and never wins
-__device__ __forceinline__ void meet(float& best, int& at, float ob, int oa)
-{
-    if (ob > best || (ob == best && oa < at)) best = ob, at = oa;
-}
-
-__device__ __forceinline__ void meet_lanes(float& best, int& at)
-{
-#pragma unroll
-    for (int off = 1; off < LANES; off <<= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(at, off);
-        meet(best, at, ob, oa);
-    }
-}
-
-}  // namespace
+using stages::meet;
+using stages::meet_lanes;
 
 template <int LOG2N>
 __global__ __launch_bounds__(threads_of(LOG2N)) void period_kernel(const Params p)
@@ -191,7 +176,7 @@ __global__ __launch_bounds__(threads_of(LOG2N)) void period_kernel(const Params 
     // ---- 5: the harmonic sums and the peaks: a wavefront walks a chunk of k, a lane every 64th ----
     {
         const int levels = p.levels, seg = p.seg, klo = p.klo;
-        const int chunk = chunk_of(LOG2N, seg), nchunks = M / chunk, nseg = M / seg;
+        const int chunk = chunk_of(M, seg), nchunks = M / chunk, nseg = M / seg;
         const float ninf = -__builtin_huge_valf();
         for (int c = wave; c < nchunks; c += WAVES) {
             float best[MAX_LEVELS];

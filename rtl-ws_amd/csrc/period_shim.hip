@@ -10,8 +10,8 @@
 #include <vector>
 
 #include "period.h"
+#include "period_plan.h"
 #include "rtlws_period.h"
-#include "shim_common.h"
 #include "twiddle_tables.h"
 
 // The transform's table on the engine's device
@@ -30,21 +30,12 @@ static_assert(MIN_LOG2N == RTLWS_PERIOD_MIN_LOG2N && MAX_LOG2N == RTLWS_PERIOD_M
                   MIN_NORM == RTLWS_PERIOD_MIN_NORM && MIN_SEG == RTLWS_PERIOD_MIN_SEG && MAX_TRIALS == RTLWS_PERIOD_MAX_TRIALS,
               "rtlws_period.h and period.h disagree");
 
-const char* const NULL_PLAN = "null plan (no usable HIP device: there is no CPU path)";
+// ---- the library's own rules; a run's, ntrials' and the period of a bin are the family's (period_plan.h) ----
+const char* why_not_log2n(int log2n) { return log2n < MIN_LOG2N || log2n > MAX_LOG2N ? "log2n must be 10 .. 15" : nullptr; }
 
-bool power_of_two(int v) { return v > 0 && !(v & (v - 1)); }
-
-int log2_of(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
-// ---- the rules, each worded once ----
 const char* why_not_plan(int log2n, int levels, int norm, int seg, int klo)
 {
-    if (log2n < MIN_LOG2N || log2n > MAX_LOG2N) return "log2n must be 10 .. 15";
+    if (const char* why = why_not_log2n(log2n)) return why;
     const int m = 1 << (log2n - 1);
     if (levels < 1 || levels > MAX_LEVELS) return "levels must be 1 .. 5";
     if (norm < MIN_NORM || norm > m || !power_of_two(norm)) return "norm must be a power of two 16 .. N / 2";
@@ -52,8 +43,6 @@ const char* why_not_plan(int log2n, int levels, int norm, int seg, int klo)
     if (klo < 1 || klo > m - 1) return "klo must be 1 .. N / 2 - 1";
     return nullptr;
 }
-
-const char* why_not_ntrials(int ntrials) { return ntrials < 1 || ntrials > MAX_TRIALS ? "ntrials must be 1 .. 65536" : nullptr; }
 
 }  // namespace
 
@@ -119,16 +108,7 @@ int rtlws_period_run(rtlws_period_plan* p, const float* d_in, long in_stride, in
     const char* fn = "rtlws_period_run";
     g_err.clear();
     // what needs no plan
-    if (const char* why = why_not_ntrials(ntrials)) return fail(fn, why, -1);
-    if (nsamp < 1 || nsamp > (1 << MAX_LOG2N)) return fail(fn, "nsamp must be 1 .. 32768", -1);
-    if (in_stride < nsamp) return fail(fn, "in_stride must be >= nsamp", -1);
-    if (in_stride % 4) return fail(fn, "in_stride must be a multiple of 4", -1);
-    if (!d_in || !d_best || !d_at) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_in) & 15u) return fail(fn, "d_in must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_best) & 3u) return fail(fn, "d_best must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_at) & 3u) return fail(fn, "d_at must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_power) & 3u) return fail(fn, "d_power must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_white) & 3u) return fail(fn, "d_white must be 4-byte aligned", -1);
+    if (const char* why = why_not_run(ntrials, nsamp, MAX_LOG2N, "nsamp must be 1 .. 32768", in_stride, d_in, d_best, d_at, d_power, d_white)) return fail(fn, why, -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     if (nsamp > (1 << p->log2n)) return fail(fn, "nsamp must be at most the plan's N", -1);
@@ -154,15 +134,7 @@ int rtlws_period_run(rtlws_period_plan* p, const float* d_in, long in_stride, in
     return 0;
 }
 
-double rtlws_period_samples(int log2n, int level, int k)
-{
-    const char* fn = "rtlws_period_samples";
-    g_err.clear();
-    if (log2n < MIN_LOG2N || log2n > MAX_LOG2N) return fail(fn, "log2n must be 10 .. 15", 0);
-    if (level < 0 || level >= MAX_LEVELS) return fail(fn, "level must be 0 .. 4", 0);
-    if (k < 1 || k > (1 << (log2n - 1)) - 1) return fail(fn, "k must be 1 .. N / 2 - 1", 0);
-    return (double)(1L << (log2n + level)) / (double)k;
-}
+double rtlws_period_samples(int log2n, int level, int k) { return samples("rtlws_period_samples", why_not_log2n(log2n), log2n, level, k); }
 
 double rtlws_period_lnq(double S, int H)
 {

@@ -6,12 +6,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "period.h"
+
 namespace rtlws {
 namespace periodlong {
 
-constexpr int MIN_LOG2N = 16, MAX_LOG2N = 22, MAX_LEVELS = 5, MIN_NORM = 16, MAX_NORM = 16384, MIN_SEG = 64, MAX_SEG = 16384,
-              MAX_TRIALS = 65536;
-constexpr int LANES = 64;
+// the family's own (period.h): the stages behind the transform are one text (period_stages.h)
+using period::LANES;
+using period::MAX_LEVELS;
+using period::MIN_NORM;
+using period::MIN_SEG;
+using period::chunk_of;
+constexpr int MIN_LOG2N = 16, MAX_LOG2N = 22, MAX_NORM = 16384, MAX_SEG = 16384, MAX_TRIALS = 65536;
 
 // N = 2^log2n real samples are M = N / 2 complex points z[j] = y[2 j] + i y[2 j + 1], M = M1 M2, j = j1 M2 + j2,
 // k = k1 + M1 k2: M1 = 16 up to log2n 19 and 256 above, M2 = 2^11 .. 2^14 the length of a row that row_fft.h transforms
@@ -61,10 +67,6 @@ constexpr int stage_lds(int stage, int log2n)
 
 // A trial in flight takes M float2 (the transform, in place), M float (P, then W over it) and the mean's partial sums
 constexpr size_t trial_bytes(int log2n) { return (size_t)12 * ((size_t)1 << (log2n - 1)) + 8 * MEAN_PARTS; }
-
-// The k a wavefront walks before it reduces its lanes' peaks: a segment, but never more than 1024, the partial peaks of
-// a longer segment meeting in LDS (period.h's rule over a span of 16384 bins)
-constexpr int chunk_of(int seg) { return seg < 1024 ? seg : 1024; }
 
 struct Params {
     const float* in;       // the first trial of the group

@@ -12,8 +12,12 @@
 //             real-input untangling and the square: P in natural order
 //   whiten    period.hip's stage 4 over spans of 16384 bins: W over P
 //   peaks     period.hip's stage 5 over spans of 16384 bins, W read through the caches
+// meet, meet_lanes and the untangling of a pair are period_stages.h's.  Stages 4 and 5 are written out here as they are
+// in period.hip, line for line but for a span's first bin: as templates they compile to other instructions (DESIGN.md
+// 4.24a), and tests/test_period_family_digest_gpu.py holds the two texts to the same bits.
 #include <hip/hip_runtime.h>
 
+#include "period_stages.h"
 #include "periodlong.h"
 #include "periodlong_front.h"
 #include "row_fft.h"
@@ -22,26 +26,9 @@
 namespace rtlws {
 namespace periodlong {
 
-namespace {
-
-// period.hip's rule of the peaks between two partial results (best, at): the strict maximum, ties to the smaller k; a
-// partial that took nothing is (-Inf, -1) and never wins
-__device__ __forceinline__ void meet(float& best, int& at, float ob, int oa)
-{
-    if (ob > best || (ob == best && oa < at)) best = ob, at = oa;
-}
-
-__device__ __forceinline__ void meet_lanes(float& best, int& at)
-{
-#pragma unroll
-    for (int off = 1; off < LANES; off <<= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(at, off);
-        meet(best, at, ob, oa);
-    }
-}
-
-}  // namespace
+namespace stages = period::stages;
+using stages::meet;
+using stages::meet_lanes;
 
 // ---- mean and cols: periodlong_front.h's text over the series as it lies, the trial of a workgroup at blockIdx.y ----
 __device__ __forceinline__ front::Plain series_of(const Params& p) { return front::Plain{p.in + (long)blockIdx.y * p.in_stride}; }
@@ -75,7 +62,7 @@ __global__ __launch_bounds__(rows_threads(LOG2M2)) void rows_kernel(const Params
 }
 
 // ---- untangle: workgroup (i, trial) takes bins k = K0 .. K0 + L - 1, K0 = i L < M / 2, and their mirrors M - k ----
-// X[k] = E - i W^k O, X[M - k] = conj(E) - i conj(W^k O), E, O = (Z[k] +- conj Z[M - k]) / 2, as period.hip does
+// the pair's arithmetic is period_stages.h's untangle and power, the arithmetic of period.hip's stage 3
 template <int LOG2M1>
 __global__ __launch_bounds__(UNTANGLE_THREADS) void untangle_kernel(const Params p)
 {
@@ -109,13 +96,9 @@ __global__ __launch_bounds__(UNTANGLE_THREADS) void untangle_kernel(const Params
         } else {
             const int km = m - k;
             const f2 zb = tb[(km & (M1 - 1)) * PITCH + ((km >> LOG2M1) - b0)];
-            const float2 w = p.tw[k];
-            const f2 e = mk(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));
-            const f2 o = mk(0.5f * (za.x - zb.x), 0.5f * (za.y + zb.y));
-            const f2 t = cmul(o, mk(w.x, w.y));
-            const float ax = e.x + t.y, ay = e.y - t.x, bx = e.x - t.y, by = e.y + t.x;
-            pk = fmaf(ax, ax, ay * ay);
-            const float pm = fmaf(bx, bx, by * by);
+            const stages::Pair x = stages::untangle(za, zb, p.tw[k]);
+            pk = stages::power(x.a);
+            const float pm = stages::power(x.b);
             pw[km] = pm;
             if (power) __builtin_nontemporal_store(pm, power + km);
         }
@@ -125,12 +108,7 @@ __global__ __launch_bounds__(UNTANGLE_THREADS) void untangle_kernel(const Params
     if (k0 + L == m / 2 && tid == 0) {                       // the bin that is its own mirror: row 0, column M2 / 2
         const int k = m / 2;
         const f2 zh = tb[0];
-        const float2 w = p.tw[k];
-        const f2 e = mk(0.5f * (zh.x + zh.x), 0.5f * (zh.y - zh.y));
-        const f2 o = mk(0.5f * (zh.x - zh.x), 0.5f * (zh.y + zh.y));
-        const f2 t = cmul(o, mk(w.x, w.y));
-        const float ax = e.x + t.y, ay = e.y - t.x;
-        const float pk = fmaf(ax, ax, ay * ay);
+        const float pk = stages::power(stages::untangle(zh, zh, p.tw[k]).a);
         pw[k] = pk;
         if (power) __builtin_nontemporal_store(pk, power + k);
     }
@@ -204,7 +182,7 @@ __global__ __launch_bounds__(SPAN_THREADS) void peaks_kernel(const Params p)
     const float* const pw = p.pw + ((long)blockIdx.y << log2m);
     const long trial = p.trial0 + (int)blockIdx.y;
     const int levels = p.levels, seg = p.seg, klo = p.klo;
-    const int chunk = chunk_of(seg), nchunks = SPAN / chunk, nseg = (1 << log2m) / seg;
+    const int chunk = chunk_of(SPAN, seg), nchunks = SPAN / chunk, nseg = (1 << log2m) / seg;
     const int kb = (int)blockIdx.x * SPAN, segb = kb / seg;  // the span's first bin and segment
     const float ninf = -__builtin_huge_valf();
     for (int c = wave; c < nchunks; c += WAVES) {

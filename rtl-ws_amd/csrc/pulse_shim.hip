@@ -32,8 +32,6 @@ static_assert(MAX_WIDTHS == RTLWS_PULSE_MAX_WIDTHS && MAX_WIDTH == RTLWS_PULSE_M
                   MAX_SEG == RTLWS_PULSE_MAX_SEG && MAX_TRIALS == RTLWS_PULSE_MAX_TRIALS && MAX_NOUT == RTLWS_PULSE_MAX_NOUT,
               "rtlws_pulse.h and pulse.h disagree");
 
-const char* const NULL_PLAN = "null plan (no usable HIP device: there is no CPU path)";
-
 // ---- the rules, each worded once ----
 const char* why_not_table(int nwidths, const int32_t* widths, long seg)
 {

@@ -32,6 +32,9 @@ thread_local std::string g_err;
     return -3;
 }
 
+// what a run answers to a null plan, beside the null engine's text below: the open that would have made it failed
+[[maybe_unused]] const char* const NULL_PLAN = "null plan (no usable HIP device: there is no CPU path)";
+
 // The head of an rtlws_*_open (pfb_plan.h, ddc_plan.h): `why`, the verdict of the library's own rules, or else the null
 // engine is refused; then the engine's device is made current.  That device, or -1 with the text recorded
 [[maybe_unused]] int open_device(const char* fn, const char* why, rtlws_engine* e)

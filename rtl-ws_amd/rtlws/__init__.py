@@ -1434,67 +1434,72 @@ class FoldPlan(_Plan):
                           self._ptr(d_hits), stream)
 
 
-class PeriodPlan(_Plan):
+class _SearchPlan(_Plan):
+    """The plans of the periodicity-search family (include/rtlws_period.h, rtlws_periodlong.h, rtlws_accel.h): the five
+    plan parameters, nbins = M and nseg = M / seg, and the marshalling of a search.  A subclass names its library and hands
+    __init__ what its open takes behind klo.  eng may be None (as a C caller's NULL engine): open then fails with the
+    library's text."""
+
+    def __init__(self, eng, log2n, levels, norm, seg, klo, *more):
+        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
+        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo, *more)
+        self.nbins = 1 << (self.log2n - 1)
+        self.nseg = self.nbins // self.seg
+
+    def _search(self, what, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power, d_white, stream, check):
+        return self._call(what, check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
+                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+
+
+class _LongSearchPlan(_SearchPlan):
+    """The two plans that keep a workspace on the device (the long frames')."""
+
+    def workspace_bytes(self):
+        return self._fn("workspace_bytes")(self.h)
+
+
+class PeriodPlan(_SearchPlan):
     """rtlws_period_plan* of include/rtlws_period.h: the transform's table on the engine's device, the kernel of the frame
-    length loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    length loaded."""
     _name, _lib = "period", staticmethod(period_lib)
 
     def __init__(self, eng, log2n, levels, norm, seg, klo):
-        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
-        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo)
-        self.nbins = 1 << (self.log2n - 1)
-        self.nseg = self.nbins // self.seg
+        super().__init__(eng, log2n, levels, norm, seg, klo)
 
     def run(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
         """One launch: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials, levels, nseg] (f32, int32),
         d_power and d_white [ntrials, M] (f32) or None."""
-        return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
-                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+        return self._search("run", d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power, d_white, stream, check)
 
 
-class PeriodLongPlan(_Plan):
+class PeriodLongPlan(_LongSearchPlan):
     """rtlws_periodlong_plan* of include/rtlws_periodlong.h: the tables and a workspace for min(max_trials, what fits under
-    the cap) trials in flight on the engine's device, the kernels of the frame length loaded.  eng may be None (as a C
-    caller's NULL engine): open then fails with the library's text."""
+    the cap) trials in flight on the engine's device, the kernels of the frame length loaded."""
     _name, _lib = "periodlong", staticmethod(periodlong_lib)
 
     def __init__(self, eng, log2n, levels, norm, seg, klo, max_trials=1):
-        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
-        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo, int(max_trials))
-        self.nbins = 1 << (self.log2n - 1)
-        self.nseg = self.nbins // self.seg
-
-    def workspace_bytes(self):
-        return self._fn("workspace_bytes")(self.h)
+        super().__init__(eng, log2n, levels, norm, seg, klo, int(max_trials))
 
     def run(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
         """Six launches a group of trials: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials, levels,
         nseg] (f32, int32), d_power and d_white [ntrials, M] (f32) or None."""
-        return self._call("run", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
-                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+        return self._search("run", d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power, d_white, stream, check)
 
 
-class AccelPlan(_Plan):
+class AccelPlan(_LongSearchPlan):
     """rtlws_accel_plan* of include/rtlws_accel.h: rtlws_periodlong.h's tables, the coefficients (int64 [naccel]) and a
     workspace for min(max_trials, what fits under the cap) virtual trials in flight on the engine's device, the kernels of
-    the frame length loaded.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
+    the frame length loaded."""
     _name, _lib = "accel", staticmethod(accel_lib)
 
     def __init__(self, eng, log2n, levels, norm, seg, klo, coefs, max_trials=1):
-        self.log2n, self.levels, self.norm, self.seg, self.klo = int(log2n), int(levels), int(norm), int(seg), int(klo)
         self.naccel, self.coefs, ptr = _accel_table(coefs)
-        self._open(eng, self.log2n, self.levels, self.norm, self.seg, self.klo, self.naccel, ptr, int(max_trials))
-        self.nbins = 1 << (self.log2n - 1)
-        self.nseg = self.nbins // self.seg
-
-    def workspace_bytes(self):
-        return self._fn("workspace_bytes")(self.h)
+        super().__init__(eng, log2n, levels, norm, seg, klo, self.naccel, ptr, int(max_trials))
 
     def search(self, d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power=None, d_white=None, stream=None, check=True):
         """Six launches a group of virtual trials: trial t at d_in + t * in_stride elements; d_best and d_at [ntrials,
         naccel, levels, nseg] (f32, int32), d_power and d_white [ntrials, naccel, M] (f32) or None."""
-        return self._call("search", check, self._ptr(d_in), int(in_stride), int(ntrials), int(nsamp), self._ptr(d_best),
-                          self._ptr(d_at), self._ptr(d_power), self._ptr(d_white), stream)
+        return self._search("search", d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power, d_white, stream, check)
 
     def resample(self, d_in, in_stride, ntrials, nsamp, a_first, a_count, d_out, out_stride, stream=None, check=True):
         """One launch: the series of (t, a), a = a_first .. a_first + a_count - 1, at d_out + (t * a_count + a - a_first) *
@@ -1914,6 +1919,49 @@ class Engine:
             d_out.free()
         return out if out_stride is not None else out[:, :nout]
 
+    # -- what the searches over series share: the shaped, padded series; the preset buffers, the run and the download ----
+    @staticmethod
+    def _series(series, in_stride, what="nsamp"):
+        """series as float32 [ntrials, width] (with in_stride: rows of in_stride elements, the padding as the caller left
+        it; without: zeros behind the samples up to a multiple of 4, the library's stride) -> (the array, its samples)"""
+        series = np.ascontiguousarray(series, dtype=np.float32)
+        if in_stride is not None:
+            series = series.reshape(-1, int(in_stride))
+        assert series.ndim == 2, "the series are [ntrials, %s]" % what
+        samples = series.shape[1]
+        if in_stride is None and samples % 4:
+            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        return series, samples
+
+    def _search(self, plan, call, series, nsamp, lead_shape, want_power, want_white, fill):
+        """call(d_in, in_stride, ntrials, nsamp, d_best, d_at, d_power, d_white) of `plan` over the uploaded series into
+        preset buffers, the plan closed behind it -> (best, at, power, white) with lead_shape in front of [levels, nseg]
+        and [M]; an optional row that is neither wanted nor preset is not allocated and comes back None.  With `fill` the
+        four whole flat buffers, PERIOD_GUARD elements longer than the outputs, every element preset to fill."""
+        ntrials, width = series.shape
+        nv = int(np.prod(lead_shape))
+        guard = 0 if fill is None else PERIOD_GUARD
+        preset = np.float32(0.0 if fill is None else fill)
+        npeaks, nrows = nv * plan.levels * plan.nseg, nv * plan.nbins
+        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
+                 np.full((nrows if want_power or fill is not None else 0) + guard, preset, np.float32),
+                 np.full((nrows if want_white or fill is not None else 0) + guard, preset, np.float32)]
+        bufs = [self.upload(series)] + [self.upload(h) if h.size else None for h in hosts]
+        try:
+            call(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_power else None, bufs[4] if want_white else None)
+            self.sync()
+            best, at, power, white = [h if b is None else self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
+        finally:
+            plan.close()
+            for b in bufs:
+                if b is not None:
+                    b.free()
+        if fill is not None:
+            return best, at, power, white
+        shape = tuple(lead_shape) + (plan.levels, plan.nseg)
+        return (best.reshape(shape), at.reshape(shape), power.reshape(tuple(lead_shape) + (plan.nbins,)) if want_power else None,
+                white.reshape(tuple(lead_shape) + (plan.nbins,)) if want_white else None)
+
     # -- include/rtlws_pulse.h: host series in, (peaks, places, moments) out ----
     def pulse(self, series, widths, seg, nout=None, in_stride=None, want_moments=True, fill=None):
         """rtlws_pulse_run: series float32 [ntrials, nsamples] (with in_stride: [ntrials, in_stride], the padding as the
@@ -1924,13 +1972,7 @@ class Engine:
         (moments), so that a caller sees what the run left untouched; without want_moments the run gets a NULL d_mom and
         the preset moments buffer comes back as it was."""
         plan = PulsePlan(self, widths, seg)
-        series = np.ascontiguousarray(series, dtype=np.float32)
-        if in_stride is not None:
-            series = series.reshape(-1, int(in_stride))
-        assert series.ndim == 2, "the series are [ntrials, nsamples]"
-        samples = series.shape[1]
-        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
-            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        series, samples = self._series(series, in_stride, "nsamples")
         ntrials, width = series.shape
         if nout is None:
             nout = max(samples - (plan.samples_needed(1) - 1), 0)
@@ -1964,13 +2006,7 @@ class Engine:
         every element preset to fill (profiles) and to fill's bits (hits), so that a caller sees what the run left
         untouched; without want_hits the run gets a NULL d_hits and the preset hits buffer comes back as it was."""
         plan = FoldPlan(self, steps, phases, nbins, sub)
-        series = np.ascontiguousarray(series, dtype=np.float32)
-        if in_stride is not None:
-            series = series.reshape(-1, int(in_stride))
-        assert series.ndim == 2, "the series are [ntrials, nsamp]"
-        samples = series.shape[1]
-        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
-            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
+        series, samples = self._series(series, in_stride)
         ntrials, width = series.shape
         nsamp = samples if nsamp is None else int(nsamp)
         assert samples >= nsamp, "fewer samples than nsamp"
@@ -2002,123 +2038,38 @@ class Engine:
         what the run left untouched; without want_rows the run gets NULL rows and the preset buffers come back as they
         were."""
         plan = PeriodPlan(self, log2n, levels, norm, seg, klo)
-        series = np.ascontiguousarray(series, dtype=np.float32)
-        if in_stride is not None:
-            series = series.reshape(-1, int(in_stride))
-        assert series.ndim == 2, "the series are [ntrials, nsamp]"
-        samples = series.shape[1]
-        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
-            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
-        ntrials, width = series.shape
+        series, samples = self._series(series, in_stride)
         nsamp = samples if nsamp is None else int(nsamp)
         assert samples >= nsamp, "fewer samples than nsamp"
-        guard = 0 if fill is None else PERIOD_GUARD
-        preset = np.float32(0.0 if fill is None else fill)
-        npeaks, nrows = ntrials * plan.levels * plan.nseg, ntrials * plan.nbins
-        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
-                 np.full(nrows + guard, preset, np.float32), np.full(nrows + guard, preset, np.float32)]
-        bufs = [self.upload(series)] + [self.upload(h) for h in hosts]
-        try:
-            plan.run(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_rows else None, bufs[4] if want_rows else None)
-            self.sync()
-            best, at, power, white = [self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
-        finally:
-            plan.close()
-            for b in bufs:
-                b.free()
-        if fill is not None:
-            return best, at, power, white
-        shape = (ntrials, plan.levels, plan.nseg)
-        return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, plan.nbins) if want_rows else None,
-                white.reshape(ntrials, plan.nbins) if want_rows else None)
+        return self._search(plan, plan.run, series, nsamp, (series.shape[0],), want_rows, want_rows, fill)
 
     # -- include/rtlws_periodlong.h: host series in, (best, at, power, white) out ----
     def periodlong(self, series, log2n, levels, norm, seg, klo, nsamp=None, in_stride=None, want_rows=True, fill=None, max_trials=None,
                    want_power=None, want_white=None):
         """rtlws_periodlong_run with Engine.period's arguments and results.  max_trials: what the plan is opened for (None:
         the trials given); want_power / want_white: one optional row alone (None: want_rows)."""
-        series = np.ascontiguousarray(series, dtype=np.float32)
-        if in_stride is not None:
-            series = series.reshape(-1, int(in_stride))
-        assert series.ndim == 2, "the series are [ntrials, nsamp]"
-        samples = series.shape[1]
-        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
-            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
-        ntrials, width = series.shape
+        series, samples = self._series(series, in_stride)
+        ntrials = series.shape[0]
         plan = PeriodLongPlan(self, log2n, levels, norm, seg, klo, ntrials if max_trials is None else max_trials)
         nsamp = samples if nsamp is None else int(nsamp)
         assert samples >= nsamp, "fewer samples than nsamp"
-        want_power = want_rows if want_power is None else want_power
-        want_white = want_rows if want_white is None else want_white
-        guard = 0 if fill is None else PERIOD_GUARD
-        preset = np.float32(0.0 if fill is None else fill)
-        npeaks, nrows = ntrials * plan.levels * plan.nseg, ntrials * plan.nbins
-        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
-                 np.full((nrows if want_power or fill is not None else 0) + guard, preset, np.float32),
-                 np.full((nrows if want_white or fill is not None else 0) + guard, preset, np.float32)]
-        bufs = [self.upload(series)] + [self.upload(h) if h.size else None for h in hosts]
-        try:
-            plan.run(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_power else None, bufs[4] if want_white else None)
-            self.sync()
-            best, at, power, white = [h if b is None else self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
-        finally:
-            plan.close()
-            for b in bufs:
-                if b is not None:
-                    b.free()
-        if fill is not None:
-            return best, at, power, white
-        shape = (ntrials, plan.levels, plan.nseg)
-        return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, plan.nbins) if want_power else None,
-                white.reshape(ntrials, plan.nbins) if want_white else None)
+        return self._search(plan, plan.run, series, nsamp, (ntrials,), want_rows if want_power is None else want_power,
+                            want_rows if want_white is None else want_white, fill)
 
     # -- include/rtlws_accel.h: host series in, (best, at, power, white) out with a leading [ntrials, naccel] ----
-    def _accel_series(self, series, nsamp, in_stride):
-        series = np.ascontiguousarray(series, dtype=np.float32)
-        if in_stride is not None:
-            series = series.reshape(-1, int(in_stride))
-        assert series.ndim == 2, "the series are [ntrials, nsamp]"
-        samples = series.shape[1]
-        if in_stride is None and samples % 4:                 # the library's stride is a multiple of 4: zeros behind the samples
-            series = np.concatenate([series, np.zeros((series.shape[0], -samples % 4), np.float32)], axis=1)
-        nsamp = samples if nsamp is None else int(nsamp)
-        assert samples >= nsamp, "fewer samples than nsamp"
-        return series, nsamp
-
     def accel_search(self, series, log2n, levels, norm, seg, klo, coefs, nsamp=None, in_stride=None, want_rows=True, fill=None,
                      max_trials=None, want_power=None, want_white=None):
         """rtlws_accel_search with Engine.periodlong's arguments and, over the ntrials * naccel virtual trials, its
         results: (float32 [ntrials, naccel, levels, nseg] the peaks, int32 of that shape their bins, float32 [ntrials,
         naccel, M] the power spectra and the whitened ones, or None).  max_trials counts virtual trials (None: all of
         them).  With `fill` the four come back as the whole flat buffers, PERIOD_GUARD elements longer than the outputs."""
-        series, nsamp = self._accel_series(series, nsamp, in_stride)
-        ntrials, width = series.shape
-        naccel = np.asarray(coefs).size
-        nv = ntrials * naccel
-        plan = AccelPlan(self, log2n, levels, norm, seg, klo, coefs, nv if max_trials is None else max_trials)
-        want_power = want_rows if want_power is None else want_power
-        want_white = want_rows if want_white is None else want_white
-        guard = 0 if fill is None else PERIOD_GUARD
-        preset = np.float32(0.0 if fill is None else fill)
-        npeaks, nrows = nv * plan.levels * plan.nseg, nv * plan.nbins
-        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
-                 np.full((nrows if want_power or fill is not None else 0) + guard, preset, np.float32),
-                 np.full((nrows if want_white or fill is not None else 0) + guard, preset, np.float32)]
-        bufs = [self.upload(series)] + [self.upload(h) if h.size else None for h in hosts]
-        try:
-            plan.search(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_power else None, bufs[4] if want_white else None)
-            self.sync()
-            best, at, power, white = [h if b is None else self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
-        finally:
-            plan.close()
-            for b in bufs:
-                if b is not None:
-                    b.free()
-        if fill is not None:
-            return best, at, power, white
-        shape = (ntrials, naccel, plan.levels, plan.nseg)
-        return (best.reshape(shape), at.reshape(shape), power.reshape(ntrials, naccel, plan.nbins) if want_power else None,
-                white.reshape(ntrials, naccel, plan.nbins) if want_white else None)
+        series, samples = self._series(series, in_stride)
+        nsamp = samples if nsamp is None else int(nsamp)
+        assert samples >= nsamp, "fewer samples than nsamp"
+        ntrials, naccel = series.shape[0], np.asarray(coefs).size
+        plan = AccelPlan(self, log2n, levels, norm, seg, klo, coefs, ntrials * naccel if max_trials is None else max_trials)
+        return self._search(plan, plan.search, series, nsamp, (ntrials, naccel), want_rows if want_power is None else want_power,
+                            want_rows if want_white is None else want_white, fill)
 
     def accel_resample(self, series, log2n, coefs, a_first=0, a_count=None, nsamp=None, in_stride=None, out_stride=None, fill=None):
         """rtlws_accel_resample: series float32 [ntrials, nsamp] (with in_stride: [ntrials, in_stride], the padding as the
@@ -2126,7 +2077,9 @@ class Engine:
         accelerations a_first .. a_first + a_count - 1 (a_count None: the rest of the table).  out_stride None: nsamp
         rounded up to a multiple of 4.  With `fill` (a float32) the whole flat buffer comes back, [ntrials * a_count *
         out_stride + PERIOD_GUARD] elements preset to fill, so that a caller sees what the run left untouched."""
-        series, nsamp = self._accel_series(series, nsamp, in_stride)
+        series, samples = self._series(series, in_stride)
+        nsamp = samples if nsamp is None else int(nsamp)
+        assert samples >= nsamp, "fewer samples than nsamp"
         ntrials, width = series.shape
         naccel = np.asarray(coefs).size
         a_count = naccel - int(a_first) if a_count is None else int(a_count)

@@ -23,24 +23,18 @@ import dedisp_ref
 import fold_ref
 import period_ref
 import periodlong_ref
+from period_family import FILL, FILL_BITS, same_bits
+from period_family import noise as _noise, padded as _padded
 
 pytestmark = pytest.mark.gpu
 
-FILL = np.float32(-12345.678)
-FILL_BITS = FILL.view(np.uint32)
 TOP = 1 << 40
 N16 = 1 << 16
 
 
 def _same_bits(got, want, what=None):
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
-    bad = got.reshape(-1).view(np.uint32) != want.reshape(-1).view(np.uint32)
-    assert not bad.any(), (what, int(bad.sum()), np.flatnonzero(bad)[:5], got.reshape(-1)[bad][:5], want.reshape(-1)[bad][:5])
-
-
-def _noise(ntrials, nsamp, seed, mean=10.0):
-    rng = np.random.default_rng(seed)
-    return (mean + rng.standard_normal((ntrials, nsamp), dtype=np.float32)).astype(np.float32)
+    """device against device: a NaN's bits count too"""
+    same_bits(got, want, what, nan_by_place=False)
 
 
 def _seeded(seed, count):
@@ -49,13 +43,6 @@ def _seeded(seed, count):
 
 def _ceil4(n):
     return (n + 3) // 4 * 4
-
-
-def _padded(x, nsamp, wide):
-    stride = _ceil4(nsamp) + (12 if wide else 0)
-    padded = np.full((x.shape[0], stride), np.nan, np.float32)
-    padded[:, :nsamp] = x[:, :nsamp]
-    return padded, stride
 
 
 def _resample(built, engine, x, log2n, coefs, nsamp, wide_in=False, wide_out=False, a_first=0, a_count=None, name=None):

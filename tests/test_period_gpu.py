@@ -19,44 +19,33 @@ import dedisp_ref
 import fold_ref
 import period_ref
 import pulse_ref
+from period_family import FILL, check_bare, check_behind, check_stage1, noise, padded, unpack
+from period_family import same_bits as _same_bits
 from test_fold_gpu import CHAIN_NSAMP, CHAIN_TRIAL, P0, periodic_capture
 
 pytestmark = pytest.mark.gpu
 
-FILL = np.float32(-12345.678)
 WORST = {}
 
 
-def _same_bits(got, want, what=None):
-    """bit for bit on uint32 views, NaN by place (the default NaN of the host's division and the device's may differ)"""
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
-    nan = np.isnan(want) if got.dtype.kind == "f" else np.zeros(want.shape, bool)
-    gnan = np.isnan(got) if got.dtype.kind == "f" else nan
-    bad = (gnan != nan) | (~nan & (got.view(np.uint32) != want.view(np.uint32)))
-    assert not bad.any(), (what, np.argwhere(bad)[:5], got[bad][:5], want[bad][:5])
-
-
 def _noise(ntrials, nsamp, seed, mean=10.0):
-    rng = np.random.default_rng(seed)
-    return (mean + rng.standard_normal((ntrials, nsamp))).astype(np.float32)
+    return noise(ntrials, nsamp, seed, mean, draw=np.float64)
+
+
+def _reference(log2n):
+    """the f64 spectrum of a trial's samples; the premises of the bound hold for them"""
+    def reference(xs, name):
+        ref = period_ref.power(xs, log2n)
+        if xs.size > 1:
+            x64 = xs.astype(np.float64)
+            assert period_ref.nyquist_power(xs, log2n) <= ref.sum() and (x64.std() == 0 or abs(x64.mean()) <= 256 * x64.std()), name
+        return ref
+    return reference
 
 
 def _check_stage1(power, x, log2n, nsamp, name, finite=None):
     """per trial sum |P^ - P| <= c sum P against the f64 spectrum; the premises of the bound hold for x"""
-    c, worst = period_ref.bound(log2n), 0.0
-    for t in range(x.shape[0]):
-        if finite is not None and not finite[t]:
-            continue
-        ref = period_ref.power(x[t, :nsamp], log2n)
-        if nsamp > 1:
-            xs = x[t, :nsamp].astype(np.float64)
-            assert period_ref.nyquist_power(x[t, :nsamp], log2n) <= ref.sum() and (xs.std() == 0 or abs(xs.mean()) <= 256 * xs.std()), name
-        err = np.abs(power[t].astype(np.float64) - ref).sum()
-        assert err <= c * ref.sum(), (name, t, err, c * ref.sum())
-        if ref.sum() > 0:
-            worst = max(worst, err / (c * ref.sum()))
-    WORST[log2n] = max(WORST.get(log2n, 0.0), worst)
-    return worst
+    return check_stage1(power, x, nsamp, period_ref.bound(log2n), _reference(log2n), WORST, log2n, name, finite)
 
 
 def _run(built, engine, x, log2n, levels, norm, seg, klo, nsamp=None, wide=False, name=None, stage1=True, finite=None):
@@ -66,29 +55,14 @@ def _run(built, engine, x, log2n, levels, norm, seg, klo, nsamp=None, wide=False
     ntrials = x.shape[0]
     nsamp = x.shape[1] if nsamp is None else nsamp
     m = 1 << (log2n - 1)
-    nseg = m // seg
-    stride = (nsamp + 3) // 4 * 4 + (12 if wide else 0)
-    padded = np.full((ntrials, stride), np.nan, np.float32)
-    padded[:, :nsamp] = x[:, :nsamp]
-    outs = engine.period(padded, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, fill=FILL)
-    bare = engine.period(padded, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, want_rows=False, fill=FILL)
-    n1, n2, guard = ntrials * levels * nseg, ntrials * m, built.PERIOD_GUARD
-    fill_bits = FILL.view(np.uint32)
-    for o, n in zip(outs, (n1, n1, n2, n2)):
-        assert o.shape == (n + guard,) and np.all(o[n:].view(np.uint32) == fill_bits), name
-    assert np.all(bare[2].view(np.uint32) == fill_bits) and np.all(bare[3].view(np.uint32) == fill_bits), name
-    best, at = outs[0][:n1].reshape(ntrials, levels, nseg), outs[1][:n1].reshape(ntrials, levels, nseg)
-    power, white = outs[2][:n2].reshape(ntrials, m), outs[3][:n2].reshape(ntrials, m)
-    assert at.dtype == np.int32
-    _same_bits(bare[0][:n1].reshape(best.shape), best, (name, "best without rows"))
-    assert np.array_equal(bare[1][:n1].reshape(at.shape), at), (name, "at without rows")
+    rows, stride = padded(x, nsamp, wide)
+    outs = engine.period(rows, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, fill=FILL)
+    bare = engine.period(rows, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, want_rows=False, fill=FILL)
+    best, at, power, white = unpack(outs, ntrials, levels, m // seg, m, built.PERIOD_GUARD, name)
+    check_bare(bare, best, at, name)
     if stage1:
         _check_stage1(power, x, log2n, nsamp, name, finite)
-    want_white = period_ref.whiten(power, norm)
-    _same_bits(white, want_white, (name, "white"))
-    want_best, want_at = period_ref.peaks(period_ref.sums(white, levels), seg, klo)
-    _same_bits(best, want_best, (name, "best"))
-    assert np.array_equal(at, want_at), (name, "at", np.argwhere(at != want_at)[:5])
+    check_behind(power, white, best, at, levels, norm, seg, klo, name)
     return best, at, power, white
 
 

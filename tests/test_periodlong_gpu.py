@@ -21,51 +21,28 @@ import dedisp_ref
 import fold_ref
 import period_ref
 import periodlong_ref
+from period_family import FILL, check_bare, check_stage1, padded, unpack
+from period_family import check_behind as _check_behind, noise as _noise, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
-FILL = np.float32(-12345.678)
 WORST = {}
 LOG2NS = range(16, 23)
 
 
-def _same_bits(got, want, what=None):
-    """bit for bit on uint32 views, NaN by place (the default NaN of the host's division and the device's may differ)"""
-    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape)
-    nan = np.isnan(want) if got.dtype.kind == "f" else np.zeros(want.shape, bool)
-    gnan = np.isnan(got) if got.dtype.kind == "f" else nan
-    bad = (gnan != nan) | (~nan & (got.view(np.uint32) != want.view(np.uint32)))
-    assert not bad.any(), (what, np.argwhere(bad)[:5], got[bad][:5], want[bad][:5])
-
-
-def _noise(ntrials, nsamp, seed, mean=10.0):
-    rng = np.random.default_rng(seed)
-    return (mean + rng.standard_normal((ntrials, nsamp), dtype=np.float32)).astype(np.float32)
+def _reference(log2n):
+    """the f64 spectrum of a trial's samples; both premises of the bound hold for them"""
+    def reference(xs, name):
+        ref, nyquist_small, mean_small = periodlong_ref.power_and_premises(xs, log2n)
+        if xs.size > 1 and ref.sum() > 0:
+            assert nyquist_small and mean_small, name
+        return ref
+    return reference
 
 
 def _check_stage1(power, x, log2n, nsamp, name, finite=None):
     """per trial sum |P^ - P| <= c sum P against the f64 spectrum; both premises of the bound hold for x"""
-    c, worst = periodlong_ref.bound(log2n), 0.0
-    for t in range(x.shape[0]):
-        if finite is not None and not finite[t]:
-            continue
-        ref, nyquist_small, mean_small = periodlong_ref.power_and_premises(x[t, :nsamp], log2n)
-        if nsamp > 1 and ref.sum() > 0:
-            assert nyquist_small and mean_small, name
-        err = np.abs(power[t].astype(np.float64) - ref).sum()
-        assert err <= c * ref.sum(), (name, t, err, c * ref.sum())
-        if ref.sum() > 0:
-            worst = max(worst, err / (c * ref.sum()))
-    WORST[log2n] = max(WORST.get(log2n, 0.0), worst)
-    return worst
-
-
-def _check_behind(power, white, best, at, levels, norm, seg, klo, name):
-    """stages 2 - 4 from the device's own rows"""
-    _same_bits(white, period_ref.whiten(power, norm), (name, "white"))
-    want_best, want_at = period_ref.peaks(period_ref.sums(white, levels), seg, klo)
-    _same_bits(best, want_best, (name, "best"))
-    assert np.array_equal(at, want_at), (name, "at", np.argwhere(at != want_at)[:5])
+    return check_stage1(power, x, nsamp, periodlong_ref.bound(log2n), _reference(log2n), WORST, log2n, name, finite)
 
 
 def _run(built, engine, x, log2n, levels, norm, seg, klo, nsamp=None, wide=False, name=None, stage1=True, finite=None, bare=True, max_trials=None):
@@ -76,23 +53,12 @@ def _run(built, engine, x, log2n, levels, norm, seg, klo, nsamp=None, wide=False
     ntrials = x.shape[0]
     nsamp = x.shape[1] if nsamp is None else nsamp
     m = 1 << (log2n - 1)
-    nseg = m // seg
-    stride = (nsamp + 3) // 4 * 4 + (12 if wide else 0)
-    padded = np.full((ntrials, stride), np.nan, np.float32)
-    padded[:, :nsamp] = x[:, :nsamp]
-    outs = engine.periodlong(padded, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, fill=FILL, max_trials=max_trials)
-    n1, n2, guard = ntrials * levels * nseg, ntrials * m, built.PERIOD_GUARD
-    fill_bits = FILL.view(np.uint32)
-    for o, n in zip(outs, (n1, n1, n2, n2)):
-        assert o.shape == (n + guard,) and np.all(o[n:].view(np.uint32) == fill_bits), name
-    best, at = outs[0][:n1].reshape(ntrials, levels, nseg), outs[1][:n1].reshape(ntrials, levels, nseg)
-    power, white = outs[2][:n2].reshape(ntrials, m), outs[3][:n2].reshape(ntrials, m)
-    assert at.dtype == np.int32
+    rows, stride = padded(x, nsamp, wide)
+    outs = engine.periodlong(rows, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, fill=FILL, max_trials=max_trials)
+    best, at, power, white = unpack(outs, ntrials, levels, m // seg, m, built.PERIOD_GUARD, name)
     if bare:
-        none = engine.periodlong(padded, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, want_rows=False, fill=FILL, max_trials=max_trials)
-        assert np.all(none[2].view(np.uint32) == fill_bits) and np.all(none[3].view(np.uint32) == fill_bits), name
-        _same_bits(none[0][:n1].reshape(best.shape), best, (name, "best without rows"))
-        assert np.array_equal(none[1][:n1].reshape(at.shape), at), (name, "at without rows")
+        none = engine.periodlong(rows, log2n, levels, norm, seg, klo, nsamp=nsamp, in_stride=stride, want_rows=False, fill=FILL, max_trials=max_trials)
+        check_bare(none, best, at, name)
     if stage1:
         _check_stage1(power, x, log2n, nsamp, name, finite)
     _check_behind(power, white, best, at, levels, norm, seg, klo, name)
