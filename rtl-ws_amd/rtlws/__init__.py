@@ -70,6 +70,7 @@ FLAG_ROWS_F32 = 1          # rtlws_spectra_batch_f64: f64 arithmetic, f32 rows
 FLAG_F64 = 2               # rtlws_stream.h: this stream computes in f64
 
 _INPUTS = {"cu8": IN_CU8, "cs32": IN_CS32, "rf32": IN_RF32}
+_SAMPLE_BYTES = {"cu8": 2, "cs32": 8, "rf32": 4}
 _WINDOWS = {"rect": WIN_RECT, "hann": WIN_HANN, None: WIN_RECT}
 _OUTPUTS = {"power_sum": OUT_POWER_SUM, "mean_db": OUT_MEAN_DB, "payload_u8": OUT_PAYLOAD_U8}
 
@@ -100,87 +101,8 @@ class CicDelayLine(C.Structure):
     _fields_ = [("integrator_prev_out", CmplxS32), ("comb_prev_in", CmplxS32)]
 
 
-# every symbol include/*.h declares, by library (tests check the exports)
-HIP_SYMBOLS = [
-    "rtlws_device_count", "rtlws_device_pci_bus_id", "rtlws_engine_create", "rtlws_engine_destroy", "rtlws_engine_device",
-    "rtlws_engine_stream",
-    "rtlws_engine_prepare", "rtlws_engine_prepare_f64", "rtlws_engine_set_option", "rtlws_engine_get_option",
-    "rtlws_last_error", "rtlws_dev_alloc", "rtlws_dev_free", "rtlws_pinned_alloc",
-    "rtlws_pinned_free", "rtlws_copy_h2d", "rtlws_copy_d2h", "rtlws_memset_dev",
-    "rtlws_stream_sync", "rtlws_event_create", "rtlws_event_destroy", "rtlws_event_record",
-    "rtlws_event_elapsed_ms", "rtlws_event_sync", "rtlws_spectra_batch", "rtlws_spectra_kernel_kind",
-    "rtlws_cic_block_sums", "rtlws_halfband", "rtlws_spectra_grid", "rtlws_payload_from_sums",
-    "rtlws_fm_demod", "rtlws_copy_d2d", "rtlws_spectra_batch_f64", "rtlws_payload_from_sums_f64",
-    "rtlws_welch_accumulate_f64", "rtlws_welch_finish_f64",
-    "rtlws_queue_create", "rtlws_queue_destroy", "rtlws_queue_wait_event", "rtlws_event_create_blocking",
-    "rtlws_clock_stamp",
-]
-LONG_SYMBOLS = ["rtlws_long_supported", "rtlws_long_open", "rtlws_long_workspace_bytes", "rtlws_long_run",
-                "rtlws_long_close", "rtlws_long_last_error"]
-ANYLEN_SYMBOLS = ["rtlws_anylen_supported", "rtlws_anylen_open", "rtlws_anylen_conv_log2", "rtlws_anylen_workspace_bytes",
-                  "rtlws_anylen_run", "rtlws_anylen_close", "rtlws_anylen_last_error"]
-FM_SYMBOLS = ["rtlws_fm_supported", "rtlws_fm_grid", "rtlws_fm_prepare", "rtlws_fm_audio_blocks",
-              "rtlws_fm_audio_blocks_cu8", "rtlws_fm_last_error"]
-FM_STATE_FLOATS = 21       # rtlws_fm.h: phase carry, delay line 1, delay line 2
-DDC_SYMBOLS = ["rtlws_ddc_supported", "rtlws_ddc_table", "rtlws_ddc_tuning_word", "rtlws_ddc_open", "rtlws_ddc_grid",
-               "rtlws_ddc_run", "rtlws_ddc_close", "rtlws_ddc_last_error"]
-DDC_LOG2_PERIOD = 16       # rtlws_ddc.h: the phase period P = 2^16
-DDC_MAX_CHANNELS = 32
-DDCFIR_SYMBOLS = ["rtlws_ddcfir_supported", "rtlws_ddcfir_samples_needed", "rtlws_ddcfir_grid", "rtlws_ddcfir_design",
-                  "rtlws_ddcfir_bound", "rtlws_ddcfir_open", "rtlws_ddcfir_run", "rtlws_ddcfir_close", "rtlws_ddcfir_last_error"]
-DDCFIR_MAX_TAPS, DDCFIR_MAX_TAP, DDCFIR_MAX_SHIFT = 256, 32639, 30       # rtlws_ddcfir.h
-FMBANK_SYMBOLS = ["rtlws_fmbank_supported", "rtlws_fmbank_grid", "rtlws_fmbank_open", "rtlws_fmbank_run",
-                  "rtlws_fmbank_close", "rtlws_fmbank_last_error"]
-FMFIR_SYMBOLS = ["rtlws_fmfir_supported", "rtlws_fmfir_samples_needed", "rtlws_fmfir_grid", "rtlws_fmfir_open",
-                 "rtlws_fmfir_run", "rtlws_fmfir_close", "rtlws_fmfir_last_error"]
-FMFIR_MAX_CHANNELS = 32                                                   # rtlws_fmfir.h
-FMBANK_MAX_CHANNELS = 32
-PFB_SYMBOLS = ["rtlws_pfb_supported", "rtlws_pfb_design", "rtlws_pfb_twiddles", "rtlws_pfb_samples_needed", "rtlws_pfb_grid",
-               "rtlws_pfb_open", "rtlws_pfb_run", "rtlws_pfb_close", "rtlws_pfb_last_error"]
-PFB_CHANNEL_MAJOR, PFB_TIME_MAJOR = 0, 1       # rtlws_pfb.h: the output layouts
-_PFB_LAYOUTS = {"channel": PFB_CHANNEL_MAJOR, "time": PFB_TIME_MAJOR}
-PFBSPEC_SYMBOLS = ["rtlws_pfbspec_supported", "rtlws_pfbspec_samples_needed", "rtlws_pfbspec_grid", "rtlws_pfbspec_open",
-                   "rtlws_pfbspec_run", "rtlws_pfbspec_close", "rtlws_pfbspec_last_error"]
-PFBSPEC_MAX_K_AVG = 65536
-# rtlws_pfbspec.h's output kinds are enum rtlws_output's values
-_PFBSPEC_OUTPUTS = {"power": OUT_POWER_SUM, "db": OUT_MEAN_DB, "payload": OUT_PAYLOAD_U8}
-_PFBSPEC_OUTPUTS.update(_OUTPUTS)
-PFBXC_SYMBOLS = ["rtlws_pfbxc_supported", "rtlws_pfbxc_samples_needed", "rtlws_pfbxc_pair_index", "rtlws_pfbxc_grid",
-                 "rtlws_pfbxc_open", "rtlws_pfbxc_run", "rtlws_pfbxc_close", "rtlws_pfbxc_last_error"]
-PFBXC_MAX_K_AVG = 65536
-PFBXC_MIN_INPUTS, PFBXC_MAX_INPUTS = 2, 4
-PFBBF_SYMBOLS = ["rtlws_pfbbf_supported", "rtlws_pfbbf_samples_needed", "rtlws_pfbbf_grid", "rtlws_pfbbf_open",
-                 "rtlws_pfbbf_run", "rtlws_pfbbf_power", "rtlws_pfbbf_close", "rtlws_pfbbf_last_error"]
-PFBBF_MAX_K_AVG = 65536
-PFBBF_MIN_INPUTS, PFBBF_MAX_INPUTS = 1, 8
-PFBBF_MIN_BEAMS, PFBBF_MAX_BEAMS = 1, 4
-PFBSK_SYMBOLS = ["rtlws_pfbsk_supported", "rtlws_pfbsk_samples_needed", "rtlws_pfbsk_grid", "rtlws_pfbsk_power_scale",
-                 "rtlws_pfbsk_bounds", "rtlws_pfbsk_open", "rtlws_pfbsk_run", "rtlws_pfbsk_close", "rtlws_pfbsk_last_error"]
-PFBSK_MAX_K_AVG, PFBSK_MAX_NSUB = 65536, 65535
-DEDISP_SYMBOLS = ["rtlws_dedisp_supported", "rtlws_dedisp_delays", "rtlws_dedisp_geometry", "rtlws_dedisp_open",
-                  "rtlws_dedisp_rows_needed", "rtlws_dedisp_run", "rtlws_dedisp_close", "rtlws_dedisp_last_error"]
-DEDISP_MIN_NCHAN, DEDISP_MAX_NCHAN, DEDISP_MAX_TRIALS, DEDISP_MAX_DELAY = 4, 4096, 4096, 65535
-PULSE_SYMBOLS = ["rtlws_pulse_supported", "rtlws_pulse_geometry", "rtlws_pulse_open", "rtlws_pulse_samples_needed",
-                 "rtlws_pulse_segments", "rtlws_pulse_run", "rtlws_pulse_snr", "rtlws_pulse_close", "rtlws_pulse_last_error"]
-PULSE_MAX_WIDTHS, PULSE_MAX_WIDTH, PULSE_MIN_SEG, PULSE_MAX_SEG, PULSE_MAX_TRIALS, PULSE_MAX_NOUT = 16, 1024, 64, 1 << 20, 65536, 1 << 30
-PULSE_GUARD = 8            # Engine.pulse(fill=...): preset elements behind every output array
-FOLD_SYMBOLS = ["rtlws_fold_supported", "rtlws_fold_geometry", "rtlws_fold_open", "rtlws_fold_subints", "rtlws_fold_run",
-                "rtlws_fold_step", "rtlws_fold_phase_at", "rtlws_fold_chi2", "rtlws_fold_close", "rtlws_fold_last_error"]
-FOLD_MAX_PERIODS, FOLD_MIN_BINS, FOLD_MAX_BINS, FOLD_MIN_SUB, FOLD_MAX_SUB, FOLD_MAX_TRIALS, FOLD_MAX_NSAMP = 4096, 2, 256, 64, 1 << 24, 65536, 1 << 30
-FOLD_GUARD = 8             # Engine.fold(fill=...): preset elements behind both output arrays
-PERIOD_SYMBOLS = ["rtlws_period_supported", "rtlws_period_geometry", "rtlws_period_open", "rtlws_period_run", "rtlws_period_samples",
-                  "rtlws_period_lnq", "rtlws_period_close", "rtlws_period_last_error"]
-PERIOD_MIN_LOG2N, PERIOD_MAX_LOG2N, PERIOD_MAX_LEVELS, PERIOD_MIN_NORM, PERIOD_MIN_SEG, PERIOD_MAX_TRIALS = 10, 15, 5, 16, 64, 65536
-PERIOD_GUARD = 8           # Engine.period(fill=...): preset elements behind every output array
-PERIODLONG_SYMBOLS = ["rtlws_periodlong_supported", "rtlws_periodlong_geometry", "rtlws_periodlong_open", "rtlws_periodlong_workspace_bytes",
-                      "rtlws_periodlong_run", "rtlws_periodlong_samples", "rtlws_periodlong_close", "rtlws_periodlong_last_error"]
-PERIODLONG_MIN_LOG2N, PERIODLONG_MAX_LOG2N, PERIODLONG_MAX_LEVELS, PERIODLONG_MAX_TRIALS, PERIODLONG_STAGES = 16, 22, 5, 65536, 6
-PERIODLONG_MIN_NORM, PERIODLONG_MAX_NORM, PERIODLONG_MIN_SEG, PERIODLONG_MAX_SEG = 16, 16384, 64, 16384
-PERIODLONG_WORKSPACE_CAP = 1 << 30
-ACCEL_SYMBOLS = ["rtlws_accel_supported", "rtlws_accel_geometry", "rtlws_accel_open", "rtlws_accel_workspace_bytes", "rtlws_accel_search",
-                 "rtlws_accel_resample", "rtlws_accel_coef", "rtlws_accel_coef_from_shift", "rtlws_accel_shift", "rtlws_accel_close",
-                 "rtlws_accel_last_error"]
-ACCEL_MAX_NACCEL, ACCEL_MAX_COEF, ACCEL_MAX_VIRTUAL, ACCEL_STAGES = 1024, 1 << 40, 65536, 6
+# every symbol include/*.h declares, by library (tests check the exports).  A library with a prototype table below lists
+# its table's functions: X_SYMBOLS = list(_X_PROTOTYPES).
 AUDIO_SYMBOLS = ["audio_init", "audio_new_audio_available", "audio_get_audio_payload",
                  "audio_fm_demodulator", "audio_close"]
 STREAM_SYMBOLS = ["rtlws_stream_open", "rtlws_stream_open_q", "rtlws_stream_push", "rtlws_stream_flush",
@@ -211,8 +133,7 @@ SYNTH_SYMBOLS = ["rtl_init", "rtl_set_frequency", "rtl_set_sample_rate", "rtl_se
                  "signal_source_start", "signal_source_add_callback",
                  "signal_source_remove_callbacks", "signal_source_stop"]
 
-_hip = None
-_satellites = {}          # path -> the loaded satellite library (_satellite)
+_loaded = {}              # path -> a library with a prototype table, loaded (_load)
 _amd = None
 _cbb = None
 
@@ -234,70 +155,17 @@ def _need(path):
             "g.build()' or make -C rtl-ws_amd). There is no CPU fallback." % path)
 
 
-def hip_lib():
-    global _hip
-    if _hip is None:
-        _need(HIP_LIB)
-        L = C.CDLL(HIP_LIB, mode=C.RTLD_GLOBAL)
-        vp, i, l, sz = C.c_void_p, C.c_int, C.c_long, C.c_size_t
-        L.rtlws_device_count.restype = i
-        L.rtlws_engine_create.argtypes = [i]
-        L.rtlws_engine_create.restype = vp
-        L.rtlws_engine_destroy.argtypes = [vp]
-        L.rtlws_engine_device.argtypes = [vp]
-        L.rtlws_engine_stream.argtypes = [vp]
-        L.rtlws_engine_stream.restype = vp
-        L.rtlws_engine_prepare.argtypes = [vp, i]
-        L.rtlws_engine_prepare_f64.argtypes = [vp, i]
-        L.rtlws_engine_set_option.argtypes = [vp, C.c_char_p, i]
-        L.rtlws_engine_get_option.argtypes = [vp, C.c_char_p]
-        L.rtlws_last_error.restype = C.c_char_p
-        L.rtlws_dev_alloc.argtypes = [vp, sz]
-        L.rtlws_dev_alloc.restype = vp
-        L.rtlws_dev_free.argtypes = [vp, vp]
-        L.rtlws_pinned_alloc.argtypes = [sz]
-        L.rtlws_pinned_alloc.restype = vp
-        L.rtlws_pinned_free.argtypes = [vp]
-        L.rtlws_copy_h2d.argtypes = [vp, vp, vp, sz, vp]
-        L.rtlws_copy_d2h.argtypes = [vp, vp, vp, sz, vp]
-        L.rtlws_memset_dev.argtypes = [vp, vp, i, sz, vp]
-        L.rtlws_stream_sync.argtypes = [vp, vp]
-        L.rtlws_event_create.restype = vp
-        L.rtlws_event_create_blocking.restype = vp
-        L.rtlws_queue_create.argtypes = [vp]
-        L.rtlws_queue_create.restype = vp
-        L.rtlws_queue_destroy.argtypes = [vp, vp]
-        L.rtlws_queue_wait_event.argtypes = [vp, vp, vp]
-        L.rtlws_event_destroy.argtypes = [vp]
-        L.rtlws_event_record.argtypes = [vp, vp, vp]
-        L.rtlws_event_elapsed_ms.argtypes = [vp, vp]
-        L.rtlws_event_sync.argtypes = [vp]
-        L.rtlws_event_elapsed_ms.restype = C.c_float
-        L.rtlws_spectra_batch.argtypes = [vp, C.POINTER(SpectraDesc), vp, l, vp, vp]
-        L.rtlws_spectra_batch_f64.argtypes = [vp, C.POINTER(SpectraDesc), vp, l, vp, vp]
-        L.rtlws_payload_from_sums_f64.argtypes = [vp, vp, i, i, i, vp, vp]
-        L.rtlws_welch_accumulate_f64.argtypes = [vp, vp, vp, i, l, vp, vp]
-        L.rtlws_welch_finish_f64.argtypes = [vp, vp, i, l, vp, vp]
-        L.rtlws_spectra_kernel_kind.argtypes = [C.POINTER(SpectraDesc)]
-        L.rtlws_cic_block_sums.argtypes = [vp, i, vp, l, vp, vp]
-        L.rtlws_halfband.argtypes = [vp, vp, vp, l, vp]
-        L.rtlws_payload_from_sums.argtypes = [vp, vp, i, i, i, vp, vp]
-        L.rtlws_fm_demod.argtypes = [vp, vp, l, vp, vp, vp, vp]
-        L.rtlws_copy_d2d.argtypes = [vp, vp, vp, sz, vp]
-        L.rtlws_clock_stamp.argtypes = [vp, vp, C.c_int, vp]
-        L.rtlws_spectra_grid.argtypes = [vp, C.POINTER(SpectraDesc), l, C.POINTER(i),
-                                         C.POINTER(i), C.POINTER(i)]
-        _hip = L
-    return _hip
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
 
 
-def _satellite(path, prototypes):
-    """A library of its own on top of librtlws_hip.so's engine (include/rtlws_<name>.h), loaded once: librtlws_hip.so
-    first, the build where it is missing, then its prototypes from a table name -> argtypes (an int comes back) or
-    (argtypes, restype)."""
-    L = _satellites.get(path)
+# ---- the libraries with a prototype table: one loader, one out-parameter call ----
+
+def _load(path, prototypes):
+    """The library at path, loaded once (RTLD_GLOBAL; the build first where it is missing), with its prototypes from a
+    table name -> argtypes (an int comes back) or (argtypes, restype)."""
+    L = _loaded.get(path)
     if L is None:
-        hip_lib()
         _need(path)
         L = C.CDLL(path, mode=C.RTLD_GLOBAL)
         for name, proto in prototypes.items():
@@ -306,92 +174,249 @@ def _satellite(path, prototypes):
                 f.argtypes, f.restype = proto
             else:
                 f.argtypes = proto
-        _satellites[path] = L
+        _loaded[path] = L
     return L
 
 
-_i, _l, _vp, _ip, _str = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int), C.c_char_p
-_desc, _vpp = C.POINTER(SpectraDesc), C.POINTER(C.c_void_p)
+def _satellite(path, prototypes):
+    """A library of its own on top of librtlws_hip.so's engine (include/rtlws_<name>.h): librtlws_hip.so first."""
+    hip_lib()
+    return _load(path, prototypes)
 
+
+def _library(name, prototypes):
+    """(x_lib, x_last_error) of the satellite library `name`: its loader over X_LIB and its table, and the reader of
+    rtlws_<name>_last_error."""
+    path = globals()[name.upper() + "_LIB"]
+
+    def lib():
+        return _satellite(path, prototypes)
+
+    def last_error():
+        return getattr(lib(), "rtlws_%s_last_error" % name)().decode()
+
+    lib.__name__ = lib.__qualname__ = name + "_lib"
+    lib.__doc__ = "librtlws_%s.so (include/rtlws_%s.h); it needs librtlws_hip.so's engine." % (name, name)
+    last_error.__name__ = last_error.__qualname__ = name + "_last_error"
+    return lib, last_error
+
+
+def _outs(fn, args, types):
+    """fn(*args, *outs) -> (rc, *values): behind args one fresh zero-initialised object of each of `types` by reference
+    (a ctypes scalar type, whose value comes back; or an array type, passed as it is, which comes back as a tuple)."""
+    outs = [t() for t in types]
+    rc = fn(*args, *[o if isinstance(o, C.Array) else C.byref(o) for o in outs])
+    return (rc,) + tuple(tuple(o) if isinstance(o, C.Array) else o.value for o in outs)
+
+
+_i, _l, _vp, _ip, _str, _sz = C.c_int, C.c_long, C.c_void_p, C.POINTER(C.c_int), C.c_char_p, C.c_size_t
+_desc, _vpp = C.POINTER(SpectraDesc), C.POINTER(C.c_void_p)
+_GRID = (C.c_int,) * 4    # what most rtlws_*_grid give: workgroups, threads, LDS bytes and the library's own fourth
+
+# ---- include/rtlws_hip.h ----
+_HIP_PROTOTYPES = {
+    "rtlws_device_count": [], "rtlws_device_pci_bus_id": [_i, _str, _i], "rtlws_engine_create": ([_i], _vp),
+    "rtlws_engine_destroy": [_vp], "rtlws_engine_device": [_vp], "rtlws_engine_stream": ([_vp], _vp),
+    "rtlws_engine_prepare": [_vp, _i], "rtlws_engine_prepare_f64": [_vp, _i], "rtlws_engine_set_option": [_vp, _str, _i],
+    "rtlws_engine_get_option": [_vp, _str], "rtlws_last_error": ([], _str), "rtlws_dev_alloc": ([_vp, _sz], _vp),
+    "rtlws_dev_free": [_vp, _vp], "rtlws_pinned_alloc": ([_sz], _vp), "rtlws_pinned_free": [_vp],
+    "rtlws_copy_h2d": [_vp, _vp, _vp, _sz, _vp], "rtlws_copy_d2h": [_vp, _vp, _vp, _sz, _vp],
+    "rtlws_copy_d2d": [_vp, _vp, _vp, _sz, _vp], "rtlws_memset_dev": [_vp, _vp, _i, _sz, _vp], "rtlws_stream_sync": [_vp, _vp],
+    "rtlws_event_create": ([], _vp), "rtlws_event_create_blocking": ([], _vp), "rtlws_event_destroy": [_vp],
+    "rtlws_event_record": [_vp, _vp, _vp], "rtlws_event_elapsed_ms": ([_vp, _vp], C.c_float), "rtlws_event_sync": [_vp],
+    "rtlws_queue_create": ([_vp], _vp), "rtlws_queue_destroy": [_vp, _vp], "rtlws_queue_wait_event": [_vp, _vp, _vp],
+    "rtlws_spectra_batch": [_vp, _desc, _vp, _l, _vp, _vp], "rtlws_spectra_batch_f64": [_vp, _desc, _vp, _l, _vp, _vp],
+    "rtlws_spectra_kernel_kind": [_desc], "rtlws_spectra_grid": [_vp, _desc, _l, _ip, _ip, _ip],
+    "rtlws_payload_from_sums": [_vp, _vp, _i, _i, _i, _vp, _vp], "rtlws_payload_from_sums_f64": [_vp, _vp, _i, _i, _i, _vp, _vp],
+    "rtlws_welch_accumulate_f64": [_vp, _vp, _vp, _i, _l, _vp, _vp], "rtlws_welch_finish_f64": [_vp, _vp, _i, _l, _vp, _vp],
+    "rtlws_cic_block_sums": [_vp, _i, _vp, _l, _vp, _vp], "rtlws_halfband": [_vp, _vp, _vp, _l, _vp],
+    "rtlws_fm_demod": [_vp, _vp, _l, _vp, _vp, _vp, _vp], "rtlws_clock_stamp": [_vp, _vp, _i, _vp]}
+HIP_SYMBOLS = list(_HIP_PROTOTYPES)
+
+
+def hip_lib():
+    return _load(HIP_LIB, _HIP_PROTOTYPES)
+
+
+def last_error():
+    return hip_lib().rtlws_last_error().decode()
+
+
+def device_count():
+    return hip_lib().rtlws_device_count()
+
+
+# ---- include/rtlws_long.h ----
 _LONG_PROTOTYPES = {
     "rtlws_long_supported": [_desc], "rtlws_long_open": ([_vp, _desc, _l], _vp),
-    "rtlws_long_workspace_bytes": ([_vp], C.c_size_t), "rtlws_long_run": [_vp, _vp, _l, _vp, _vp],
+    "rtlws_long_workspace_bytes": ([_vp], _sz), "rtlws_long_run": [_vp, _vp, _l, _vp, _vp],
     "rtlws_long_close": ([_vp], None), "rtlws_long_last_error": ([], _str)}
+LONG_SYMBOLS = list(_LONG_PROTOTYPES)
+long_lib, long_last_error = _library("long", _LONG_PROTOTYPES)
 
 
-def long_lib():
-    """librtlws_long.so (include/rtlws_long.h); it needs librtlws_hip.so's engine."""
-    return _satellite(LONG_LIB, _LONG_PROTOTYPES)
+def long_supported(desc):
+    return long_lib().rtlws_long_supported(C.byref(desc))
 
 
+# ---- include/rtlws_anylen.h ----
 _ANYLEN_PROTOTYPES = {
     "rtlws_anylen_supported": [_desc], "rtlws_anylen_conv_log2": [_desc], "rtlws_anylen_open": ([_vp, _desc, _l], _vp),
-    "rtlws_anylen_workspace_bytes": ([_vp], C.c_size_t), "rtlws_anylen_run": [_vp, _vp, _l, _vp, _vp],
+    "rtlws_anylen_workspace_bytes": ([_vp], _sz), "rtlws_anylen_run": [_vp, _vp, _l, _vp, _vp],
     "rtlws_anylen_close": ([_vp], None), "rtlws_anylen_last_error": ([], _str)}
+ANYLEN_SYMBOLS = list(_ANYLEN_PROTOTYPES)
+anylen_lib, anylen_last_error = _library("anylen", _ANYLEN_PROTOTYPES)
 
 
-def anylen_lib():
-    """librtlws_anylen.so (include/rtlws_anylen.h); it needs librtlws_hip.so's engine."""
-    return _satellite(ANYLEN_LIB, _ANYLEN_PROTOTYPES)
+def anylen_supported(desc):
+    return anylen_lib().rtlws_anylen_supported(C.byref(desc))
 
 
+def anylen_conv_log2(desc):
+    """m of the convolution length 2^m the descriptor runs at, -1 if it is not served."""
+    return anylen_lib().rtlws_anylen_conv_log2(C.byref(desc))
+
+
+# ---- include/rtlws_fm.h ----
+FM_STATE_FLOATS = 21       # rtlws_fm.h: phase carry, delay line 1, delay line 2
 _FM_PROTOTYPES = {
     "rtlws_fm_supported": [_i, _l, _i], "rtlws_fm_grid": [_i, _l, _i, _ip, _ip, _ip, _ip], "rtlws_fm_prepare": [_vp],
     "rtlws_fm_audio_blocks": [_vp, _vp, _i, _l, _vp, _vp, _i, _vp, _vp],
     "rtlws_fm_audio_blocks_cu8": [_vp, _i, _vp, _i, _l, _vp, _vp, _i, _vp, _vp, _vp], "rtlws_fm_last_error": ([], _str)}
+FM_SYMBOLS = list(_FM_PROTOTYPES)
+fm_lib, fm_last_error = _library("fm", _FM_PROTOTYPES)
 
 
-def fm_lib():
-    """librtlws_fm.so (include/rtlws_fm.h); it needs librtlws_hip.so's engine."""
-    return _satellite(FM_LIB, _FM_PROTOTYPES)
+def fm_supported(block_len, nblocks=1, cic_r=0):
+    return fm_lib().rtlws_fm_supported(int(block_len), int(nblocks), int(cic_r))
 
 
+def fm_grid(block_len, nblocks, cic_r=0):
+    """rtlws_fm_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
+    return _outs(fm_lib().rtlws_fm_grid, (int(block_len), int(nblocks), int(cic_r)), _GRID)
+
+
+# ---- include/rtlws_ddc.h ----
+DDC_LOG2_PERIOD = 16       # rtlws_ddc.h: the phase period P = 2^16
+DDC_MAX_CHANNELS = 32
 _DDC_PROTOTYPES = {
     "rtlws_ddc_supported": [_i, _i], "rtlws_ddc_table": [_vp], "rtlws_ddc_tuning_word": [C.c_double, C.c_double, _ip],
     "rtlws_ddc_open": ([_vp], _vp), "rtlws_ddc_grid": [_i, _i, _l, _ip, _ip, _ip, _ip],
     "rtlws_ddc_run": [_vp, _i, _vp, _l, _l, _i, _vp, _vp, _l, _vp], "rtlws_ddc_close": ([_vp], None),
     "rtlws_ddc_last_error": ([], _str)}
+DDC_SYMBOLS = list(_DDC_PROTOTYPES)
+ddc_lib, ddc_last_error = _library("ddc", _DDC_PROTOTYPES)
 
 
-def ddc_lib():
-    """librtlws_ddc.so (include/rtlws_ddc.h); it needs librtlws_hip.so's engine."""
-    return _satellite(DDC_LIB, _DDC_PROTOTYPES)
+def ddc_supported(cic_r, nchannels=1):
+    return ddc_lib().rtlws_ddc_supported(int(cic_r), int(nchannels))
 
 
+def ddc_table():
+    """rtlws_ddc_table: the phasor table as the library builds it, int16 [P, 2] = (cos, sin).  No GPU needed."""
+    t = np.empty((1 << DDC_LOG2_PERIOD, 2), dtype=np.int16)
+    rc = ddc_lib().rtlws_ddc_table(_p(t))
+    if rc != 0:
+        raise RuntimeError("rtlws_ddc_table failed (rc=%d): %s" % (rc, ddc_last_error()))
+    return t
+
+
+def ddc_tuning_word(offset_hz, sample_rate_hz):
+    """rtlws_ddc_tuning_word: (rc, word).  No GPU needed."""
+    return _outs(ddc_lib().rtlws_ddc_tuning_word, (float(offset_hz), float(sample_rate_hz)), (C.c_int,))
+
+
+def ddc_grid(cic_r, nchannels, dec_len):
+    """rtlws_ddc_grid: (rc, workgroups, threads, LDS bytes, decimated samples per tile).  No GPU needed."""
+    return _outs(ddc_lib().rtlws_ddc_grid, (int(cic_r), int(nchannels), int(dec_len)), _GRID)
+
+
+# ---- include/rtlws_ddcfir.h ----
+DDCFIR_MAX_TAPS, DDCFIR_MAX_TAP, DDCFIR_MAX_SHIFT = 256, 32639, 30       # rtlws_ddcfir.h
 _DDCFIR_PROTOTYPES = {
     "rtlws_ddcfir_supported": [_i, _i, _i], "rtlws_ddcfir_samples_needed": ([_i, _i, _l], _l),
     "rtlws_ddcfir_grid": [_i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_ddcfir_design": [_i, _i, _vp],
     "rtlws_ddcfir_bound": [_i, _vp, _i, C.POINTER(C.c_double)], "rtlws_ddcfir_open": ([_vp, _i, _i, _vp], _vp),
     "rtlws_ddcfir_run": [_vp, _vp, _l, _l, _i, _vp, _i, _vp, _l, _vp], "rtlws_ddcfir_close": ([_vp], None),
     "rtlws_ddcfir_last_error": ([], _str)}
+DDCFIR_SYMBOLS = list(_DDCFIR_PROTOTYPES)
+ddcfir_lib, ddcfir_last_error = _library("ddcfir", _DDCFIR_PROTOTYPES)
 
 
-def ddcfir_lib():
-    """librtlws_ddcfir.so (include/rtlws_ddcfir.h); it needs librtlws_hip.so's engine."""
-    return _satellite(DDCFIR_LIB, _DDCFIR_PROTOTYPES)
+def ddcfir_supported(decim, ntaps, nchannels=1):
+    return ddcfir_lib().rtlws_ddcfir_supported(int(decim), int(ntaps), int(nchannels))
 
 
+def ddcfir_samples_needed(decim, ntaps, dec_len):
+    """rtlws_ddcfir_samples_needed: (dec_len - 1) * decim + ntaps, or -1.  No GPU needed."""
+    return ddcfir_lib().rtlws_ddcfir_samples_needed(int(decim), int(ntaps), int(dec_len))
+
+
+def ddcfir_grid(decim, ntaps, nchannels, dec_len):
+    """rtlws_ddcfir_grid: (rc, workgroups, threads, LDS bytes, decimated samples per tile).  No GPU needed."""
+    return _outs(ddcfir_lib().rtlws_ddcfir_grid, (int(decim), int(ntaps), int(nchannels), int(dec_len)), _GRID)
+
+
+def ddcfir_design(decim, ntaps):
+    """rtlws_ddcfir_design: the Hamming-windowed sinc for decimation by decim, int16 [ntaps].  No GPU needed."""
+    taps = np.zeros(max(int(ntaps), 1), dtype=np.int16)
+    rc = ddcfir_lib().rtlws_ddcfir_design(int(decim), int(ntaps), _p(taps))
+    if rc != 0:
+        raise RuntimeError("rtlws_ddcfir_design failed (rc=%d): %s" % (rc, ddcfir_last_error()))
+    return taps[:ntaps]
+
+
+def ddcfir_bound(taps, out_shift):
+    """rtlws_ddcfir_bound: how far a component lies from the ideal mixer and filter at most.  No GPU needed."""
+    taps = np.ascontiguousarray(taps, dtype=np.int16)
+    rc, bound = _outs(ddcfir_lib().rtlws_ddcfir_bound, (taps.size, _p(taps), int(out_shift)), (C.c_double,))
+    if rc != 0:
+        raise RuntimeError("rtlws_ddcfir_bound failed (rc=%d): %s" % (rc, ddcfir_last_error()))
+    return bound
+
+
+# ---- include/rtlws_fmbank.h ----
+FMBANK_MAX_CHANNELS = 32
 _FMBANK_PROTOTYPES = {
     "rtlws_fmbank_supported": [_i, _i, _i, _l], "rtlws_fmbank_grid": [_i, _i, _i, _l, _ip, _ip, _ip, _ip],
     "rtlws_fmbank_open": ([_vp], _vp), "rtlws_fmbank_run": [_vp, _i, _vp, _i, _l, _l, _i, _vp, _vp, _vp, _vp, _l, _vp],
     "rtlws_fmbank_close": ([_vp], None), "rtlws_fmbank_last_error": ([], _str)}
+FMBANK_SYMBOLS = list(_FMBANK_PROTOTYPES)
+fmbank_lib, fmbank_last_error = _library("fmbank", _FMBANK_PROTOTYPES)
 
 
-def fmbank_lib():
-    """librtlws_fmbank.so (include/rtlws_fmbank.h); it needs librtlws_hip.so's engine."""
-    return _satellite(FMBANK_LIB, _FMBANK_PROTOTYPES)
+def fmbank_supported(cic_r, nchannels=1, block_len=20, nblocks=1):
+    return fmbank_lib().rtlws_fmbank_supported(int(cic_r), int(nchannels), int(block_len), int(nblocks))
 
 
+def fmbank_grid(cic_r, nchannels, block_len, nblocks):
+    """rtlws_fmbank_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
+    return _outs(fmbank_lib().rtlws_fmbank_grid, (int(cic_r), int(nchannels), int(block_len), int(nblocks)), _GRID)
+
+
+# ---- include/rtlws_fmfir.h ----
+FMFIR_MAX_CHANNELS = 32                                                   # rtlws_fmfir.h
 _FMFIR_PROTOTYPES = {
     "rtlws_fmfir_supported": [_i, _i, _i, _i, _l], "rtlws_fmfir_samples_needed": ([_i, _i, _i, _l], _l),
     "rtlws_fmfir_grid": [_i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_fmfir_open": ([_vp, _i, _i, _vp], _vp),
     "rtlws_fmfir_run": [_vp, _vp, _i, _l, _l, _i, _vp, _i, _vp, _vp, _vp, _l, _vp], "rtlws_fmfir_close": ([_vp], None),
     "rtlws_fmfir_last_error": ([], _str)}
+FMFIR_SYMBOLS = list(_FMFIR_PROTOTYPES)
+fmfir_lib, fmfir_last_error = _library("fmfir", _FMFIR_PROTOTYPES)
 
 
-def fmfir_lib():
-    """librtlws_fmfir.so (include/rtlws_fmfir.h); it needs librtlws_hip.so's engine."""
-    return _satellite(FMFIR_LIB, _FMFIR_PROTOTYPES)
+def fmfir_supported(decim, ntaps, nchannels=1, block_len=20, nblocks=1):
+    return fmfir_lib().rtlws_fmfir_supported(int(decim), int(ntaps), int(nchannels), int(block_len), int(nblocks))
+
+
+def fmfir_samples_needed(decim, ntaps, block_len, nblocks):
+    """rtlws_fmfir_samples_needed: (nblocks * block_len - 1) * decim + ntaps, 0 without blocks, or -1.  No GPU needed."""
+    return fmfir_lib().rtlws_fmfir_samples_needed(int(decim), int(ntaps), int(block_len), int(nblocks))
+
+
+def fmfir_grid(decim, ntaps, nchannels, block_len, nblocks):
+    """rtlws_fmfir_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
+    return _outs(fmfir_lib().rtlws_fmfir_grid, (int(decim), int(ntaps), int(nchannels), int(block_len), int(nblocks)), _GRID)
 
 
 def amd_lib():
@@ -451,47 +476,16 @@ def amd_lib():
     return _amd
 
 
-def last_error():
-    return hip_lib().rtlws_last_error().decode()
-
-
-def long_last_error():
-    return long_lib().rtlws_long_last_error().decode()
-
-
-def anylen_last_error():
-    return anylen_lib().rtlws_anylen_last_error().decode()
-
-
-def fm_last_error():
-    return fm_lib().rtlws_fm_last_error().decode()
-
-
-def fm_supported(block_len, nblocks=1, cic_r=0):
-    return fm_lib().rtlws_fm_supported(int(block_len), int(nblocks), int(cic_r))
-
-
-def fm_grid(block_len, nblocks, cic_r=0):
-    """rtlws_fm_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
-    b, t, s, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = fm_lib().rtlws_fm_grid(int(block_len), int(nblocks), int(cic_r), C.byref(b), C.byref(t), C.byref(s), C.byref(a))
-    return rc, b.value, t.value, s.value, a.value
-
-
+# ---- include/rtlws_pfb.h ----
+PFB_CHANNEL_MAJOR, PFB_TIME_MAJOR = 0, 1       # rtlws_pfb.h: the output layouts
+_PFB_LAYOUTS = {"channel": PFB_CHANNEL_MAJOR, "time": PFB_TIME_MAJOR}
 _PFB_PROTOTYPES = {
     "rtlws_pfb_supported": [_i, _i, _i], "rtlws_pfb_design": [_i, _i, _vp], "rtlws_pfb_twiddles": [_i, _vp],
     "rtlws_pfb_samples_needed": ([_i, _i, _i, _l], _l), "rtlws_pfb_grid": [_i, _i, _i, _l, _ip, _ip, _ip, _ip],
     "rtlws_pfb_open": ([_vp, _i, _i, _vp], _vp), "rtlws_pfb_run": [_vp, _vp, _l, _i, _l, _i, _vp, _l, _vp],
     "rtlws_pfb_close": ([_vp], None), "rtlws_pfb_last_error": ([], _str)}
-
-
-def pfb_lib():
-    """librtlws_pfb.so (include/rtlws_pfb.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PFB_LIB, _PFB_PROTOTYPES)
-
-
-def pfb_last_error():
-    return pfb_lib().rtlws_pfb_last_error().decode()
+PFB_SYMBOLS = list(_PFB_PROTOTYPES)
+pfb_lib, pfb_last_error = _library("pfb", _PFB_PROTOTYPES)
 
 
 def pfb_supported(log2_channels, taps_per_branch, hop=None):
@@ -529,26 +523,21 @@ def pfb_samples_needed(log2_channels, taps_per_branch, hop, nframes):
 
 def pfb_grid(log2_channels, taps_per_branch, hop, nframes):
     """rtlws_pfb_grid: (rc, workgroups, threads, LDS bytes, frames per tile).  No GPU needed."""
-    b, t, s, f = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = pfb_lib().rtlws_pfb_grid(int(log2_channels), int(taps_per_branch), int(hop), int(nframes), C.byref(b), C.byref(t),
-                                  C.byref(s), C.byref(f))
-    return rc, b.value, t.value, s.value, f.value
+    return _outs(pfb_lib().rtlws_pfb_grid, (int(log2_channels), int(taps_per_branch), int(hop), int(nframes)), _GRID)
 
 
+# ---- include/rtlws_pfbspec.h ----
+PFBSPEC_MAX_K_AVG = 65536
+# rtlws_pfbspec.h's output kinds are enum rtlws_output's values
+_PFBSPEC_OUTPUTS = {"power": OUT_POWER_SUM, "db": OUT_MEAN_DB, "payload": OUT_PAYLOAD_U8}
+_PFBSPEC_OUTPUTS.update(_OUTPUTS)
 _PFBSPEC_PROTOTYPES = {
     "rtlws_pfbspec_supported": [_i, _i, _i, _i, _i], "rtlws_pfbspec_samples_needed": ([_i, _i, _i, _i, _l], _l),
     "rtlws_pfbspec_grid": [_i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_pfbspec_open": ([_vp, _i, _i, _vp], _vp),
     "rtlws_pfbspec_run": [_vp, _vp, _l, _i, _i, _i, _i, C.c_float, _vp, _l, _vp], "rtlws_pfbspec_close": ([_vp], None),
     "rtlws_pfbspec_last_error": ([], _str)}
-
-
-def pfbspec_lib():
-    """librtlws_pfbspec.so (include/rtlws_pfbspec.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PFBSPEC_LIB, _PFBSPEC_PROTOTYPES)
-
-
-def pfbspec_last_error():
-    return pfbspec_lib().rtlws_pfbspec_last_error().decode()
+PFBSPEC_SYMBOLS = list(_PFBSPEC_PROTOTYPES)
+pfbspec_lib, pfbspec_last_error = _library("pfbspec", _PFBSPEC_PROTOTYPES)
 
 
 def pfbspec_supported(log2_channels, taps_per_branch, hop, k_avg, output="power"):
@@ -565,26 +554,20 @@ def pfbspec_samples_needed(log2_channels, taps_per_branch, hop, k_avg, nspectra)
 
 def pfbspec_grid(log2_channels, taps_per_branch, hop, k_avg, nspectra):
     """rtlws_pfbspec_grid: (rc, workgroups, threads, LDS bytes, spectra per workgroup).  No GPU needed."""
-    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = pfbspec_lib().rtlws_pfbspec_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nspectra),
-                                          C.byref(b), C.byref(t), C.byref(s), C.byref(g))
-    return rc, b.value, t.value, s.value, g.value
+    return _outs(pfbspec_lib().rtlws_pfbspec_grid,
+                 (int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nspectra)), _GRID)
 
 
+# ---- include/rtlws_pfbxc.h ----
+PFBXC_MAX_K_AVG = 65536
+PFBXC_MIN_INPUTS, PFBXC_MAX_INPUTS = 2, 4
 _PFBXC_PROTOTYPES = {
     "rtlws_pfbxc_supported": [_i, _i, _i, _i, _i], "rtlws_pfbxc_samples_needed": ([_i, _i, _i, _i, _l], _l),
     "rtlws_pfbxc_pair_index": [_i, _i, _i], "rtlws_pfbxc_grid": [_i, _i, _i, _i, _i, _l, _ip, _ip, _ip, _ip],
     "rtlws_pfbxc_open": ([_vp, _i, _i, _vp, _i], _vp), "rtlws_pfbxc_run": [_vp, _vpp, _l, _i, _i, _i, _vp, _l, _vp, _l, _vp],
     "rtlws_pfbxc_close": ([_vp], None), "rtlws_pfbxc_last_error": ([], _str)}
-
-
-def pfbxc_lib():
-    """librtlws_pfbxc.so (include/rtlws_pfbxc.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PFBXC_LIB, _PFBXC_PROTOTYPES)
-
-
-def pfbxc_last_error():
-    return pfbxc_lib().rtlws_pfbxc_last_error().decode()
+PFBXC_SYMBOLS = list(_PFBXC_PROTOTYPES)
+pfbxc_lib, pfbxc_last_error = _library("pfbxc", _PFBXC_PROTOTYPES)
 
 
 def pfbxc_supported(log2_channels, taps_per_branch, hop, k_avg, ninputs=2):
@@ -605,27 +588,22 @@ def pfbxc_pair_index(ninputs, a, b):
 
 def pfbxc_grid(log2_channels, taps_per_branch, hop, k_avg, ninputs, nspectra):
     """rtlws_pfbxc_grid: (rc, workgroups, threads, LDS bytes, spectra per workgroup).  No GPU needed."""
-    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = pfbxc_lib().rtlws_pfbxc_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(ninputs),
-                                      int(nspectra), C.byref(b), C.byref(t), C.byref(s), C.byref(g))
-    return rc, b.value, t.value, s.value, g.value
+    return _outs(pfbxc_lib().rtlws_pfbxc_grid,
+                 (int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(ninputs), int(nspectra)), _GRID)
 
 
+# ---- include/rtlws_pfbbf.h ----
+PFBBF_MAX_K_AVG = 65536
+PFBBF_MIN_INPUTS, PFBBF_MAX_INPUTS = 1, 8
+PFBBF_MIN_BEAMS, PFBBF_MAX_BEAMS = 1, 4
 _PFBBF_PROTOTYPES = {
     "rtlws_pfbbf_supported": [_i, _i, _i, _i, _i], "rtlws_pfbbf_samples_needed": ([_i, _i, _i, _i, _l], _l),
     "rtlws_pfbbf_grid": [_i, _i, _i, _i, _l, _ip, _ip, _ip, _ip], "rtlws_pfbbf_open": ([_vp, _i, _i, _vp, _i, _i], _vp),
     "rtlws_pfbbf_run": [_vp, _vpp, _i, _vp, _i, _l, _i, _l, _i, _vp, _l, _l, _vp],
     "rtlws_pfbbf_power": [_vp, _vpp, _i, _vp, _i, _l, _i, _i, _i, _vp, _l, _vp], "rtlws_pfbbf_close": ([_vp], None),
     "rtlws_pfbbf_last_error": ([], _str)}
-
-
-def pfbbf_lib():
-    """librtlws_pfbbf.so (include/rtlws_pfbbf.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PFBBF_LIB, _PFBBF_PROTOTYPES)
-
-
-def pfbbf_last_error():
-    return pfbbf_lib().rtlws_pfbbf_last_error().decode()
+PFBBF_SYMBOLS = list(_PFBBF_PROTOTYPES)
+pfbbf_lib, pfbbf_last_error = _library("pfbbf", _PFBBF_PROTOTYPES)
 
 
 def pfbbf_supported(log2_channels, taps_per_branch, hop, ninputs=1, nbeams=1):
@@ -641,12 +619,12 @@ def pfbbf_samples_needed(log2_channels, taps_per_branch, hop, k_avg, count):
 
 def pfbbf_grid(log2_channels, taps_per_branch, hop, k_avg, count):
     """rtlws_pfbbf_grid: (rc, workgroups, threads, LDS bytes, frames (k_avg 0) or spectra per workgroup).  No GPU needed."""
-    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = pfbbf_lib().rtlws_pfbbf_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(count),
-                                      C.byref(b), C.byref(t), C.byref(s), C.byref(g))
-    return rc, b.value, t.value, s.value, g.value
+    return _outs(pfbbf_lib().rtlws_pfbbf_grid,
+                 (int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(count)), _GRID)
 
 
+# ---- include/rtlws_pfbsk.h ----
+PFBSK_MAX_K_AVG, PFBSK_MAX_NSUB = 65536, 65535
 _fp = C.POINTER(C.c_float)
 _PFBSK_PROTOTYPES = {
     "rtlws_pfbsk_supported": [_i, _i, _i, _i, _i, _i], "rtlws_pfbsk_samples_needed": ([_i, _i, _i, _i, _i, _l], _l),
@@ -655,15 +633,8 @@ _PFBSK_PROTOTYPES = {
     "rtlws_pfbsk_run": [_vp, _vp, _l, _i, _i, _i, C.c_float, C.c_float, C.c_float, _i, _i, C.c_float, _vp, _l, _vp, _l, _vp, _vp,
                         _l, _vp],
     "rtlws_pfbsk_close": ([_vp], None), "rtlws_pfbsk_last_error": ([], _str)}
-
-
-def pfbsk_lib():
-    """librtlws_pfbsk.so (include/rtlws_pfbsk.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PFBSK_LIB, _PFBSK_PROTOTYPES)
-
-
-def pfbsk_last_error():
-    return pfbsk_lib().rtlws_pfbsk_last_error().decode()
+PFBSK_SYMBOLS = list(_PFBSK_PROTOTYPES)
+pfbsk_lib, pfbsk_last_error = _library("pfbsk", _PFBSK_PROTOTYPES)
 
 
 def pfbsk_supported(log2_channels, taps_per_branch, hop, k_avg, nsub, output="power"):
@@ -680,10 +651,8 @@ def pfbsk_samples_needed(log2_channels, taps_per_branch, hop, k_avg, nsub, nspec
 
 def pfbsk_grid(log2_channels, taps_per_branch, hop, k_avg, nsub, nspectra):
     """rtlws_pfbsk_grid: (rc, workgroups, threads, LDS bytes, output rows per workgroup).  No GPU needed."""
-    b, t, s, g = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = pfbsk_lib().rtlws_pfbsk_grid(int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nsub), int(nspectra),
-                                      C.byref(b), C.byref(t), C.byref(s), C.byref(g))
-    return rc, b.value, t.value, s.value, g.value
+    return _outs(pfbsk_lib().rtlws_pfbsk_grid,
+                 (int(log2_channels), int(taps_per_branch), int(hop), int(k_avg), int(nsub), int(nspectra)), _GRID)
 
 
 def pfbsk_power_scale(log2_channels, taps):
@@ -697,27 +666,21 @@ def pfbsk_power_scale(log2_channels, taps):
 
 def pfbsk_bounds(k_avg, sk_lo, sk_hi):
     """rtlws_pfbsk_bounds: thresholds on the estimator -> (ratio_lo, ratio_hi) as floats.  No GPU needed."""
-    lo, hi = C.c_float(), C.c_float()
-    rc = pfbsk_lib().rtlws_pfbsk_bounds(int(k_avg), float(sk_lo), float(sk_hi), C.byref(lo), C.byref(hi))
+    rc, lo, hi = _outs(pfbsk_lib().rtlws_pfbsk_bounds, (int(k_avg), float(sk_lo), float(sk_hi)), (C.c_float,) * 2)
     if rc != 0:
         raise RuntimeError("rtlws_pfbsk_bounds failed (rc=%d): %s" % (rc, pfbsk_last_error()))
-    return lo.value, hi.value
+    return lo, hi
 
 
+# ---- include/rtlws_dedisp.h ----
+DEDISP_MIN_NCHAN, DEDISP_MAX_NCHAN, DEDISP_MAX_TRIALS, DEDISP_MAX_DELAY = 4, 4096, 4096, 65535
 _DEDISP_PROTOTYPES = {
     "rtlws_dedisp_supported": [_i, _i], "rtlws_dedisp_delays": [_i, _i, C.c_double, C.c_double, C.c_double, _i, C.c_double, C.c_double, _vp],
     "rtlws_dedisp_geometry": [_i, _i, _vp, _vp, _l, _ip, _ip, _ip, _ip, _ip, _ip], "rtlws_dedisp_open": ([_vp, _i, _i, _vp, _vp], _vp),
     "rtlws_dedisp_rows_needed": ([_vp, _l], _l), "rtlws_dedisp_run": [_vp, _vp, _l, _l, _vp, _l, _vp],
     "rtlws_dedisp_close": ([_vp], None), "rtlws_dedisp_last_error": ([], _str)}
-
-
-def dedisp_lib():
-    """librtlws_dedisp.so (include/rtlws_dedisp.h); it needs librtlws_hip.so's engine."""
-    return _satellite(DEDISP_LIB, _DEDISP_PROTOTYPES)
-
-
-def dedisp_last_error():
-    return dedisp_lib().rtlws_dedisp_last_error().decode()
+DEDISP_SYMBOLS = list(_DEDISP_PROTOTYPES)
+dedisp_lib, dedisp_last_error = _library("dedisp", _DEDISP_PROTOTYPES)
 
 
 def dedisp_supported(nchan, ntrials):
@@ -752,12 +715,13 @@ def dedisp_geometry(delays, mask=None, nout=0):
     """rtlws_dedisp_geometry of a table int32 [ntrials, nchan]: (rc, workgroups, threads, LDS bytes, outputs per
     workgroup, trials per workgroup, largest delay over the kept positions).  No GPU needed."""
     delays, mask = _dedisp_table(delays, mask)
-    v = [C.c_int(0) for _ in range(6)]
-    rc = dedisp_lib().rtlws_dedisp_geometry(delays.shape[1], delays.shape[0], _p(delays), None if mask is None else _p(mask),
-                                            int(nout), *[C.byref(x) for x in v])
-    return (rc,) + tuple(x.value for x in v)
+    return _outs(dedisp_lib().rtlws_dedisp_geometry,
+                 (delays.shape[1], delays.shape[0], _p(delays), None if mask is None else _p(mask), int(nout)), (C.c_int,) * 6)
 
 
+# ---- include/rtlws_pulse.h ----
+PULSE_MAX_WIDTHS, PULSE_MAX_WIDTH, PULSE_MIN_SEG, PULSE_MAX_SEG, PULSE_MAX_TRIALS, PULSE_MAX_NOUT = 16, 1024, 64, 1 << 20, 65536, 1 << 30
+PULSE_GUARD = 8            # Engine.pulse(fill=...): preset elements behind every output array
 _lp = C.POINTER(C.c_long)
 _PULSE_PROTOTYPES = {
     "rtlws_pulse_supported": [_i, _vp, _l], "rtlws_pulse_geometry": [_i, _vp, _l, _i, _l, _ip, _ip, _ip, _ip, _ip, _lp],
@@ -765,15 +729,8 @@ _PULSE_PROTOTYPES = {
     "rtlws_pulse_segments": ([_vp, _l], _l), "rtlws_pulse_run": [_vp, _vp, _l, _i, _l, _vp, _vp, _vp, _vp],
     "rtlws_pulse_snr": ([C.c_double, _i, C.c_double, C.c_double, _l], C.c_double),
     "rtlws_pulse_close": ([_vp], None), "rtlws_pulse_last_error": ([], _str)}
-
-
-def pulse_lib():
-    """librtlws_pulse.so (include/rtlws_pulse.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PULSE_LIB, _PULSE_PROTOTYPES)
-
-
-def pulse_last_error():
-    return pulse_lib().rtlws_pulse_last_error().decode()
+PULSE_SYMBOLS = list(_PULSE_PROTOTYPES)
+pulse_lib, pulse_last_error = _library("pulse", _PULSE_PROTOTYPES)
 
 
 def _pulse_widths(widths):
@@ -791,11 +748,9 @@ def pulse_geometry(widths, seg, ntrials=1, nout=0):
     """rtlws_pulse_geometry: (rc, workgroups, threads, LDS bytes, outputs per tile, levels kept, segments).  No GPU
     needed."""
     widths = _pulse_widths(widths)
-    v = [C.c_int(0) for _ in range(5)]
-    nseg = C.c_long(0)
-    rc = pulse_lib().rtlws_pulse_geometry(0 if widths is None else widths.size, None if widths is None else _p(widths), int(seg),
-                                          int(ntrials), int(nout), *([C.byref(x) for x in v] + [C.byref(nseg)]))
-    return (rc,) + tuple(x.value for x in v) + (nseg.value,)
+    return _outs(pulse_lib().rtlws_pulse_geometry,
+                 (0 if widths is None else widths.size, None if widths is None else _p(widths), int(seg), int(ntrials), int(nout)),
+                 (C.c_int,) * 5 + (C.c_long,))
 
 
 def pulse_snr(peak, width, sum1, sum2, count):
@@ -803,6 +758,9 @@ def pulse_snr(peak, width, sum1, sum2, count):
     return pulse_lib().rtlws_pulse_snr(float(peak), int(width), float(sum1), float(sum2), int(count))
 
 
+# ---- include/rtlws_fold.h ----
+FOLD_MAX_PERIODS, FOLD_MIN_BINS, FOLD_MAX_BINS, FOLD_MIN_SUB, FOLD_MAX_SUB, FOLD_MAX_TRIALS, FOLD_MAX_NSAMP = 4096, 2, 256, 64, 1 << 24, 65536, 1 << 30
+FOLD_GUARD = 8             # Engine.fold(fill=...): preset elements behind both output arrays
 _u64 = C.c_uint64
 _FOLD_PROTOTYPES = {
     "rtlws_fold_supported": [_i, _vp, _vp, _i, _l], "rtlws_fold_geometry": [_i, _i, _l, _i, _l, _ip, _ip, _ip, _ip, _ip, _lp],
@@ -811,15 +769,8 @@ _FOLD_PROTOTYPES = {
     "rtlws_fold_phase_at": ([_u64, _u64, _l], _u64),
     "rtlws_fold_chi2": ([_vp, _vp, _i, C.c_double, C.c_double, _l], C.c_double),
     "rtlws_fold_close": ([_vp], None), "rtlws_fold_last_error": ([], _str)}
-
-
-def fold_lib():
-    """librtlws_fold.so (include/rtlws_fold.h); it needs librtlws_hip.so's engine."""
-    return _satellite(FOLD_LIB, _FOLD_PROTOTYPES)
-
-
-def fold_last_error():
-    return fold_lib().rtlws_fold_last_error().decode()
+FOLD_SYMBOLS = list(_FOLD_PROTOTYPES)
+fold_lib, fold_last_error = _library("fold", _FOLD_PROTOTYPES)
 
 
 def _fold_table(values):
@@ -837,11 +788,8 @@ def fold_supported(steps, phases, nbins, sub):
 def fold_geometry(nperiods, nbins, sub, ntrials=1, nsamp=0):
     """rtlws_fold_geometry: (rc, workgroups, threads, LDS bytes, samples per tile, wavefronts per workgroup, sub-integrations).
     No GPU needed."""
-    v = [C.c_int(0) for _ in range(5)]
-    nsub = C.c_long(0)
-    rc = fold_lib().rtlws_fold_geometry(int(nperiods), int(nbins), int(sub), int(ntrials), int(nsamp),
-                                        *([C.byref(x) for x in v] + [C.byref(nsub)]))
-    return (rc,) + tuple(x.value for x in v) + (nsub.value,)
+    return _outs(fold_lib().rtlws_fold_geometry, (int(nperiods), int(nbins), int(sub), int(ntrials), int(nsamp)),
+                 (C.c_int,) * 5 + (C.c_long,))
 
 
 def fold_step(period_in_samples):
@@ -863,20 +811,16 @@ def fold_chi2(prof, hits, sum1, sum2, count):
                                       float(sum2), int(count))
 
 
+# ---- include/rtlws_period.h ----
+PERIOD_MIN_LOG2N, PERIOD_MAX_LOG2N, PERIOD_MAX_LEVELS, PERIOD_MIN_NORM, PERIOD_MIN_SEG, PERIOD_MAX_TRIALS = 10, 15, 5, 16, 64, 65536
+PERIOD_GUARD = 8           # Engine.period(fill=...): preset elements behind every output array
 _PERIOD_PROTOTYPES = {
     "rtlws_period_supported": [_i, _i, _i, _i, _i], "rtlws_period_geometry": [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip],
     "rtlws_period_open": ([_vp, _i, _i, _i, _i, _i], _vp), "rtlws_period_run": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "rtlws_period_samples": ([_i, _i, _i], C.c_double), "rtlws_period_lnq": ([C.c_double, _i], C.c_double),
     "rtlws_period_close": ([_vp], None), "rtlws_period_last_error": ([], _str)}
-
-
-def period_lib():
-    """librtlws_period.so (include/rtlws_period.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PERIOD_LIB, _PERIOD_PROTOTYPES)
-
-
-def period_last_error():
-    return period_lib().rtlws_period_last_error().decode()
+PERIOD_SYMBOLS = list(_PERIOD_PROTOTYPES)
+period_lib, period_last_error = _library("period", _PERIOD_PROTOTYPES)
 
 
 def period_supported(log2n, levels, norm, seg, klo):
@@ -886,9 +830,7 @@ def period_supported(log2n, levels, norm, seg, klo):
 
 def period_geometry(log2n, levels, norm, seg, klo, ntrials=1):
     """rtlws_period_geometry: (rc, workgroups, threads, LDS bytes, segments).  No GPU needed."""
-    v = [C.c_int(0) for _ in range(4)]
-    rc = period_lib().rtlws_period_geometry(int(log2n), int(levels), int(norm), int(seg), int(klo), int(ntrials), *[C.byref(x) for x in v])
-    return (rc,) + tuple(x.value for x in v)
+    return _outs(period_lib().rtlws_period_geometry, (int(log2n), int(levels), int(norm), int(seg), int(klo), int(ntrials)), _GRID)
 
 
 def period_samples(log2n, level, k):
@@ -903,20 +845,17 @@ def period_lnq(s, h):
     return period_lib().rtlws_period_lnq(float(s), int(h))
 
 
+# ---- include/rtlws_periodlong.h ----
+PERIODLONG_MIN_LOG2N, PERIODLONG_MAX_LOG2N, PERIODLONG_MAX_LEVELS, PERIODLONG_MAX_TRIALS, PERIODLONG_STAGES = 16, 22, 5, 65536, 6
+PERIODLONG_MIN_NORM, PERIODLONG_MAX_NORM, PERIODLONG_MIN_SEG, PERIODLONG_MAX_SEG = 16, 16384, 64, 16384
+PERIODLONG_WORKSPACE_CAP = 1 << 30
 _PERIODLONG_PROTOTYPES = {
     "rtlws_periodlong_supported": [_i, _i, _i, _i, _i], "rtlws_periodlong_geometry": [_i, _i, _i, _i, _i, _i, _ip, _ip, _ip, _ip],
-    "rtlws_periodlong_open": ([_vp, _i, _i, _i, _i, _i, _i], _vp), "rtlws_periodlong_workspace_bytes": ([_vp], C.c_size_t),
+    "rtlws_periodlong_open": ([_vp, _i, _i, _i, _i, _i, _i], _vp), "rtlws_periodlong_workspace_bytes": ([_vp], _sz),
     "rtlws_periodlong_run": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp], "rtlws_periodlong_samples": ([_i, _i, _i], C.c_double),
     "rtlws_periodlong_close": ([_vp], None), "rtlws_periodlong_last_error": ([], _str)}
-
-
-def periodlong_lib():
-    """librtlws_periodlong.so (include/rtlws_periodlong.h); it needs librtlws_hip.so's engine."""
-    return _satellite(PERIODLONG_LIB, _PERIODLONG_PROTOTYPES)
-
-
-def periodlong_last_error():
-    return periodlong_lib().rtlws_periodlong_last_error().decode()
+PERIODLONG_SYMBOLS = list(_PERIODLONG_PROTOTYPES)
+periodlong_lib, periodlong_last_error = _library("periodlong", _PERIODLONG_PROTOTYPES)
 
 
 def periodlong_supported(log2n, levels, norm, seg, klo):
@@ -927,11 +866,8 @@ def periodlong_supported(log2n, levels, norm, seg, klo):
 def periodlong_geometry(log2n, levels, norm, seg, klo, ntrials=1):
     """rtlws_periodlong_geometry: (rc, workgroups, threads, LDS bytes -- a tuple of PERIODLONG_STAGES each: mean, columns,
     rows, untangling, whitening, peaks -- and segments).  No GPU needed."""
-    v = [(C.c_int * PERIODLONG_STAGES)() for _ in range(3)]
-    nseg = C.c_int()
-    rc = periodlong_lib().rtlws_periodlong_geometry(int(log2n), int(levels), int(norm), int(seg), int(klo), int(ntrials), v[0], v[1], v[2],
-                                                    C.byref(nseg))
-    return (rc,) + tuple(tuple(x) for x in v) + (nseg.value,)
+    return _outs(periodlong_lib().rtlws_periodlong_geometry, (int(log2n), int(levels), int(norm), int(seg), int(klo), int(ntrials)),
+                 (C.c_int * PERIODLONG_STAGES,) * 3 + (C.c_int,))
 
 
 def periodlong_samples(log2n, level, k):
@@ -940,22 +876,17 @@ def periodlong_samples(log2n, level, k):
     return periodlong_lib().rtlws_periodlong_samples(int(log2n), int(level), int(k))
 
 
+# ---- include/rtlws_accel.h ----
+ACCEL_MAX_NACCEL, ACCEL_MAX_COEF, ACCEL_MAX_VIRTUAL, ACCEL_STAGES = 1024, 1 << 40, 65536, 6
 _i64p = C.POINTER(C.c_int64)
 _ACCEL_PROTOTYPES = {
     "rtlws_accel_supported": [_i, _i, _i, _i, _i, _i, _i64p], "rtlws_accel_geometry": [_i, _i, _i, _i, _i, _i, _i64p, _i, _ip, _ip, _ip, _ip],
-    "rtlws_accel_open": ([_vp, _i, _i, _i, _i, _i, _i, _i64p, _i], _vp), "rtlws_accel_workspace_bytes": ([_vp], C.c_size_t),
+    "rtlws_accel_open": ([_vp, _i, _i, _i, _i, _i, _i, _i64p, _i], _vp), "rtlws_accel_workspace_bytes": ([_vp], _sz),
     "rtlws_accel_search": [_vp, _vp, _l, _i, _i, _vp, _vp, _vp, _vp, _vp], "rtlws_accel_resample": [_vp, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp],
     "rtlws_accel_coef": ([C.c_double, C.c_double], C.c_int64), "rtlws_accel_coef_from_shift": ([C.c_double, _i], C.c_int64),
     "rtlws_accel_shift": ([C.c_int64, _i, _i], C.c_long), "rtlws_accel_close": ([_vp], None), "rtlws_accel_last_error": ([], _str)}
-
-
-def accel_lib():
-    """librtlws_accel.so (include/rtlws_accel.h); it needs librtlws_hip.so's engine."""
-    return _satellite(ACCEL_LIB, _ACCEL_PROTOTYPES)
-
-
-def accel_last_error():
-    return accel_lib().rtlws_accel_last_error().decode()
+ACCEL_SYMBOLS = list(_ACCEL_PROTOTYPES)
+accel_lib, accel_last_error = _library("accel", _ACCEL_PROTOTYPES)
 
 
 def _accel_table(coefs):
@@ -977,11 +908,9 @@ def accel_geometry(log2n, levels, norm, seg, klo, coefs, ntrials=1, naccel=None)
     """rtlws_accel_geometry: (rc, workgroups over all ntrials * naccel virtual trials, threads, LDS bytes -- a tuple of
     ACCEL_STAGES each -- and segments).  No GPU needed."""
     n, _table, ptr = _accel_table(coefs)
-    v = [(C.c_int * ACCEL_STAGES)() for _ in range(3)]
-    nseg = C.c_int()
-    rc = accel_lib().rtlws_accel_geometry(int(log2n), int(levels), int(norm), int(seg), int(klo), n if naccel is None else int(naccel), ptr,
-                                          int(ntrials), v[0], v[1], v[2], C.byref(nseg))
-    return (rc,) + tuple(tuple(x) for x in v) + (nseg.value,)
+    return _outs(accel_lib().rtlws_accel_geometry,
+                 (int(log2n), int(levels), int(norm), int(seg), int(klo), n if naccel is None else int(naccel), ptr, int(ntrials)),
+                 (C.c_int * ACCEL_STAGES,) * 3 + (C.c_int,))
 
 
 def accel_coef(accel_m_s2, tsamp_s):
@@ -1000,114 +929,6 @@ def accel_shift(coef, nsamp, n):
     return int(accel_lib().rtlws_accel_shift(int(coef), int(nsamp), int(n)))
 
 
-def ddc_last_error():
-    return ddc_lib().rtlws_ddc_last_error().decode()
-
-
-def ddc_supported(cic_r, nchannels=1):
-    return ddc_lib().rtlws_ddc_supported(int(cic_r), int(nchannels))
-
-
-def ddc_table():
-    """rtlws_ddc_table: the phasor table as the library builds it, int16 [P, 2] = (cos, sin).  No GPU needed."""
-    t = np.empty((1 << DDC_LOG2_PERIOD, 2), dtype=np.int16)
-    rc = ddc_lib().rtlws_ddc_table(_p(t))
-    if rc != 0:
-        raise RuntimeError("rtlws_ddc_table failed (rc=%d): %s" % (rc, ddc_last_error()))
-    return t
-
-
-def ddc_tuning_word(offset_hz, sample_rate_hz):
-    """rtlws_ddc_tuning_word: (rc, word).  No GPU needed."""
-    w = C.c_int(0)
-    rc = ddc_lib().rtlws_ddc_tuning_word(float(offset_hz), float(sample_rate_hz), C.byref(w))
-    return rc, w.value
-
-
-def ddc_grid(cic_r, nchannels, dec_len):
-    """rtlws_ddc_grid: (rc, workgroups, threads, LDS bytes, decimated samples per tile).  No GPU needed."""
-    b, t, s, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = ddc_lib().rtlws_ddc_grid(int(cic_r), int(nchannels), int(dec_len), C.byref(b), C.byref(t), C.byref(s), C.byref(d))
-    return rc, b.value, t.value, s.value, d.value
-
-
-def ddcfir_last_error():
-    return ddcfir_lib().rtlws_ddcfir_last_error().decode()
-
-
-def ddcfir_supported(decim, ntaps, nchannels=1):
-    return ddcfir_lib().rtlws_ddcfir_supported(int(decim), int(ntaps), int(nchannels))
-
-
-def ddcfir_samples_needed(decim, ntaps, dec_len):
-    """rtlws_ddcfir_samples_needed: (dec_len - 1) * decim + ntaps, or -1.  No GPU needed."""
-    return ddcfir_lib().rtlws_ddcfir_samples_needed(int(decim), int(ntaps), int(dec_len))
-
-
-def ddcfir_grid(decim, ntaps, nchannels, dec_len):
-    """rtlws_ddcfir_grid: (rc, workgroups, threads, LDS bytes, decimated samples per tile).  No GPU needed."""
-    b, t, s, d = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-    rc = ddcfir_lib().rtlws_ddcfir_grid(int(decim), int(ntaps), int(nchannels), int(dec_len), C.byref(b), C.byref(t), C.byref(s),
-                                        C.byref(d))
-    return rc, b.value, t.value, s.value, d.value
-
-
-def ddcfir_design(decim, ntaps):
-    """rtlws_ddcfir_design: the Hamming-windowed sinc for decimation by decim, int16 [ntaps].  No GPU needed."""
-    taps = np.zeros(max(int(ntaps), 1), dtype=np.int16)
-    rc = ddcfir_lib().rtlws_ddcfir_design(int(decim), int(ntaps), _p(taps))
-    if rc != 0:
-        raise RuntimeError("rtlws_ddcfir_design failed (rc=%d): %s" % (rc, ddcfir_last_error()))
-    return taps[:ntaps]
-
-
-def ddcfir_bound(taps, out_shift):
-    """rtlws_ddcfir_bound: how far a component lies from the ideal mixer and filter at most.  No GPU needed."""
-    taps = np.ascontiguousarray(taps, dtype=np.int16)
-    b = C.c_double(0.0)
-    rc = ddcfir_lib().rtlws_ddcfir_bound(taps.size, _p(taps), int(out_shift), C.byref(b))
-    if rc != 0:
-        raise RuntimeError("rtlws_ddcfir_bound failed (rc=%d): %s" % (rc, ddcfir_last_error()))
-    return b.value
-
-
-def fmfir_last_error():
-    return fmfir_lib().rtlws_fmfir_last_error().decode()
-
-
-def fmfir_supported(decim, ntaps, nchannels=1, block_len=20, nblocks=1):
-    return fmfir_lib().rtlws_fmfir_supported(int(decim), int(ntaps), int(nchannels), int(block_len), int(nblocks))
-
-
-def fmfir_samples_needed(decim, ntaps, block_len, nblocks):
-    """rtlws_fmfir_samples_needed: (nblocks * block_len - 1) * decim + ntaps, 0 without blocks, or -1.  No GPU needed."""
-    return fmfir_lib().rtlws_fmfir_samples_needed(int(decim), int(ntaps), int(block_len), int(nblocks))
-
-
-def fmfir_grid(decim, ntaps, nchannels, block_len, nblocks):
-    """rtlws_fmfir_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
-    b, t, s, a = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-    rc = fmfir_lib().rtlws_fmfir_grid(int(decim), int(ntaps), int(nchannels), int(block_len), int(nblocks), C.byref(b),
-                                      C.byref(t), C.byref(s), C.byref(a))
-    return rc, b.value, t.value, s.value, a.value
-
-
-def fmbank_last_error():
-    return fmbank_lib().rtlws_fmbank_last_error().decode()
-
-
-def fmbank_supported(cic_r, nchannels=1, block_len=20, nblocks=1):
-    return fmbank_lib().rtlws_fmbank_supported(int(cic_r), int(nchannels), int(block_len), int(nblocks))
-
-
-def fmbank_grid(cic_r, nchannels, block_len, nblocks):
-    """rtlws_fmbank_grid: (rc, workgroups, threads, LDS bytes, audio samples per tile).  No GPU needed."""
-    b, t, s, a = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    rc = fmbank_lib().rtlws_fmbank_grid(int(cic_r), int(nchannels), int(block_len), int(nblocks), C.byref(b), C.byref(t),
-                                        C.byref(s), C.byref(a))
-    return rc, b.value, t.value, s.value, a.value
-
-
 def host_error():
     """(count, first message) of include/rtlws_host.h's sticky failure record."""
     L = amd_lib()
@@ -1116,14 +937,6 @@ def host_error():
 
 def host_error_clear():
     amd_lib().rtlws_host_error_clear()
-
-
-def device_count():
-    return hip_lib().rtlws_device_count()
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 STREAM_ENGINE, STREAM_DEFAULT = None, 1     # include/rtlws_hip.h "Streams"
@@ -1233,10 +1046,6 @@ class LongPlan(_FramesPlan):
     """rtlws_long_plan* of include/rtlws_long.h: one descriptor, tables and workspace for up to max_frames frames
     per group.  eng may be None (as a C caller's NULL engine): open then fails with the library's text."""
     _name, _lib = "long", staticmethod(long_lib)
-
-
-def long_supported(desc):
-    return long_lib().rtlws_long_supported(C.byref(desc))
 
 
 class AnyLenPlan(_FramesPlan):
@@ -1583,15 +1392,6 @@ class PfbPlan(_PolyphasePlan):
                           int(lay), self._ptr(d_out), int(out_stride), stream)
 
 
-def anylen_supported(desc):
-    return anylen_lib().rtlws_anylen_supported(C.byref(desc))
-
-
-def anylen_conv_log2(desc):
-    """m of the convolution length 2^m the descriptor runs at, -1 if it is not served."""
-    return anylen_lib().rtlws_anylen_conv_log2(C.byref(desc))
-
-
 class Engine:
     """One engine per device (include/rtlws_hip.h). Fails loudly without a GPU."""
 
@@ -1619,8 +1419,12 @@ class Engine:
     def upload(self, arr, stream=None):
         arr = np.ascontiguousarray(arr)
         buf = DevBuf(self, arr.nbytes)
-        self._chk(hip_lib().rtlws_copy_h2d(self.h, buf.ptr, _p(arr), arr.nbytes, stream), "h2d")
-        self.sync(stream)
+        try:
+            self._chk(hip_lib().rtlws_copy_h2d(self.h, buf.ptr, _p(arr), arr.nbytes, stream), "h2d")
+            self.sync(stream)
+        except Exception:
+            buf.free()                                    # nobody else holds it yet
+            raise
         return buf
 
     def download(self, buf, dtype, shape, stream=None):
@@ -1716,10 +1520,83 @@ class Engine:
                                            stream), "rtlws_halfband")
 
     def grid(self, desc, nframes):
-        b, t, l = C.c_int(), C.c_int(), C.c_int()
-        rc = hip_lib().rtlws_spectra_grid(self.h, C.byref(desc), int(nframes), C.byref(b),
-                                          C.byref(t), C.byref(l))
-        return rc, b.value, t.value, l.value
+        return _outs(hip_lib().rtlws_spectra_grid, (self.h, C.byref(desc), int(nframes)), (C.c_int,) * 3)
+
+    # -- what the host-in, host-out drivers below share ----------------------
+    def _drive(self, plan, inputs, outputs, call):
+        """One run from host arrays to host arrays, and whatever raises, every device buffer freed and `plan` (None: no
+        plan) closed before it leaves.
+        inputs: host arrays, each uploaded once however often it is given (an empty one: a 16-byte stub), or None (no
+        buffer: a NULL pointer).  outputs: (dtype, shape), allocated and not initialised; or a preset host array,
+        uploaded; or None (no buffer, None comes back).  Then call(inputs' buffers, outputs' buffers), sync, and the
+        outputs downloaded -> their list; one of no bytes is not downloaded and comes back empty, or as it was preset.
+        A shape with a negative count is no work here (a stub): the refusal a caller sees is the library's own."""
+        made, by_id, d_out = [], {}, []
+
+        def nbytes(o):
+            if isinstance(o, np.ndarray):
+                return o.nbytes
+            count = np.dtype(o[0]).itemsize
+            for n in o[1]:
+                count *= max(int(n), 0)
+            return count
+
+        try:
+            for x in inputs:
+                if x is not None and id(x) not in by_id:
+                    made.append(self.upload(x) if x.nbytes else self.alloc(16))
+                    by_id[id(x)] = made[-1]
+            for o in outputs:
+                if o is not None:
+                    made.append(self.upload(o) if isinstance(o, np.ndarray) and o.nbytes else self.alloc(nbytes(o) or 16))
+                d_out.append(None if o is None else made[-1])
+            call([None if x is None else by_id[id(x)] for x in inputs], d_out)
+            self.sync()
+            got = []
+            for o, b in zip(outputs, d_out):
+                if o is None or not nbytes(o):
+                    got.append(o if o is None or isinstance(o, np.ndarray) else np.zeros(o[1], o[0]))
+                else:
+                    got.append(self.download(b, *((o.dtype, o.shape) if isinstance(o, np.ndarray) else o)))
+            return got
+        finally:
+            try:
+                if plan is not None:
+                    plan.close()
+            finally:
+                for b in made:
+                    b.free()
+
+    @staticmethod
+    def _frames_held(samples, t, m, hop):
+        """the frames of T * M samples, hop apart, that a capture of `samples` holds"""
+        return (samples - t * m) // hop + 1 if samples >= t * m and hop > 0 else 0
+
+    @staticmethod
+    def _captures(iqs, null=False):
+        """several captures as uint8 [nsamples, 2] each; an array given twice stays one array, so that _drive uploads it
+        once and its pointer is passed twice.  null: a None stays None (a NULL pointer among the captures); without it a
+        None is converted like an array, which raises numpy's TypeError"""
+        same = {id(x): np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 2) for x in iqs if not (null and x is None)}
+        return [same.get(id(x)) for x in iqs]
+
+    @staticmethod
+    def _preset(count, fill, guard, dtype=np.float32):
+        """a flat output of count elements preset to fill (None: zeros, and no guard), `guard` more behind them with a
+        fill: a float32's value for float32, its bits for the integer types, float64(fill) for float64"""
+        preset = np.float32(0.0 if fill is None else fill)
+        value = preset.view(dtype) if np.dtype(dtype).kind in "iu" else dtype(preset)
+        return np.full(count + (0 if fill is None else guard), value, dtype)
+
+    @staticmethod
+    def _rows(data, n_fft, k_avg, per_sample, output, f64_rows):
+        """spectra*: the frames of n_fft samples of per_sample bytes that data holds, all of it -> (data, nframes, the
+        rows as (dtype, shape))"""
+        data = np.ascontiguousarray(data)
+        nframes = data.nbytes // (per_sample * n_fft)
+        assert nframes * per_sample * n_fft == data.nbytes
+        dtype = np.uint8 if output == "payload_u8" else (np.float64 if f64_rows else np.float32)
+        return data, nframes, (dtype, (nframes // k_avg, n_fft))
 
     # -- include/rtlws_fm.h: host arrays in, (audio, new state[, decimated samples]) out ----
     def _fm_run(self, call, src, nsamples, block_len, state, run_stage2, want_dec):
@@ -1767,19 +1644,9 @@ class Engine:
         iq = np.ascontiguousarray(iq, dtype=np.uint8).reshape(-1, 2)
         dec_len = iq.shape[0] // cic_r if cic_r > 0 else 0
         assert cic_r <= 0 or dec_len * cic_r == iq.shape[0]
-        nch = len(tuning_words)
         plan = DdcPlan(self)
-        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
-        d_out = self.alloc(max(nch * dec_len, 1) * 8)
-        try:
-            plan.run(cic_r, d_iq, dec_len, tuning_words, d_out, dec_len, first_dec_index)
-            self.sync()
-            out = self.download(d_out, np.int32, (nch, dec_len, 2)) if nch * dec_len else np.zeros((nch, 0, 2), np.int32)
-        finally:
-            plan.close()
-            d_iq.free()
-            d_out.free()
-        return out
+        return self._drive(plan, [iq], [(np.int32, (len(tuning_words), dec_len, 2))], lambda i, o: plan.run(
+            cic_r, i[0], dec_len, tuning_words, o[0], dec_len, first_dec_index))[0]
 
     # -- include/rtlws_ddcfir.h: host arrays in, the filtered bank's streams out ----
     def ddcfir(self, iq, decim, taps, tuning_words, out_shift=14, first_dec_index=0, dec_len=None):
@@ -1791,18 +1658,8 @@ class Engine:
             dec_len = (iq.shape[0] - plan.ntaps) // plan.decim + 1 if iq.shape[0] >= plan.ntaps else 0
         need = ddcfir_samples_needed(plan.decim, plan.ntaps, dec_len)
         assert 0 <= need <= iq.shape[0]
-        nch = len(tuning_words)
-        d_iq = self.upload(iq[:need]) if need else self.alloc(16)
-        d_out = self.alloc(max(nch * dec_len, 1) * 8)
-        try:
-            plan.run(d_iq, dec_len, tuning_words, d_out, out_shift, dec_len, first_dec_index)
-            self.sync()
-            out = self.download(d_out, np.int32, (nch, dec_len, 2)) if nch * dec_len else np.zeros((nch, 0, 2), np.int32)
-        finally:
-            plan.close()
-            d_iq.free()
-            d_out.free()
-        return out
+        return self._drive(plan, [iq[:need]], [(np.int32, (len(tuning_words), dec_len, 2))], lambda i, o: plan.run(
+            i[0], dec_len, tuning_words, o[0], out_shift, dec_len, first_dec_index))[0]
 
     # -- include/rtlws_pfb.h: host arrays in, all channels out ----
     def pfb(self, iq, log2_channels, taps, hop=None, first_frame_index=0, layout="channel", nframes=None):
@@ -1813,21 +1670,12 @@ class Engine:
         m, t = 1 << plan.log2_channels, plan.taps_per_branch
         hop = m if hop is None else int(hop)
         if nframes is None:
-            nframes = (iq.shape[0] - t * m) // hop + 1 if iq.shape[0] >= t * m and hop > 0 else 0
+            nframes = self._frames_held(iq.shape[0], t, m, hop)
         need = pfb_samples_needed(plan.log2_channels, t, hop, nframes)
         assert need < 0 or iq.shape[0] >= need, "the capture is shorter than rtlws_pfb_samples_needed"
-        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
-        d_out = self.alloc(max(m * nframes, 1) * 8)
         shape = (nframes, m) if _PFB_LAYOUTS.get(layout, layout) == PFB_TIME_MAJOR else (m, nframes)
-        try:
-            plan.run(d_iq, nframes, d_out, hop, None, first_frame_index, layout)
-            self.sync()
-            out = self.download(d_out, np.complex64, shape) if nframes else np.zeros(shape, np.complex64)
-        finally:
-            plan.close()
-            d_iq.free()
-            d_out.free()
-        return out
+        return self._drive(plan, [iq], [(np.complex64, shape)], lambda i, o: plan.run(
+            i[0], nframes, o[0], hop, None, first_frame_index, layout))[0]
 
     # -- include/rtlws_pfbspec.h: host arrays in, one row per K frames out ----
     def pfbspec(self, iq, log2_channels, taps, k_avg, hop=None, output="power", shifted=False, scale=1.0, nspectra=None):
@@ -1839,22 +1687,12 @@ class Engine:
         m, t, k_avg = 1 << plan.log2_channels, plan.taps_per_branch, int(k_avg)
         hop = m if hop is None else int(hop)
         if nspectra is None:
-            nframes = (iq.shape[0] - t * m) // hop + 1 if iq.shape[0] >= t * m and hop > 0 else 0
-            nspectra = nframes // k_avg if k_avg > 0 else 0
+            nspectra = self._frames_held(iq.shape[0], t, m, hop) // k_avg if k_avg > 0 else 0
         need = pfbspec_samples_needed(plan.log2_channels, t, hop, k_avg, nspectra)
         assert need < 0 or iq.shape[0] >= need, "the capture is shorter than rtlws_pfbspec_samples_needed"
         dtype = np.uint8 if _PFBSPEC_OUTPUTS.get(output, output) == OUT_PAYLOAD_U8 else np.float32
-        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
-        d_out = self.alloc(max(m * nspectra, 1) * np.dtype(dtype).itemsize)
-        try:
-            plan.run(d_iq, nspectra, k_avg, d_out, hop, output, shifted, scale)
-            self.sync()
-            out = self.download(d_out, dtype, (nspectra, m)) if nspectra else np.zeros((nspectra, m), dtype)
-        finally:
-            plan.close()
-            d_iq.free()
-            d_out.free()
-        return out
+        return self._drive(plan, [iq], [(dtype, (nspectra, m))], lambda i, o: plan.run(
+            i[0], nspectra, k_avg, o[0], hop, output, shifted, scale))[0]
 
     # -- include/rtlws_pfbsk.h: host arrays in, (clean rows, kept counts[, S1 rows, S2 rows]) out ----
     def pfbsk(self, iq, log2_channels, taps, k_avg, nsub, ratio_lo=0.0, ratio_hi=float("inf"), power_scale=None, hop=None,
@@ -1870,27 +1708,14 @@ class Engine:
         if power_scale is None:
             power_scale = pfbsk_power_scale(plan.log2_channels, taps)
         if nspectra is None:
-            nframes = (iq.shape[0] - t * m) // hop + 1 if iq.shape[0] >= t * m and hop > 0 else 0
-            nspectra = nframes // (k_avg * nsub) if k_avg > 0 and nsub > 0 else 0
+            nspectra = self._frames_held(iq.shape[0], t, m, hop) // (k_avg * nsub) if k_avg > 0 and nsub > 0 else 0
         need = pfbsk_samples_needed(plan.log2_channels, t, hop, k_avg, nsub, nspectra)
         assert need < 0 or iq.shape[0] >= need, "the capture is shorter than rtlws_pfbsk_samples_needed"
         dtype = np.uint8 if _PFBSPEC_OUTPUTS.get(output, output) == OUT_PAYLOAD_U8 else np.float32
-        nsubs = nspectra * max(nsub, 0)
-        bufs = [self.upload(iq) if iq.nbytes else self.alloc(16), self.alloc(max(m * nspectra, 1) * np.dtype(dtype).itemsize),
-                self.alloc(max(m * nspectra, 1) * 4)]
-        if sub_rows:
-            bufs += [self.alloc(max(m * nsubs, 1) * 4), self.alloc(max(m * nsubs, 1) * 4)]
-        try:
-            plan.run(bufs[0], nspectra, k_avg, nsub, power_scale, bufs[1], ratio_lo, ratio_hi, bufs[2], *bufs[3:], hop=hop,
-                     output=output, shifted=shifted, scale=scale)
-            self.sync()
-            shapes = [(dtype, (nspectra, m)), (np.uint32, (nspectra, m))] + [(np.float32, (nsubs, m))] * (len(bufs) - 3)
-            out = tuple(self.download(b, dt, sh) if sh[0] else np.zeros(sh, dt) for b, (dt, sh) in zip(bufs[1:], shapes))
-        finally:
-            plan.close()
-            for b in bufs:
-                b.free()
-        return out
+        shapes = [(dtype, (nspectra, m)), (np.uint32, (nspectra, m))] + [(np.float32, (nspectra * max(nsub, 0), m))] * (2 if sub_rows else 0)
+        return tuple(self._drive(plan, [iq], shapes, lambda i, o: plan.run(
+            i[0], nspectra, k_avg, nsub, power_scale, o[0], ratio_lo, ratio_hi, *o[1:], hop=hop, output=output, shifted=shifted,
+            scale=scale)))
 
     # -- include/rtlws_dedisp.h: host rows in, one time series per trial out ----
     def dedisp(self, rows, delays, mask=None, nout=None, in_stride=None, out_stride=None, fill=None):
@@ -1907,16 +1732,7 @@ class Engine:
         assert rows.shape[0] >= plan.rows_needed(nout), "fewer rows than rtlws_dedisp_rows_needed"
         stride = nout if out_stride is None else int(out_stride)
         host = np.full((plan.ntrials, max(stride, 0)), 0.0 if fill is None else fill, np.float32)
-        d_rows = self.upload(rows) if rows.nbytes else self.alloc(16)
-        d_out = self.upload(host) if host.nbytes else self.alloc(16)
-        try:
-            plan.run(d_rows, nout, d_out, width, stride)
-            self.sync()
-            out = self.download(d_out, np.float32, host.shape) if host.nbytes else host
-        finally:
-            plan.close()
-            d_rows.free()
-            d_out.free()
+        out, = self._drive(plan, [rows], [host], lambda i, o: plan.run(i[0], nout, o[0], width, stride))
         return out if out_stride is not None else out[:, :nout]
 
     # -- what the searches over series share: the shaped, padded series; the preset buffers, the run and the download ----
@@ -1940,22 +1756,13 @@ class Engine:
         four whole flat buffers, PERIOD_GUARD elements longer than the outputs, every element preset to fill."""
         ntrials, width = series.shape
         nv = int(np.prod(lead_shape))
-        guard = 0 if fill is None else PERIOD_GUARD
-        preset = np.float32(0.0 if fill is None else fill)
         npeaks, nrows = nv * plan.levels * plan.nseg, nv * plan.nbins
-        hosts = [np.full(npeaks + guard, preset, np.float32), np.full(npeaks + guard, preset.view(np.int32), np.int32),
-                 np.full((nrows if want_power or fill is not None else 0) + guard, preset, np.float32),
-                 np.full((nrows if want_white or fill is not None else 0) + guard, preset, np.float32)]
-        bufs = [self.upload(series)] + [self.upload(h) if h.size else None for h in hosts]
-        try:
-            call(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2], bufs[3] if want_power else None, bufs[4] if want_white else None)
-            self.sync()
-            best, at, power, white = [h if b is None else self.download(b, h.dtype, h.shape) for b, h in zip(bufs[1:], hosts)]
-        finally:
-            plan.close()
-            for b in bufs:
-                if b is not None:
-                    b.free()
+        hosts = [self._preset(npeaks, fill, PERIOD_GUARD), self._preset(npeaks, fill, PERIOD_GUARD, np.int32),
+                 self._preset(nrows if want_power or fill is not None else 0, fill, PERIOD_GUARD),
+                 self._preset(nrows if want_white or fill is not None else 0, fill, PERIOD_GUARD)]
+        got = self._drive(plan, [series], [h if h.size else None for h in hosts], lambda i, o: call(
+            i[0], width, ntrials, nsamp, o[0], o[1], o[2] if want_power else None, o[3] if want_white else None))
+        best, at, power, white = [h if g is None else g for g, h in zip(got, hosts)]
         if fill is not None:
             return best, at, power, white
         shape = tuple(lead_shape) + (plan.levels, plan.nseg)
@@ -1978,20 +1785,12 @@ class Engine:
             nout = max(samples - (plan.samples_needed(1) - 1), 0)
         nout = int(nout)
         assert samples >= plan.samples_needed(nout), "fewer samples than rtlws_pulse_samples_needed"
-        nseg, guard = plan.segments(nout), 0 if fill is None else PULSE_GUARD
-        preset = np.float32(0.0 if fill is None else fill)
-        hosts = [np.full(ntrials * plan.nwidths * nseg + guard, preset, np.float32),
-                 np.full(ntrials * plan.nwidths * nseg + guard, preset.view(np.int32), np.int32),
-                 np.full(ntrials * nseg * 2 + guard, np.float64(preset), np.float64)]
-        bufs = [self.upload(series) if series.nbytes else self.alloc(16)] + [self.upload(h) if h.nbytes else self.alloc(16) for h in hosts]
-        try:
-            plan.run(bufs[0], width, ntrials, nout, bufs[1], bufs[2], bufs[3] if want_moments else None)
-            self.sync()
-            peak, at, mom = [self.download(b, h.dtype, h.shape) if h.nbytes else h for b, h in zip(bufs[1:], hosts)]
-        finally:
-            plan.close()
-            for b in bufs:
-                b.free()
+        nseg = plan.segments(nout)
+        hosts = [self._preset(ntrials * plan.nwidths * nseg, fill, PULSE_GUARD),
+                 self._preset(ntrials * plan.nwidths * nseg, fill, PULSE_GUARD, np.int32),
+                 self._preset(ntrials * nseg * 2, fill, PULSE_GUARD, np.float64)]
+        peak, at, mom = self._drive(plan, [series], hosts, lambda i, o: plan.run(
+            i[0], width, ntrials, nout, o[0], o[1], o[2] if want_moments else None))
         if fill is not None:
             return peak, at, mom
         return (peak.reshape(ntrials, plan.nwidths, nseg), at.reshape(ntrials, plan.nwidths, nseg),
@@ -2010,19 +1809,11 @@ class Engine:
         ntrials, width = series.shape
         nsamp = samples if nsamp is None else int(nsamp)
         assert samples >= nsamp, "fewer samples than nsamp"
-        nsub, guard = plan.subints(nsamp), 0 if fill is None else FOLD_GUARD
-        preset = np.float32(0.0 if fill is None else fill)
-        hosts = [np.full(ntrials * plan.nperiods * nsub * plan.nbins + guard, preset, np.float32),
-                 np.full(plan.nperiods * nsub * plan.nbins + guard, preset.view(np.uint32), np.uint32)]
-        bufs = [self.upload(series) if series.nbytes else self.alloc(16)] + [self.upload(h) if h.nbytes else self.alloc(16) for h in hosts]
-        try:
-            plan.run(bufs[0], width, ntrials, nsamp, bufs[1], bufs[2] if want_hits else None)
-            self.sync()
-            prof, hits = [self.download(b, h.dtype, h.shape) if h.nbytes else h for b, h in zip(bufs[1:], hosts)]
-        finally:
-            plan.close()
-            for b in bufs:
-                b.free()
+        nsub = plan.subints(nsamp)
+        hosts = [self._preset(ntrials * plan.nperiods * nsub * plan.nbins, fill, FOLD_GUARD),
+                 self._preset(plan.nperiods * nsub * plan.nbins, fill, FOLD_GUARD, np.uint32)]
+        prof, hits = self._drive(plan, [series], hosts, lambda i, o: plan.run(
+            i[0], width, ntrials, nsamp, o[0], o[1] if want_hits else None))
         if fill is not None:
             return prof, hits
         return (prof.reshape(ntrials, plan.nperiods, nsub, plan.nbins),
@@ -2086,15 +1877,8 @@ class Engine:
         out_stride = (nsamp + 3) // 4 * 4 if out_stride is None else int(out_stride)
         plan = AccelPlan(self, log2n, 1, PERIODLONG_MIN_NORM, PERIODLONG_MIN_SEG, 1, coefs)
         host = np.full(ntrials * a_count * out_stride + PERIOD_GUARD, np.float32(0.0 if fill is None else fill), np.float32)
-        bufs = [self.upload(series), self.upload(host)]
-        try:
-            plan.resample(bufs[0], width, ntrials, nsamp, a_first, a_count, bufs[1], out_stride)
-            self.sync()
-            out = self.download(bufs[1], np.float32, host.shape)
-        finally:
-            plan.close()
-            for b in bufs:
-                b.free()
+        out, = self._drive(plan, [series], [host], lambda i, o: plan.resample(
+            i[0], width, ntrials, nsamp, a_first, a_count, o[0], out_stride))
         if fill is not None:
             return out
         return out[:ntrials * a_count * out_stride].reshape(ntrials, a_count, out_stride)[:, :, :nsamp]
@@ -2105,8 +1889,7 @@ class Engine:
         (one array may be given twice: it is uploaded once and its pointer passed twice), taps int16 [T * M] ->
         (float32 [nspectra, A, M], the K-frame powers; complex64 [nspectra, A (A - 1) / 2, M], the K-frame
         cross-spectra of the pairs a < b row-major).  nspectra None: as many as the shortest capture holds."""
-        same = {id(x): np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 2) for x in iqs if x is not None}
-        iqs = [x if x is None else same[id(x)] for x in iqs]
+        iqs = self._captures(iqs, null=True)
         a = len(iqs)
         plan = PfbXcPlan(self, log2_channels, taps, a)
         nx = a * (a - 1) // 2
@@ -2114,94 +1897,49 @@ class Engine:
         hop = m if hop is None else int(hop)
         shortest = min(x.shape[0] for x in iqs if x is not None)
         if nspectra is None:
-            nframes = (shortest - t * m) // hop + 1 if shortest >= t * m and hop > 0 else 0
-            nspectra = nframes // k_avg if k_avg > 0 else 0
+            nspectra = self._frames_held(shortest, t, m, hop) // k_avg if k_avg > 0 else 0
         need = pfbxc_samples_needed(plan.log2_channels, t, hop, k_avg, nspectra)
         assert need < 0 or shortest >= need, "a capture is shorter than rtlws_pfbxc_samples_needed"
-        bufs = {}
-        for x in iqs:
-            if x is not None and id(x) not in bufs:
-                bufs[id(x)] = self.upload(x) if x.nbytes else self.alloc(16)
-        d_auto = self.alloc(max(nspectra * a * m, 1) * 4)
-        d_cross = self.alloc(max(nspectra * nx * m, 1) * 8)
-        try:
-            plan.run([None if x is None else bufs[id(x)] for x in iqs], nspectra, k_avg, d_auto, d_cross, hop, shifted)
-            self.sync()
-            if nspectra:
-                autos = self.download(d_auto, np.float32, (nspectra, a, m))
-                cross = self.download(d_cross, np.complex64, (nspectra, nx, m))
-            else:
-                autos, cross = np.zeros((0, a, m), np.float32), np.zeros((0, nx, m), np.complex64)
-        finally:
-            plan.close()
-            for b in bufs.values():
-                b.free()
-            d_auto.free()
-            d_cross.free()
+        autos, cross = self._drive(plan, iqs, [(np.float32, (nspectra, a, m)), (np.complex64, (nspectra, nx, m))],
+                                   lambda i, o: plan.run(i, nspectra, k_avg, o[0], o[1], hop, shifted))
         return autos, cross
 
     # -- include/rtlws_pfbbf.h: host arrays in, the beams out ----
     def _pfbbf_inputs(self, iqs, weights, log2_channels, taps):
-        """-> (plan, captures, device buffers by id, the weights' buffer); one array given twice is uploaded once"""
-        same = {id(x): np.ascontiguousarray(x, dtype=np.uint8).reshape(-1, 2) for x in iqs}
-        iqs = [same[id(x)] for x in iqs]
-        m = 1 << int(log2_channels)
+        """-> (plan, the captures, the weights complex64 [B, A, M], the shortest capture's samples)"""
+        iqs = self._captures(iqs)
         weights = np.ascontiguousarray(weights, dtype=np.complex64)
-        assert weights.ndim == 3 and weights.shape[1:] == (len(iqs), m), "the weights are [B, A, M]"
-        plan = PfbBfPlan(self, log2_channels, taps, len(iqs), weights.shape[0])
-        bufs = {}
-        for x in iqs:
-            if id(x) not in bufs:
-                bufs[id(x)] = self.upload(x) if x.nbytes else self.alloc(16)
-        return plan, iqs, bufs, self.upload(weights)
+        assert weights.ndim == 3 and weights.shape[1:] == (len(iqs), 1 << int(log2_channels)), "the weights are [B, A, M]"
+        return PfbBfPlan(self, log2_channels, taps, len(iqs), weights.shape[0]), iqs, weights, min(x.shape[0] for x in iqs)
 
     def pfbbf(self, iqs, weights, log2_channels, taps, hop=None, first_frame_index=0, layout="channel", nframes=None):
         """rtlws_pfbbf_run: iqs a sequence of A = 1 .. 8 captures, each uint8 [(nframes - 1) * hop + T * M, 2], weights
         complex64 [B, A, M], taps int16 [T * M] -> complex64 [B, M, nframes] (layout "channel") or [B, nframes, M]
         ("time").  nframes None: as many as the shortest capture holds."""
-        plan, iqs, bufs, d_w = self._pfbbf_inputs(iqs, weights, log2_channels, taps)
+        plan, iqs, weights, shortest = self._pfbbf_inputs(iqs, weights, log2_channels, taps)
         m, t, nb = 1 << plan.log2_channels, plan.taps_per_branch, plan.nbeams
         hop = m if hop is None else int(hop)
-        shortest = min(x.shape[0] for x in iqs)
         if nframes is None:
-            nframes = (shortest - t * m) // hop + 1 if shortest >= t * m and hop > 0 else 0
+            nframes = self._frames_held(shortest, t, m, hop)
         need = pfbbf_samples_needed(plan.log2_channels, t, hop, 0, nframes)
         assert need < 0 or shortest >= need, "a capture is shorter than rtlws_pfbbf_samples_needed"
-        d_out = self.alloc(max(nb * m * nframes, 1) * 8)
         shape = (nb, nframes, m) if _PFB_LAYOUTS.get(layout, layout) == PFB_TIME_MAJOR else (nb, m, nframes)
-        try:
-            plan.run([bufs[id(x)] for x in iqs], d_w, nframes, d_out, hop, None, None, first_frame_index, layout)
-            self.sync()
-            out = self.download(d_out, np.complex64, shape) if nframes else np.zeros(shape, np.complex64)
-        finally:
-            plan.close()
-            for b in list(bufs.values()) + [d_w, d_out]:
-                b.free()
-        return out
+        return self._drive(plan, iqs + [weights], [(np.complex64, shape)], lambda i, o: plan.run(
+            i[:-1], i[-1], nframes, o[0], hop, None, None, first_frame_index, layout))[0]
 
     def pfbbf_power(self, iqs, weights, log2_channels, taps, k_avg, hop=None, shifted=False, nspectra=None):
         """rtlws_pfbbf_power: the captures and weights of pfbbf, each capture uint8 [(nspectra * k_avg - 1) * hop +
         T * M, 2] -> float32 [nspectra, B, M], the K-frame powers of the beams.  nspectra None: as many as the shortest
         capture holds."""
-        plan, iqs, bufs, d_w = self._pfbbf_inputs(iqs, weights, log2_channels, taps)
+        plan, iqs, weights, shortest = self._pfbbf_inputs(iqs, weights, log2_channels, taps)
         m, t, nb, k_avg = 1 << plan.log2_channels, plan.taps_per_branch, plan.nbeams, int(k_avg)
         hop = m if hop is None else int(hop)
-        shortest = min(x.shape[0] for x in iqs)
         if nspectra is None:
-            nframes = (shortest - t * m) // hop + 1 if shortest >= t * m and hop > 0 else 0
-            nspectra = nframes // k_avg if k_avg > 0 else 0
+            nspectra = self._frames_held(shortest, t, m, hop) // k_avg if k_avg > 0 else 0
         need = pfbbf_samples_needed(plan.log2_channels, t, hop, k_avg, nspectra) if k_avg > 0 else -1
         assert need < 0 or shortest >= need, "a capture is shorter than rtlws_pfbbf_samples_needed"
-        d_out = self.alloc(max(nspectra * nb * m, 1) * 4)
-        try:
-            plan.power([bufs[id(x)] for x in iqs], d_w, nspectra, k_avg, d_out, hop, shifted)
-            self.sync()
-            out = self.download(d_out, np.float32, (nspectra, nb, m)) if nspectra else np.zeros((0, nb, m), np.float32)
-        finally:
-            plan.close()
-            for b in list(bufs.values()) + [d_w, d_out]:
-                b.free()
-        return out
+        return self._drive(plan, iqs + [weights], [(np.float32, (nspectra, nb, m))], lambda i, o: plan.power(
+            i[:-1], i[-1], nspectra, k_avg, o[0], hop, shifted))[0]
 
     # -- include/rtlws_fmbank.h: host arrays in, (audio, new states) out ----
     def fm_bank(self, iq, cic_r, tuning_words, block_len, states, first_dec_index=0):
@@ -2215,19 +1953,8 @@ class Engine:
         assert per_block <= 0 or nblocks * per_block == iq.shape[0]
         n = max(nblocks * (int(block_len) // 4), 0)
         plan = FmBankPlan(self)
-        d_iq = self.upload(iq) if iq.nbytes else self.alloc(16)
-        d_in = self.upload(states)
-        d_out = self.alloc(states.nbytes)
-        d_audio = self.alloc(max(nch * n, 1) * 4)
-        try:
-            plan.run(cic_r, d_iq, block_len, nblocks, tuning_words, d_in, d_out, d_audio, n, first_dec_index)
-            self.sync()
-            audio = self.download(d_audio, np.float32, (nch, n)) if nch * n else np.zeros((nch, 0), np.float32)
-            new_states = self.download(d_out, np.float32, (nch, FM_STATE_FLOATS))
-        finally:
-            plan.close()
-            for b in (d_iq, d_in, d_out, d_audio):
-                b.free()
+        new_states, audio = self._drive(plan, [iq, states], [(np.float32, states.shape), (np.float32, (nch, n))], lambda i, o: plan.run(
+            cic_r, i[0], block_len, nblocks, tuning_words, i[1], o[0], o[1], n, first_dec_index))
         return audio, new_states
 
     # -- include/rtlws_fmfir.h: host arrays in, (audio, new states) out ----
@@ -2244,19 +1971,8 @@ class Engine:
         need = fmfir_samples_needed(plan.decim, plan.ntaps, block_len, nblocks)
         assert 0 <= need <= iq.shape[0]
         n = max(int(nblocks) * (int(block_len) // 4), 0)
-        d_iq = self.upload(iq[:need]) if need else self.alloc(16)
-        d_in = self.upload(states)
-        d_out = self.alloc(states.nbytes)
-        d_audio = self.alloc(max(nch * n, 1) * 4)
-        try:
-            plan.run(d_iq, block_len, nblocks, tuning_words, d_in, d_out, d_audio, out_shift, n, first_dec_index)
-            self.sync()
-            audio = self.download(d_audio, np.float32, (nch, n)) if nch * n else np.zeros((nch, 0), np.float32)
-            new_states = self.download(d_out, np.float32, (nch, FM_STATE_FLOATS))
-        finally:
-            plan.close()
-            for b in (d_iq, d_in, d_out, d_audio):
-                b.free()
+        new_states, audio = self._drive(plan, [iq[:need], states], [(np.float32, states.shape), (np.float32, (nch, n))], lambda i, o: plan.run(
+            i[0], block_len, nblocks, tuning_words, i[1], o[0], o[1], out_shift, n, first_dec_index))
         return audio, new_states
 
     # -- convenience: host arrays in, host arrays out ------------------------
@@ -2266,20 +1982,15 @@ class Engine:
         rows_f32=True: the same arithmetic with rows rounded once to f32, RTLWS_FLAG_ROWS_F32)."""
         desc = make_desc(n_fft, k_avg, input, window, output, cic_r, gain_db,
                          FLAG_ROWS_F32 if (f64 and rows_f32) else 0)
-        data = np.ascontiguousarray(data)
-        per_sample = {"cu8": 2, "cs32": 8, "rf32": 4}[input] * max(int(cic_r), 1)
-        nframes = data.nbytes // (per_sample * n_fft)
-        assert nframes * per_sample * n_fft == data.nbytes
-        rows = nframes // k_avg
-        out_dtype = np.uint8 if output == "payload_u8" else (np.float64 if (f64 and not rows_f32) else np.float32)
-        d_in = self.upload(data)
-        d_out = self.alloc(rows * n_fft * np.dtype(out_dtype).itemsize)
-        (self.spectra_batch_f64 if f64 else self.spectra_batch)(desc, d_in, nframes, d_out)
-        res = self.download(d_out, out_dtype, (rows, n_fft))
-        d_in.free()
-        d_out.free()
-        return res
+        data, nframes, rows = self._rows(data, n_fft, k_avg, _SAMPLE_BYTES[input] * max(int(cic_r), 1), output, f64 and not rows_f32)
+        batch = self.spectra_batch_f64 if f64 else self.spectra_batch
+        return self._drive(None, [data], [rows], lambda i, o: batch(desc, i[0], nframes, o[0]))[0]
 
+    def _spectra_plan(self, cls, desc, data, input, output, max_frames):
+        """spectra_long and spectra_anylen: the plan of `cls` for the frames data holds, run over all of them"""
+        data, nframes, rows = self._rows(data, desc.n_fft, desc.k_avg, _SAMPLE_BYTES[input], output, not desc.flags & FLAG_ROWS_F32)
+        plan = cls(self, desc, nframes if max_frames is None else max_frames)
+        return self._drive(plan, [data], [rows], lambda i, o: plan.run(i[0], nframes, o[0]))[0]
 
     def spectra_long(self, data, n_fft, k_avg=1, input="cu8", output="power_sum", gain_db=0, rows_f32=False,
                      max_frames=None):
@@ -2287,46 +1998,14 @@ class Engine:
         (rows_f32=True: the same arithmetic, rows rounded once to f32).  max_frames: the plan's group size
         (default: the whole batch)."""
         desc = make_desc(n_fft, k_avg, input, "rect", output, 0, gain_db, FLAG_ROWS_F32 if rows_f32 else 0)
-        data = np.ascontiguousarray(data)
-        per_sample = {"cu8": 2, "cs32": 8, "rf32": 4}[input]
-        nframes = data.nbytes // (per_sample * n_fft)
-        assert nframes * per_sample * n_fft == data.nbytes
-        rows = nframes // k_avg
-        out_dtype = np.uint8 if output == "payload_u8" else (np.float32 if rows_f32 else np.float64)
-        plan = LongPlan(self, desc, nframes if max_frames is None else max_frames)
-        d_in = self.upload(data)
-        d_out = self.alloc(max(rows, 1) * n_fft * np.dtype(out_dtype).itemsize)
-        try:
-            plan.run(d_in, nframes, d_out)
-            res = self.download(d_out, out_dtype, (rows, n_fft))
-        finally:
-            plan.close()
-            d_in.free()
-            d_out.free()
-        return res
+        return self._spectra_plan(LongPlan, desc, data, input, output, max_frames)
 
     def spectra_anylen(self, data, n_fft, k_avg=1, input="cu8", output="power_sum", gain_db=0, rows_f32=False,
                        max_frames=None):
         """Engine.spectra_long for any frame length 2 .. 2^19 (include/rtlws_anylen.h).  The device buffers are
         exactly as long as the frames and the rows: nothing lies behind the last frame."""
         desc = make_desc(n_fft, k_avg, input, "rect", output, 0, gain_db, FLAG_ROWS_F32 if rows_f32 else 0)
-        data = np.ascontiguousarray(data)
-        per_sample = {"cu8": 2, "cs32": 8, "rf32": 4}[input]
-        nframes = data.nbytes // (per_sample * n_fft)
-        assert nframes * per_sample * n_fft == data.nbytes
-        rows = nframes // k_avg
-        out_dtype = np.uint8 if output == "payload_u8" else (np.float32 if rows_f32 else np.float64)
-        plan = AnyLenPlan(self, desc, nframes if max_frames is None else max_frames)
-        d_in = self.upload(data)
-        d_out = self.alloc(max(rows, 1) * n_fft * np.dtype(out_dtype).itemsize)
-        try:
-            plan.run(d_in, nframes, d_out)
-            res = self.download(d_out, out_dtype, (rows, n_fft))
-        finally:
-            plan.close()
-            d_in.free()
-            d_out.free()
-        return res
+        return self._spectra_plan(AnyLenPlan, desc, data, input, output, max_frames)
 
 
 # ---- drop-in API (librtlws_amd.so) -----------------------------------------
