@@ -975,10 +975,11 @@ class DevBuf:
             pass
 
 
-class _Plan:
+class _PlanBase:
     """What every satellite library's plan shares: the library (_name, _lib), the handle h of rtlws_<name>_open, the
     calls through it, close.  eng may be None (as a C caller's NULL engine): open then fails with the library's text.
-    A subclass names its library, hands _open what its open takes behind the engine, and keeps its run signatures."""
+    A subclass names its library, hands _open what its open takes behind the engine, and keeps its run signatures.
+    The plans of this module derive from _Plan below; a library's submodule derives from this."""
     _name, _lib, h = None, None, None
 
     def _open(self, eng, *args):
@@ -1020,6 +1021,10 @@ class _Plan:
             self.close()
         except Exception:
             pass
+
+
+class _Plan(_PlanBase):
+    """The plans of the libraries this module binds (tests/test_python_api_cpu.py pins its subclasses)."""
 
 
 def _words(tuning_words):
