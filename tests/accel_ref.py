@@ -13,6 +13,7 @@ MAX_NACCEL, MAX_COEF, MAX_VIRTUAL, STAGES = 1024, 1 << 40, 65536, 6
 MAX_NSAMP = 1 << 22
 LIGHT = 299792458                                # m / s
 bound = periodlong_ref.bound
+bound_bin = periodlong_ref.bound_bin             # per bin too: the map only copies samples
 _LIMB = 22                                       # n, L - n < 2^22; |c| <= 2^40 in two limbs of 22 bits
 
 

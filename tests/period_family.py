@@ -54,10 +54,18 @@ def check_bare(bare, best, at, name=None):
     assert np.array_equal(bare[1][:at.size].reshape(at.shape), at), (name, "at without rows")
 
 
-def check_stage1(power, x, nsamp, c, reference, worst_of, key, name, finite=None):
+def check_bins(power_row, xs, ref, b1, name):
+    """every bin of one trial within period_ref.bound_bin's allowance of the f64 spectrum `ref` -> the worst share"""
+    share, k = period_ref.bin_share(power_row, xs, ref, b1)
+    assert share <= 1.0, (name, "bin", k, share, float(power_row[k]), float(ref[k]))
+    return share
+
+
+def check_stage1(power, x, nsamp, c, b1, reference, worst_of, worst_bin_of, key, name, finite=None):
     """per trial sum |P^ - P| <= c sum P against reference(trial's samples, name) -> the f64 spectrum (which asserts the
-    premises of the bound itself); the worst share of the bound goes into worst_of[key] and comes back"""
-    worst = 0.0
+    premises of that bound itself), and every bin within bound_bin's allowance (b1; no premise); the worst shares of the two
+    bounds go into worst_of[key] and worst_bin_of[key], the aggregate one comes back"""
+    worst, worst_bin = 0.0, 0.0
     for t in range(x.shape[0]):
         if finite is not None and not finite[t]:
             continue
@@ -66,7 +74,9 @@ def check_stage1(power, x, nsamp, c, reference, worst_of, key, name, finite=None
         assert err <= c * ref.sum(), (name, t, err, c * ref.sum())
         if ref.sum() > 0:
             worst = max(worst, err / (c * ref.sum()))
+        worst_bin = max(worst_bin, check_bins(power[t], x[t, :nsamp], ref, b1, (name, t)))
     worst_of[key] = max(worst_of.get(key, 0.0), worst)
+    worst_bin_of[key] = max(worst_bin_of.get(key, 0.0), worst_bin)
     return worst
 
 

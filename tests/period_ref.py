@@ -58,6 +58,59 @@ def bound(log2n):
     return 2.0 * beta + beta * beta + gamma(3) * (1.0 + beta) ** 2
 
 
+def path_bound(b_fft):
+    """b1 of bound_bin from the transform's per-term error b_fft: |X^[k] - X[k]| <= b1 ||y||_1"""
+    gamma3 = 3.0 * U / (1.0 - 3.0 * U)
+    b_u = 3.0 * U + U + math.sqrt(2.0) * gamma3
+    b_path = math.sqrt(2.0) * b_fft + 2.0 * b_u * (1.0 + b_fft)
+    b_y = U + 2.0 ** -52                         # y = fl32(fl64(x - mu^)): relative to y itself
+    return b_y + b_path * (1.0 + b_y)
+
+
+def bound_bin(log2n):
+    """b1(log2n): for EVERY bin k < M, with no premise on the series,
+        | |X^[k]| - |X[k]| |  <=  A + gamma_3 (|X[k]| + A) + 2^-62,    A = b1 ||y||_1 + (1 + b1) mean_term(x),
+    |X^[k]| = sqrt(P^[k]), derived per term of X[k] = sum_n y[n] w^(n k) from bound()'s constants:
+      input   y^[n] = (y[n] + mu - mu^)(1 + d), |d| <= b_y = u + 2^-52; the mean's error is mean_term's, no premise
+      FFT     every path from a point to a bin passes t = log2 M radix-2 stages' worth of roundings and once-rounded
+              roots, (1 + eta) each: (1 + theta), |theta| <= b_fft = t eta / (1 - t eta), so |dZ[k]| <= b_fft ||z||_1
+              and ||z||_1 <= ||y||_1.  The radix-16 passes spend 13.9 u of their 4 eta = 26.6 u, with the register
+              butterflies' roots made as cos (1 + i tan) from two rounded literals (error 2 u, not u) counted
+      untangling  X[k] = Z[k] (1 - i W) / 2 + conj Z[M - k] (1 + i W) / 2, |1 - i W| / 2 + |1 + i W| / 2 <= sqrt 2: the map
+              takes the two |dZ| to sqrt 2 b_fft ||y||_1; its own roundings b_u (|E| + |O|) <= 2 b_u (1 + b_fft) ||y||_1
+      so b_path = sqrt 2 b_fft + 2 b_u (1 + b_fft), b1 = b_y + b_path (1 + b_y)
+      the square's three roundings: sqrt(P^) within gamma_3 of |X^|; 2^-62 is the square root of f32's underflow."""
+    t = log2n - 1
+    eta = U + 4.0 * U / (1.0 - 4.0 * U) * (math.sqrt(2.0) + U)
+    return path_bound(t * eta / (1.0 - t * eta))
+
+
+def mean_term(x):
+    """sum_n |mu^ - mu| over the series: the f64 sum of nsamp samples in any order, one division: at most
+    gamma64_(nsamp + 1) sum |x| (what bound() takes as a premise, computed from x)"""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    g = (x.size + 1) * 2.0 ** -53
+    return g / (1.0 - g) * float(np.abs(x).sum())
+
+
+def bin_allowance(x, ref_power, b1):
+    """the right side of bound_bin for one series x (float32 [nsamp]) and its f64 spectrum -> float64 [M]"""
+    x64 = np.asarray(x, np.float32).astype(np.float64)
+    a = b1 * float(np.abs(x64 - x64.mean()).sum()) + (1.0 + b1) * mean_term(x)
+    gamma3 = 3.0 * U / (1.0 - 3.0 * U)
+    return a + gamma3 * (np.sqrt(ref_power) + a) + 2.0 ** -62
+
+
+def bin_share(power_row, x, ref_power, b1):
+    """(the worst | |X^| - |X| | over the bins as a share of bin_allowance, its bin)"""
+    err = np.abs(np.sqrt(np.asarray(power_row, np.float64)) - np.sqrt(ref_power))
+    allow = bin_allowance(x, ref_power, b1)
+    share = err / allow                                          # the allowance is at least 2^-62
+    share = np.where(np.isnan(share), np.inf, share)             # a NaN in the row is never within
+    k = int(share.argmax())
+    return float(share[k]), k
+
+
 def tree_sums(p, norm, pairs_first=True):
     """the block sums of float32 [.., M], flat over the leading axes: the balanced halving tree, adjacent pairs first (pairs_first False: the other
     balanced tree, halves first -- test_period_cpu's check that the order is not idle)"""

@@ -5,6 +5,8 @@ import math
 
 import numpy as np
 
+import period_ref
+
 MIN_LOG2N, MAX_LOG2N, MAX_LEVELS, MIN_NORM, MAX_NORM, MIN_SEG, MAX_SEG, MAX_TRIALS = 16, 22, 5, 16, 16384, 64, 16384, 65536
 STAGES = 6                                       # mean, columns, rows, untangling, whitening, peaks
 WORKSPACE_CAP = 1 << 30
@@ -71,6 +73,19 @@ def bound(log2n):
     b_u = 3.0 * U + mu + math.sqrt(2.0) * gamma(3)
     beta = math.sqrt(3.0) * (b_z + b_u * (1.0 + b_z))
     return 2.0 * beta + beta * beta + gamma(3) * (1.0 + beta) ** 2
+
+
+def bound_bin(log2n):
+    """b1(log2n) of period_ref.bound_bin for the four-step transform: the same per-term route with
+    bound()'s b_fft, the twist one more once-rounded root on every path, (1 + eta)^t (1 + tau) - 1 <= s / (1 - s), s = t eta
+    + tau; the 256-point columns' inner roots tw256[a q] stand for one of their eight stages' roots.  The assertion, the
+    mean's term and the square's are period_ref.bin_allowance's: no premise on the Nyquist bin or on the mean."""
+    t = log2n - 1
+    gamma = lambda n: n * U / (1.0 - n * U)
+    eta = U + gamma(4) * (math.sqrt(2.0) + U)
+    tau = U + math.sqrt(2.0) * gamma(3)
+    s = t * eta + tau
+    return period_ref.path_bound(s / (1.0 - s))
 
 
 def split(log2n):

@@ -14,7 +14,11 @@ scene of DESIGN.md 4.24 with the chain dedispersion -> search -> resampling of t
 The scene as first worded has nine coefficients (a - 2) * coef_from_shift(10, 60 000), a = 0 .. 8; the ninth,
 1 229 823 932 034, is above the library's limit 2^40 = 1 099 511 627 776 (at 60 000 samples 2^40 is a mid-frame shift of
 53.6 samples) and rtlws_accel_supported refuses the table.  The scene here keeps a = 0 .. 7, the matched one a = 6 among
-them; test_the_scene asserts the refusal of the ninth."""
+them; test_the_scene asserts the refusal of the ninth.
+
+Every virtual trial's every bin is held to accel_ref.bound_bin as well (period_family.check_stage1).  Worst per-bin share
+of `bound_bin`, measured on one MI355X (printed by test_the_longer_frames): 0.0011, 0.0030, 0.0029 at log2n 19, 20, 22
+(dense noise: ||y||_1 is large; tests/test_period_bins_gpu.py has the sparse series, 0.0199 at log2n 16)."""
 import numpy as np
 import pytest
 
@@ -23,7 +27,7 @@ import dedisp_ref
 import fold_ref
 import period_ref
 import periodlong_ref
-from period_family import FILL, FILL_BITS, same_bits
+from period_family import FILL, FILL_BITS, check_stage1, same_bits
 from period_family import noise as _noise, padded as _padded
 
 pytestmark = pytest.mark.gpu
@@ -63,16 +67,25 @@ def _resample(built, engine, x, log2n, coefs, nsamp, wide_in=False, wide_out=Fal
     return rows, want
 
 
+WORST, WORST_BIN = {}, {}
+
+
+def _reference(log2n):
+    """the f64 spectrum of a resampled series, whose two premises hold"""
+    def reference(xs, name):
+        ref, nyquist_small, mean_small = periodlong_ref.power_and_premises(xs, log2n)
+        if xs.size > 1 and ref.sum() > 0:
+            assert nyquist_small and mean_small, name
+        return ref
+    return reference
+
+
 def _check_stage1(power, resampled, log2n, nsamp, name):
-    """per virtual trial sum |P^ - P| <= c sum P against the f64 spectrum of the resampled series, whose two premises hold"""
-    c = accel_ref.bound(log2n)
+    """period_family.check_stage1 with a trial's accelerations as its trials: per virtual trial sum |P^ - P| <= c sum P
+    and every bin within accel_ref.bound_bin of the f64 spectrum of the resampled series"""
     for t in range(resampled.shape[0]):
-        for a in range(resampled.shape[1]):
-            ref, nyquist_small, mean_small = periodlong_ref.power_and_premises(resampled[t, a, :nsamp], log2n)
-            if nsamp > 1 and ref.sum() > 0:
-                assert nyquist_small and mean_small, (name, t, a)
-            err = np.abs(power[t, a].astype(np.float64) - ref).sum()
-            assert err <= c * ref.sum(), (name, t, a, err, c * ref.sum())
+        check_stage1(power[t], resampled[t], nsamp, accel_ref.bound(log2n), accel_ref.bound_bin(log2n), _reference(log2n), WORST, WORST_BIN,
+                     log2n, (name, t))
 
 
 def _fused_and_composed(built, engine, x, log2n, plan, coefs, nsamp=None, wide=False, want=(True, True), max_trials=None, name=None, stage1=True):
@@ -197,6 +210,7 @@ def test_the_longer_frames(built, engine, log2n, plan):
     x[0] += (3.0 * np.cos(2.0 * np.pi * np.arange(nsamp) / 37.5)).astype(np.float32)
     coefs = [TOP, -_seeded(log2n, 1)[0] // 2]
     _fused_and_composed(built, engine, x, log2n, plan, coefs, name=("long", log2n))
+    print("log2n %d: worst stage-1 error %.3g of the bound, worst bin %.3g of bound_bin %.3g" % (log2n, WORST[log2n], WORST_BIN[log2n], accel_ref.bound_bin(log2n)))
 
 
 def test_many_virtual_trials(built, engine):
