@@ -131,6 +131,87 @@ __device__ __forceinline__ int pos(int k)
     else return (k & 15) * (M / 16) + ((k >> 4) & 15) * (M / 256) + (k >> 8);
 }
 
+// ---- the inverse: from forward's order back to natural order ----
+// forward is a product of passes A = A_last .. A_2 A_1 that leaves bin k at pos(k); what takes that order back to the
+// points, sum_k Z[k] e^(+2 pi i n k / M) at point n (not scaled by 1 / M), is its conjugate transpose
+// A^H = A_1^H A_2^H .. A_last^H: the passes in reverse order, each one decimation in time -- a thread reads the places it
+// wrote in forward, value q at j + q L / r, multiplies by the conjugate twiddle W_L^(-j q), takes the conjugate r-point
+// transform over q and writes point n at j + n L / r, the places it read in forward.  No reordering pass.  The conjugate
+// transform is the forward one between two exchanges of the real and the imaginary part, swap(z) = i conj(z), which
+// cost nothing and round nothing; and swap(conj(w) z) = w swap(z), so the table's own entry multiplies the exchanged
+// value: the same butterflies, the same table, the same count of roundings as forward.
+__device__ __forceinline__ f2 swap(f2 z) { return mk(z.y, z.x); }
+
+template <int M, int L>
+__device__ __forceinline__ void inverse_pass16(float2* row, int b, const float2* tw)
+{
+    constexpr int STRIDE = L / 16;
+    const int j = b & (STRIDE - 1), i0 = (b / STRIDE) * L + j;
+    f2 v[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) v[q] = swap(row[place(i0 + q * STRIDE)]);
+    if constexpr (L > 16) {
+#pragma unroll
+        for (int q = 1; q < 16; ++q) v[q] = cmul(v[q], root<M>(tw, j * q * (2 * M / L)));
+    }
+    fft16_fma(v);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) row[place(i0 + rev16(s) * STRIDE)] = swap(v[s]);
+}
+
+// the conjugate of pass_last: the same R-point transforms (natural order in and out) between the two exchanges
+template <int R>
+__device__ __forceinline__ void inverse_pass_last(float2* row, int b)
+{
+    if constexpr (R > 1) {
+        float2* at = row + place(16 * b);
+        f2 v[16];
+#pragma unroll
+        for (int n = 0; n < 16; ++n) v[n] = swap(at[n]);
+        if constexpr (R == 2) {
+#pragma unroll
+            for (int g = 0; g < 8; ++g) bfly2(v[2 * g], v[2 * g + 1]);
+        } else if constexpr (R == 4) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) bfly4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
+        } else {
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {
+                f2 y[8];
+#pragma unroll
+                for (int r = 0; r < 8; ++r) y[r] = v[8 * g + r];
+                fft8(y);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) v[8 * g + 2 * s] = y[s], v[8 * g + 2 * s + 1] = y[4 + s];
+            }
+        }
+#pragma unroll
+        for (int n = 0; n < 16; ++n) at[n] = swap(v[n]);
+    }
+}
+
+// The whole inverse, called as forward is: place(pos(k)) holds Z[k] on entry (its writers behind a barrier of the
+// caller's), place(n) holds sum_k Z[k] e^(+2 pi i n k / M) on return, and every thread has passed the closing barrier.
+template <int LOG2M>
+__device__ __forceinline__ void inverse(float2* row, int tid, const float2* tw)
+{
+    using S = Shape<LOG2M>;
+    constexpr int M = S::M;
+    const bool mine = tid < M / 16;
+    if constexpr (S::R > 1) {
+        if (mine) inverse_pass_last<S::R>(row, tid);
+        __syncthreads();
+    }
+    if constexpr (S::THREE) {
+        if (mine) inverse_pass16<M, M / 256>(row, tid, tw);
+        __syncthreads();
+    }
+    if (mine) inverse_pass16<M, M / 16>(row, tid, tw);
+    __syncthreads();
+    if (mine) inverse_pass16<M, M>(row, tid, tw);
+    __syncthreads();
+}
+
 }  // namespace rowfft
 }  // namespace rtlws
 #endif
