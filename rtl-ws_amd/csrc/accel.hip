@@ -85,14 +85,11 @@ hipError_t launch_resample(const ResampleParams& p, hipStream_t st)
 
 hipError_t prepare(int log2n, int device)
 {
-    hipFuncAttributes a;
-    // asking for a kernel's attributes loads its code object: nothing is left to load under a capture
-    for (const void* k : {reinterpret_cast<const void*>(&mapped_mean_kernel), reinterpret_cast<const void*>(&mapped_cols16_kernel),
-                          reinterpret_cast<const void*>(&mapped_cols256_kernel), reinterpret_cast<const void*>(&resample_kernel)}) {
-        const hipError_t e = hipFuncGetAttributes(&a, k);
-        if (e != hipSuccess) return e;
-    }
-    return periodlong::prepare(log2n, device);
+    hipError_t e = load_kernel(&mapped_mean_kernel);
+    if (e == hipSuccess) e = load_kernel(&mapped_cols16_kernel);
+    if (e == hipSuccess) e = load_kernel(&mapped_cols256_kernel);
+    if (e == hipSuccess) e = load_kernel(&resample_kernel);
+    return e == hipSuccess ? periodlong::prepare(log2n, device) : e;
 }
 
 }  // namespace accel

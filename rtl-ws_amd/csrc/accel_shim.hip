@@ -86,10 +86,7 @@ const char* rtlws_accel_last_error(void) { return g_err.c_str(); }
 
 int rtlws_accel_supported(int log2n, int levels, int norm, int seg, int klo, int naccel, const int64_t* coefs)
 {
-    g_err.clear();
-    const char* why = why_not_table(log2n, levels, norm, seg, klo, naccel, coefs);
-    if (why) fail("rtlws_accel", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_accel", why_not_table(log2n, levels, norm, seg, klo, naccel, coefs));
 }
 
 int rtlws_accel_geometry(int log2n, int levels, int norm, int seg, int klo, int naccel, const int64_t* coefs, int ntrials, int* blocks,

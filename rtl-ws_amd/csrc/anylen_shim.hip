@@ -154,10 +154,7 @@ const char* rtlws_anylen_last_error(void) { return g_err.c_str(); }
 
 int rtlws_anylen_supported(const rtlws_spectra_desc* desc)
 {
-    g_err.clear();
-    const char* why = why_not(desc);
-    if (why) g_err = std::string("rtlws_anylen: ") + why;
-    return why ? 0 : 1;
+    return supported("rtlws_anylen", why_not(desc));
 }
 
 int rtlws_anylen_conv_log2(const rtlws_spectra_desc* desc)

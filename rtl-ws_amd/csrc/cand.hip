@@ -233,22 +233,16 @@ hipError_t launch_stage(bool sums, const StageParams& p, int ncand, hipStream_t 
     });
 }
 
-// hipFuncGetAttributes loads the code object on the current device, so that a launch makes no other call
+// load_kernel (rtlws_internal.h) for the kernel of a bin count
 hipError_t prepare_fold(int nbins)
 {
-    return with_fold_kernel(nbins, [](auto kernel) {
-        hipFuncAttributes a;
-        return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
-    });
+    return with_fold_kernel(nbins, [](auto kernel) { return load_kernel(kernel); });
 }
 
 hipError_t prepare_stages(int nbins)
 {
     return pick(PerLane{}, per_lane(nbins), [&](auto r) {
-        return visit_all(Bools{}, false, [&](auto s) {
-            hipFuncAttributes a;
-            return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&cand_stage_kernel<decltype(r)::value, decltype(s)::value>));
-        });
+        return visit_all(Bools{}, false, [&](auto s) { return load_kernel(&cand_stage_kernel<decltype(r)::value, decltype(s)::value>); });
     });
 }
 

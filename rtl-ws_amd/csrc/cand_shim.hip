@@ -5,7 +5,6 @@
 // on the host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -14,19 +13,15 @@
 
 #include "cand.h"
 #include "rtlws_cand.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
-struct rtlws_cand_fold_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_cand_fold_plan : rtlws::search::Plan {
     int ncand, nchan, nbins, max_delay;
     long sub;
     uint64_t* d_tables;        // steps [ncand], phases [ncand], then the delays [ncand][nchan] as int32 (-1: masked)
 };
 
-struct rtlws_cand_search_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_cand_search_plan : rtlws::search::Plan {
     int ncand, nsub, nchan, nbins, ndm, ntr;
     int32_t* d_shifts;         // a [ncand][ndm][nchan], then g [ncand][ntr][nsub]
     float* d_work;             // T [ncand][ndm][nsub][nbins]
@@ -35,22 +30,22 @@ struct rtlws_cand_search_plan {
 namespace {
 
 using namespace rtlws::cand;
+namespace sp = rtlws::search;
+using sp::why_not_nbins;
+using sp::why_not_nchan;
+using sp::why_not_nsamp;
 
 static_assert(MAX_CANDS == RTLWS_CAND_MAX_CANDS && MIN_NCHAN == RTLWS_CAND_MIN_NCHAN && MAX_NCHAN == RTLWS_CAND_MAX_NCHAN &&
                   MAX_DELAY == RTLWS_CAND_MAX_DELAY && MIN_BINS == RTLWS_CAND_MIN_BINS && MAX_BINS == RTLWS_CAND_MAX_BINS &&
                   MIN_SUB == RTLWS_CAND_MIN_SUB && MAX_SUB == RTLWS_CAND_MAX_SUB && MAX_NSAMP == RTLWS_CAND_MAX_NSAMP &&
                   MAX_NSUB == RTLWS_CAND_MAX_NSUB && MAX_NDM == RTLWS_CAND_MAX_NDM && MAX_NTR == RTLWS_CAND_MAX_NTR &&
-                  MAX_WORKSPACE == RTLWS_CAND_MAX_WORKSPACE,
-              "rtlws_cand.h and cand.h disagree");
-
-constexpr double DISPERSION = 4.148808e3;                      // rtlws_dedisp_delays' constant, seconds MHz^2
+                  MAX_WORKSPACE == RTLWS_CAND_MAX_WORKSPACE && MIN_NCHAN == sp::MIN_NCHAN && MAX_NCHAN == sp::MAX_NCHAN &&
+                  MIN_BINS == sp::MIN_BINS && MAX_BINS == sp::MAX_BINS && MAX_NSAMP == sp::MAX_NSAMP,
+              "rtlws_cand.h, cand.h and search_plan.h disagree");
 
 // ---- the rules, each worded once ----
 const char* why_not_ncand(int ncand) { return ncand < 1 || ncand > MAX_CANDS ? "ncand must be 1 .. 64" : nullptr; }
-const char* why_not_nchan(int nchan) { return nchan < MIN_NCHAN || nchan > MAX_NCHAN || nchan % 4 ? "nchan must be 4 .. 4096 and a multiple of 4" : nullptr; }
-const char* why_not_nbins(int nbins) { return nbins < MIN_BINS || nbins > MAX_BINS ? "nbins must be 2 .. 256" : nullptr; }
 const char* why_not_sub(long sub) { return sub < MIN_SUB || sub > MAX_SUB ? "sub must be 16 .. 16777216" : nullptr; }
-const char* why_not_nsamp(long nsamp) { return nsamp < 0 || nsamp > MAX_NSAMP ? "nsamp must be 0 .. 2^30" : nullptr; }
 const char* why_not_nsub(int nsub) { return nsub < 1 || nsub > MAX_NSUB ? "nsub must be 1 .. 1024" : nullptr; }
 const char* why_not_ndm(int ndm) { return ndm < 1 || ndm > MAX_NDM ? "ndm must be 1 .. 256" : nullptr; }
 
@@ -65,19 +60,16 @@ const char* why_not_cube(int ncand, int nchan, int nbins, long sub)
 const char* why_not_fold_tables(int ncand, const uint64_t* steps, const uint64_t* phases, int nchan, const int32_t* delays, int nbins, long sub)
 {
     if (const char* why = why_not_cube(ncand, nchan, nbins, sub)) return why;
-    if (!steps) return "null steps";
-    if (!phases) return "null phases";
+    if (const char* why = sp::why_not_steps(steps, phases)) return why;
     if (delays)
         for (long j = 0; j < (long)ncand * nchan; ++j)
             if (delays[j] < 0 || delays[j] > MAX_DELAY) return "a delay outside 0 .. 65535";
     return nullptr;
 }
 
-long subints_of(long nsamp, long sub) { return (nsamp + sub - 1) / sub; }
-
 const char* why_not_grid(int ncand, int nchan, int nbins, long sub, long nsamp)
 {
-    return subints_of(nsamp, sub) > INT_MAX / ((long)ncand * chan_groups(nchan, nbins)) ? "more workgroups than one grid holds" : nullptr;
+    return sp::why_not_grid(sp::ceil_div(nsamp, sub), (long)ncand * chan_groups(nchan, nbins));
 }
 
 long workspace_of(int ncand, int nsub, int nbins, int ndm) { return (long)ncand * ndm * nsub * nbins * (long)sizeof(float); }
@@ -127,13 +119,7 @@ extern "C" {
 
 const char* rtlws_cand_last_error(void) { return g_err.c_str(); }
 
-int rtlws_cand_fold_supported(int ncand, int nchan, int nbins, long sub)
-{
-    g_err.clear();
-    const char* why = why_not_cube(ncand, nchan, nbins, sub);
-    if (why) fail("rtlws_cand_fold", why, 0);
-    return why ? 0 : 1;
-}
+int rtlws_cand_fold_supported(int ncand, int nchan, int nbins, long sub) { return supported("rtlws_cand_fold", why_not_cube(ncand, nchan, nbins, sub)); }
 
 int rtlws_cand_fold_geometry(int ncand, int nchan, int nbins, long sub, long nsamp, int* blocks, int* threads, int* lds, int* wpb, long* nsub)
 {
@@ -142,54 +128,41 @@ int rtlws_cand_fold_geometry(int ncand, int nchan, int nbins, long sub, long nsa
     if (const char* why = why_not_cube(ncand, nchan, nbins, sub)) return fail(fn, why, -1);
     if (const char* why = why_not_nsamp(nsamp)) return fail(fn, why, -1);
     if (const char* why = why_not_grid(ncand, nchan, nbins, sub, nsamp)) return fail(fn, why, -1);
-    if (blocks) *blocks = (int)(subints_of(nsamp, sub) * ncand * chan_groups(nchan, nbins));
+    if (blocks) *blocks = (int)(sp::ceil_div(nsamp, sub) * ncand * chan_groups(nchan, nbins));
     if (threads) *threads = LANES * waves_per_block(nbins);
     if (lds) *lds = lds_bytes(nbins);
     if (wpb) *wpb = waves_per_block(nbins);
-    if (nsub) *nsub = subints_of(nsamp, sub);
+    if (nsub) *nsub = sp::ceil_div(nsamp, sub);
     return 0;
 }
 
 rtlws_cand_fold_plan* rtlws_cand_fold_open(rtlws_engine* e, int ncand, const uint64_t* steps, const uint64_t* phases, int nchan,
                                            const int32_t* delays, const uint8_t* mask, int nbins, long sub)
 {
-    const char* fn = "rtlws_cand_fold_open";
-    g_err.clear();
-    const int device = open_device(fn, why_not_fold_tables(ncand, steps, phases, nchan, delays, nbins, sub), e);
-    if (device < 0) return nullptr;
-    // steps, phases, then the delays as the kernel reads them: -1 where the mask drops the channel
-    const size_t cells = (size_t)ncand * nchan;
-    std::vector<uint64_t> host(2 * (size_t)ncand + (cells + 1) / 2);
-    int32_t* const d = reinterpret_cast<int32_t*>(host.data() + 2 * (size_t)ncand);
-    int max_delay = 0;
-    for (int c = 0; c < ncand; ++c) {
-        host[c] = steps[c];
-        host[(size_t)ncand + c] = phases[c];
-        for (int i = 0; i < nchan; ++i) {
-            const int32_t v = delays ? delays[(size_t)c * nchan + i] : 0;
-            const bool kept = !mask || mask[i];
-            d[(size_t)c * nchan + i] = kept ? v : -1;
-            if (kept && v > max_delay) max_delay = v;
+    const auto fill = [&](rtlws_cand_fold_plan& p) {
+        p.ncand = ncand, p.nchan = nchan, p.nbins = nbins, p.sub = sub;
+        // steps, phases, then the delays as the kernel reads them: -1 where the mask drops the channel
+        const size_t cells = (size_t)ncand * nchan;
+        std::vector<uint64_t> host(2 * (size_t)ncand + (cells + 1) / 2);
+        int32_t* const d = reinterpret_cast<int32_t*>(host.data() + 2 * (size_t)ncand);
+        for (int c = 0; c < ncand; ++c) {
+            host[c] = steps[c];
+            host[(size_t)ncand + c] = phases[c];
+            for (int i = 0; i < nchan; ++i) {
+                const int32_t v = delays ? delays[(size_t)c * nchan + i] : 0;
+                const bool kept = !mask || mask[i];
+                d[(size_t)c * nchan + i] = kept ? v : -1;
+                if (kept && v > p.max_delay) p.max_delay = v;
+            }
         }
-    }
-    uint64_t* d_tables = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_tables), host.size() * sizeof(uint64_t));
-    if (err == hipSuccess) err = hipMemcpy(d_tables, host.data(), host.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_fold(nbins);
-    if (err != hipSuccess) {
-        if (d_tables) (void)hipFree(d_tables);
-        fail_hip(fn, "the tables or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_cand_fold_plan{e, device, ncand, nchan, nbins, max_delay, sub, d_tables};
+        const hipError_t err = sp::upload(&p.d_tables, host.data(), host.size());
+        return err == hipSuccess ? prepare_fold(nbins) : err;
+    };
+    return sp::open_plan<rtlws_cand_fold_plan>("rtlws_cand_fold_open", why_not_fold_tables(ncand, steps, phases, nchan, delays, nbins, sub), e, fill,
+                                               "the tables or the kernel", rtlws_cand_fold_close);
 }
 
-void rtlws_cand_fold_close(rtlws_cand_fold_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_tables);
-    delete p;
-}
+void rtlws_cand_fold_close(rtlws_cand_fold_plan* p) { sp::close_plan(p, &rtlws_cand_fold_plan::d_tables); }
 
 long rtlws_cand_fold_rows_needed(const rtlws_cand_fold_plan* p, long nsamp)
 {
@@ -206,19 +179,18 @@ int rtlws_cand_fold_run(rtlws_cand_fold_plan* p, const float* d_rows, long in_st
     g_err.clear();
     // what needs no plan
     if (const char* why = why_not_nsamp(nsamp)) return fail(fn, why, -1);
-    if (in_stride < 4 || in_stride % 4) return fail(fn, "in_stride must be >= 4 and a multiple of 4", -1);
+    if (const char* why = sp::why_not_stride_of_rows(in_stride)) return fail(fn, why, -1);
     if (!d_rows || !d_cube) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_rows) & 15u) return fail(fn, "d_rows must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_cube) & 3u) return fail(fn, "d_cube must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_hits) & 3u) return fail(fn, "d_hits must be 4-byte aligned", -1);
+    if (sp::misaligned(d_rows, 16)) return fail(fn, "d_rows must be 16-byte aligned", -1);
+    if (sp::misaligned(d_cube, 4)) return fail(fn, "d_cube must be 4-byte aligned", -1);
+    if (sp::misaligned(d_hits, 4)) return fail(fn, "d_hits must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
-    if (in_stride < p->nchan) return fail(fn, "in_stride must be >= nchan", -1);
+    if (const char* why = sp::why_not_row_stride(in_stride, p->nchan)) return fail(fn, why, -1);
     if (const char* why = why_not_grid(p->ncand, p->nchan, p->nbins, p->sub, nsamp)) return fail(fn, why, -1);
     if (nsamp == 0) return 0;
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     FoldParams kp;
     kp.rows = d_rows;
     kp.cube = d_cube;
@@ -229,21 +201,18 @@ int rtlws_cand_fold_run(rtlws_cand_fold_plan* p, const float* d_rows, long in_st
     kp.in_stride = in_stride;
     kp.nsamp = nsamp;
     kp.sub = p->sub;
-    kp.nsub = subints_of(nsamp, p->sub);
+    kp.nsub = sp::ceil_div(nsamp, p->sub);
     kp.nchan = p->nchan;
     kp.nbins = p->nbins;
     kp.groups = chan_groups(p->nchan, p->nbins);
-    err = launch_fold(kp, p->ncand, stream_of(p->engine, stream));
+    const hipError_t err = launch_fold(kp, p->ncand, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }
 
 int rtlws_cand_search_supported(int ncand, int nsub, int nchan, int nbins, int ndm, int ntr)
 {
-    g_err.clear();
-    const char* why = why_not_search(ncand, nsub, nchan, nbins, ndm, ntr);
-    if (why) fail("rtlws_cand_search", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_cand_search", why_not_search(ncand, nsub, nchan, nbins, ndm, ntr));
 }
 
 int rtlws_cand_search_geometry(int ncand, int nsub, int nchan, int nbins, int ndm, int ntr, int* blocks1, int* blocks2, int* threads, int* lds1,
@@ -263,33 +232,22 @@ int rtlws_cand_search_geometry(int ncand, int nsub, int nchan, int nbins, int nd
 rtlws_cand_search_plan* rtlws_cand_search_open(rtlws_engine* e, int ncand, int nsub, int nchan, int nbins, int ndm, const int32_t* a, int ntr,
                                                const int32_t* g)
 {
-    const char* fn = "rtlws_cand_search_open";
-    g_err.clear();
-    const int device = open_device(fn, why_not_search_tables(ncand, nsub, nchan, nbins, ndm, a, ntr, g), e);
-    if (device < 0) return nullptr;
-    rtlws_cand_search_plan* p = new rtlws_cand_search_plan{e, device, ncand, nsub, nchan, nbins, ndm, ntr, nullptr, nullptr};
-    const size_t na = (size_t)ncand * ndm * nchan, ng = (size_t)ncand * ntr * nsub;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->d_shifts), (na + ng) * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMemcpy(p->d_shifts, a, na * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(p->d_shifts + na, g, ng * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&p->d_work), (size_t)workspace_of(ncand, nsub, nbins, ndm));
-    if (err == hipSuccess) err = prepare_stages(nbins);
-    if (err != hipSuccess) {
-        fail_hip(fn, "the tables, the workspace or the kernels", err);
-        rtlws_cand_search_close(p);
-        return nullptr;
-    }
-    return p;
+    const auto fill = [&](rtlws_cand_search_plan& p) {
+        p.ncand = ncand, p.nsub = nsub, p.nchan = nchan, p.nbins = nbins, p.ndm = ndm, p.ntr = ntr;
+        const size_t na = (size_t)ncand * ndm * nchan, ng = (size_t)ncand * ntr * nsub;
+        hipError_t err = hipMalloc(reinterpret_cast<void**>(&p.d_shifts), (na + ng) * sizeof(int32_t));
+        if (err == hipSuccess) err = hipMemcpy(p.d_shifts, a, na * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMemcpy(p.d_shifts + na, g, ng * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&p.d_work), (size_t)workspace_of(ncand, nsub, nbins, ndm));
+        return err == hipSuccess ? prepare_stages(nbins) : err;
+    };
+    return sp::open_plan<rtlws_cand_search_plan>("rtlws_cand_search_open", why_not_search_tables(ncand, nsub, nchan, nbins, ndm, a, ntr, g), e, fill,
+                                                 "the tables, the workspace or the kernels", rtlws_cand_search_close);
 }
 
 void rtlws_cand_search_close(rtlws_cand_search_plan* p)
 {
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) {
-        (void)hipFree(p->d_shifts);
-        (void)hipFree(p->d_work);
-    }
-    delete p;
+    sp::close_plan(p, &rtlws_cand_search_plan::d_shifts, &rtlws_cand_search_plan::d_work);
 }
 
 int rtlws_cand_search_run(rtlws_cand_search_plan* p, const float* d_cube, double* d_stat, double* d_total, float* d_prof, float* d_tphase,
@@ -298,15 +256,14 @@ int rtlws_cand_search_run(rtlws_cand_search_plan* p, const float* d_cube, double
     const char* fn = "rtlws_cand_search_run";
     g_err.clear();
     if (!d_cube || !d_stat || !d_total) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_cube) & 3u) return fail(fn, "d_cube must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_stat) & 7u) return fail(fn, "d_stat must be 8-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_total) & 7u) return fail(fn, "d_total must be 8-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_prof) & 3u) return fail(fn, "d_prof must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_tphase) & 3u) return fail(fn, "d_tphase must be 4-byte aligned", -1);
+    if (sp::misaligned(d_cube, 4)) return fail(fn, "d_cube must be 4-byte aligned", -1);
+    if (sp::misaligned(d_stat, 8)) return fail(fn, "d_stat must be 8-byte aligned", -1);
+    if (sp::misaligned(d_total, 8)) return fail(fn, "d_total must be 8-byte aligned", -1);
+    if (sp::misaligned(d_prof, 4)) return fail(fn, "d_prof must be 4-byte aligned", -1);
+    if (sp::misaligned(d_tphase, 4)) return fail(fn, "d_tphase must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     const hipStream_t st = stream_of(p->engine, stream);
     StageParams s1{};
     s1.in = d_cube;
@@ -314,7 +271,7 @@ int rtlws_cand_search_run(rtlws_cand_search_plan* p, const float* d_cube, double
     s1.out = p->d_work;
     s1.copy = d_tphase;
     s1.no = p->nsub, s1.nk = p->nchan, s1.nt = p->ndm, s1.nbins = p->nbins;
-    err = launch_stage(false, s1, p->ncand, st);
+    hipError_t err = launch_stage(false, s1, p->ncand, st);
     if (err != hipSuccess) return fail_hip(fn, "kernel launch (stage 1)", err);
     StageParams s2{};
     s2.in = p->d_work;
@@ -335,27 +292,18 @@ int rtlws_cand_dm_shifts(int nchan, int shifted, double f_centre_hz, double band
     g_err.clear();
     if (const char* why = why_not_nchan(nchan)) return fail(fn, why, -1);
     if (shifted != 0 && shifted != 1) return fail(fn, "shifted must be 0 or 1", -1);
-    if (!(std::isfinite(bandwidth_hz) && bandwidth_hz > 0.0)) return fail(fn, "bandwidth_hz must be finite and > 0", -1);
-    if (!(std::isfinite(row_seconds) && row_seconds > 0.0)) return fail(fn, "row_seconds must be finite and > 0", -1);
+    if (const char* why = sp::why_not_band(nchan, f_centre_hz, bandwidth_hz, row_seconds)) return fail(fn, why, -1);
     const int M = nchan;
-    if (!(std::isfinite(f_centre_hz) && f_centre_hz + (double)(M / 2 - M) * bandwidth_hz / (double)M > 0.0))
-        return fail(fn, "every channel's frequency must be finite and > 0", -1);
     if (!(std::isfinite(period_rows) && period_rows > 0.0)) return fail(fn, "period_rows must be finite and > 0", -1);
     if (const char* why = why_not_nbins(nbins)) return fail(fn, why, -1);
     if (const char* why = why_not_ndm(ndm)) return fail(fn, why, -1);
     if (!std::isfinite(ddm0) || !std::isfinite(ddm_step)) return fail(fn, "the DM offsets must be finite", -1);
     if (!a) return fail(fn, "null table", -1);
-    std::vector<double> excess(M);                            // nu_i^-2 - nu_max^-2, nu in MHz: rtlws_dedisp_delays'
-    const double top = (f_centre_hz + (double)(M / 2 - 1) * bandwidth_hz / (double)M) / 1e6;
-    for (int i = 0; i < M; ++i) {
-        const int c = shifted ? (i + M / 2) % M : i;
-        const double nu = (f_centre_hz + (double)(c < M / 2 ? c : c - M) * bandwidth_hz / (double)M) / 1e6;
-        excess[i] = 1.0 / (nu * nu) - 1.0 / (top * top);
-    }
+    const std::vector<double> excess = sp::excess(M, shifted, f_centre_hz, bandwidth_hz);
     for (int q = 0; q < ndm; ++q) {
         const double ddm = ddm0 + (double)q * ddm_step;
         for (int i = 0; i < M; ++i) {
-            const double rows = DISPERSION * ddm * excess[i] / row_seconds;
+            const double rows = sp::DISPERSION * ddm * excess[i] / row_seconds;
             if (!shift_of((double)nbins * rows / period_rows, nbins, a + (long)q * M + i)) return fail(fn, "a shift of 2^31 bins or more", -1);
         }
     }

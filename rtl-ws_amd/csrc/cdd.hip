@@ -91,8 +91,7 @@ hipError_t launch(int log2n, const Params& p, long nseg, int nchan, hipStream_t 
 hipError_t prepare(int log2n, int device)
 {
     return pick(Log2Ns{}, log2n, [&](auto n) {
-        hipFuncAttributes a;
-        const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&cdd_kernel<decltype(n)::value>));
+        const hipError_t e = load_kernel(&cdd_kernel<decltype(n)::value>);
         return e != hipSuccess ? e : lds_opt_in(&cdd_kernel<decltype(n)::value>, device, (size_t)lds_of(log2n));
     });
 }

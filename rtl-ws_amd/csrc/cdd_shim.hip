@@ -10,11 +10,9 @@
 
 #include "cdd.h"
 #include "rtlws_cdd.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
-struct rtlws_cdd_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_cdd_plan : rtlws::search::Plan {
     int log2n, lead, trail, hop, nchan, ksum;
     float2* d_tables;          // the filters [nchan][N] in the order of the places, then the twiddles [N]
 };
@@ -22,12 +20,13 @@ struct rtlws_cdd_plan {
 namespace {
 
 using namespace rtlws::cdd;
+namespace sp = rtlws::search;
 
 static_assert(MIN_LOG2N == RTLWS_CDD_MIN_LOG2_NFFT && MAX_LOG2N == RTLWS_CDD_MAX_LOG2_NFFT && MAX_NCHAN == RTLWS_CDD_MAX_NCHAN &&
                   MAX_NSEG == RTLWS_CDD_MAX_NSEG && CHANNEL_MAJOR == RTLWS_CDD_CHANNEL_MAJOR && TIME_MAJOR == RTLWS_CDD_TIME_MAJOR,
               "rtlws_cdd.h and cdd.h disagree");
 
-constexpr double DISPERSION = 4.148808e3 * 1e6;               // rtlws_dedisp_delays' constant, in microseconds MHz^2
+constexpr double DISPERSION = sp::DISPERSION * 1e6;           // the band's constant, in microseconds MHz^2
 constexpr double TWO_PI = 6.283185307179586476925286766559;
 
 // ---- the rules, each worded once ----
@@ -66,10 +65,7 @@ const char* rtlws_cdd_last_error(void) { return g_err.c_str(); }
 
 int rtlws_cdd_supported(int log2_nfft, int lead, int trail, int nchan, int ksum)
 {
-    g_err.clear();
-    const char* why = why_not_plan(log2_nfft, lead, trail, nchan, ksum);
-    if (why) fail("rtlws_cdd", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_cdd", why_not_plan(log2_nfft, lead, trail, nchan, ksum));
 }
 
 int rtlws_cdd_geometry(int log2_nfft, int lead, int trail, int nchan, int ksum, long nseg, int* blocks, int* threads, int* lds_bytes)
@@ -86,40 +82,27 @@ int rtlws_cdd_geometry(int log2_nfft, int lead, int trail, int nchan, int ksum, 
 
 rtlws_cdd_plan* rtlws_cdd_open(rtlws_engine* e, int log2_nfft, int lead, int trail, int nchan, int ksum, const float* tables)
 {
-    const char* fn = "rtlws_cdd_open";
-    g_err.clear();
     const char* why = why_not_plan(log2_nfft, lead, trail, nchan, ksum);
     if (!why && !tables) why = "null tables";
-    const int device = open_device(fn, why, e);
-    if (device < 0) return nullptr;
-    const int n = 1 << log2_nfft;
-    rtlws_cdd_plan* p = new rtlws_cdd_plan{e, device, log2_nfft, lead, trail, n - lead - trail, nchan, ksum, nullptr};
-    // bin k of a channel goes where forward leaves it; behind the filters e^(-2 pi i j / (2 N)), j < N, rounded once
-    std::vector<float2> host((size_t)(nchan + 1) * n);
-    for (int c = 0; c < nchan; ++c)
-        for (int k = 0; k < n; ++k) {
-            const float* const h = tables + 2 * ((size_t)c * n + k);
-            host[(size_t)c * n + pos_of(log2_nfft, k)] = make_float2(h[0], h[1]);
-        }
-    const long double step = 3.141592653589793238462643383279L / (long double)n;
-    for (int j = 0; j < n; ++j) host[(size_t)nchan * n + j] = make_float2((float)cosl(step * j), (float)-sinl(step * j));
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->d_tables), host.size() * sizeof(float2));
-    if (err == hipSuccess) err = hipMemcpy(p->d_tables, host.data(), host.size() * sizeof(float2), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare(log2_nfft, device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "the tables or the kernel", err);
-        rtlws_cdd_close(p);
-        return nullptr;
-    }
-    return p;
+    const auto fill = [&](rtlws_cdd_plan& p) {
+        const int n = 1 << log2_nfft;
+        p.log2n = log2_nfft, p.lead = lead, p.trail = trail, p.hop = n - lead - trail, p.nchan = nchan, p.ksum = ksum;
+        // bin k of a channel goes where forward leaves it; behind the filters e^(-2 pi i j / (2 N)), j < N, rounded once
+        std::vector<float2> host((size_t)(nchan + 1) * n);
+        for (int c = 0; c < nchan; ++c)
+            for (int k = 0; k < n; ++k) {
+                const float* const h = tables + 2 * ((size_t)c * n + k);
+                host[(size_t)c * n + pos_of(log2_nfft, k)] = make_float2(h[0], h[1]);
+            }
+        const long double step = 3.141592653589793238462643383279L / (long double)n;
+        for (int j = 0; j < n; ++j) host[(size_t)nchan * n + j] = make_float2((float)cosl(step * j), (float)-sinl(step * j));
+        const hipError_t err = sp::upload(&p.d_tables, host.data(), host.size());
+        return err == hipSuccess ? prepare(log2_nfft, p.device) : err;
+    };
+    return sp::open_plan<rtlws_cdd_plan>("rtlws_cdd_open", why, e, fill, "the tables or the kernel", rtlws_cdd_close);
 }
 
-void rtlws_cdd_close(rtlws_cdd_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_tables);
-    delete p;
-}
+void rtlws_cdd_close(rtlws_cdd_plan* p) { sp::close_plan(p, &rtlws_cdd_plan::d_tables); }
 
 long rtlws_cdd_samples_needed(const rtlws_cdd_plan* p, long nseg)
 {
@@ -138,20 +121,19 @@ int rtlws_cdd_run(rtlws_cdd_plan* p, const float* d_in, long in_stride, long nse
     if (const char* why = why_not_nseg(nseg)) return fail(fn, why, -1);
     if (layout != CHANNEL_MAJOR && layout != TIME_MAJOR) return fail(fn, "unknown layout", -1);
     if (!d_in || !d_out) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_in) & 7u) return fail(fn, "d_in must be 8-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(fn, "d_out must be 4-byte aligned", -1);
+    if (sp::misaligned(d_in, 8)) return fail(fn, "d_in must be 8-byte aligned", -1);
+    if (sp::misaligned(d_out, 4)) return fail(fn, "d_out must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     const long rows = p->ksum ? nseg * (p->hop / p->ksum) : nseg * p->hop;        // of a channel
     if (!p->ksum && layout != CHANNEL_MAJOR) return fail(fn, "voltages are channel-major", -1);
-    if (!p->ksum && (reinterpret_cast<uintptr_t>(d_out) & 7u)) return fail(fn, "d_out must be 8-byte aligned for voltages", -1);
+    if (!p->ksum && sp::misaligned(d_out, 8)) return fail(fn, "d_out must be 8-byte aligned for voltages", -1);
     if (in_stride < needed(*p, nseg)) return fail(fn, "in_stride must be >= samples_needed", -1);
     if (layout == TIME_MAJOR ? out_stride < p->nchan : out_stride < rows)
         return fail(fn, layout == TIME_MAJOR ? "out_stride must be >= nchan" : "out_stride must be >= the outputs of a channel", -1);
     if (nseg == 0) return 0;
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     Params kp{};
     kp.in = reinterpret_cast<const float2*>(d_in);
     kp.out = d_out;
@@ -160,7 +142,7 @@ int rtlws_cdd_run(rtlws_cdd_plan* p, const float* d_in, long in_stride, long nse
     kp.in_stride = in_stride, kp.out_stride = out_stride;
     kp.lead = p->lead, kp.hop = p->hop, kp.ksum = p->ksum, kp.layout = layout;
     kp.scale = 1.0f / (float)(1 << p->log2n);
-    err = launch(p->log2n, kp, nseg, p->nchan, stream_of(p->engine, stream));
+    const hipError_t err = launch(p->log2n, kp, nseg, p->nchan, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }

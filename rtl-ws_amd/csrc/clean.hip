@@ -343,17 +343,14 @@ hipError_t launch_apply(const ApplyParams& p, long nblocks, hipStream_t st)
     });
 }
 
-// hipFuncGetAttributes loads the code object on the current device, so that a launch makes no other call
+// load_kernel (rtlws_internal.h) for the kernels of a channel count
 hipError_t prepare(int nchan, int device)
 {
-    hipFuncAttributes a;
-    hipError_t err = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&clean_stats_kernel));
-    if (err == hipSuccess) err = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&clean_flags_kernel));
+    hipError_t err = load_kernel(&clean_stats_kernel);
+    if (err == hipSuccess) err = load_kernel(&clean_flags_kernel);
     if (err == hipSuccess) err = lds_opt_in(&clean_flags_kernel, device, (size_t)flag_lds(nchan));        // above 64 KiB from 2052 channels on
     if (err != hipSuccess) return err;
-    return pick(RowWaves{}, row_waves(nchan), [&](auto w) {
-        return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&clean_apply_kernel<decltype(w)::value>));
-    });
+    return pick(RowWaves{}, row_waves(nchan), [&](auto w) { return load_kernel(&clean_apply_kernel<decltype(w)::value>); });
 }
 
 }  // namespace clean

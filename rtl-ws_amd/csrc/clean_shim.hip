@@ -4,18 +4,15 @@
 // host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "clean.h"
 #include "rtlws_clean.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
-struct rtlws_clean_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_clean_plan : rtlws::search::Plan {
     int nchan, block_rows, zerodm;
     double t_mean, t_sigma;
     long max_blocks;
@@ -25,14 +22,15 @@ struct rtlws_clean_plan {
 namespace {
 
 using namespace rtlws::clean;
+namespace sp = rtlws::search;
+using sp::why_not_nchan;
 
 static_assert(MIN_NCHAN == RTLWS_CLEAN_MIN_NCHAN && MAX_NCHAN == RTLWS_CLEAN_MAX_NCHAN && MIN_BLOCK == RTLWS_CLEAN_MIN_BLOCK &&
                   MAX_BLOCK == RTLWS_CLEAN_MAX_BLOCK && MAX_NROWS == RTLWS_CLEAN_MAX_NROWS && MAX_CELLS == RTLWS_CLEAN_MAX_CELLS &&
-                  FLAG_ZERODM == RTLWS_CLEAN_ZERODM,
-              "rtlws_clean.h and clean.h disagree");
+                  FLAG_ZERODM == RTLWS_CLEAN_ZERODM && MIN_NCHAN == sp::MIN_NCHAN && MAX_NCHAN == sp::MAX_NCHAN,
+              "rtlws_clean.h, clean.h and search_plan.h disagree");
 
 // ---- the rules, each worded once ----
-const char* why_not_nchan(int nchan) { return nchan < MIN_NCHAN || nchan > MAX_NCHAN || nchan % 4 ? "nchan must be 4 .. 4096 and a multiple of 4" : nullptr; }
 const char* why_not_block(long block_rows) { return block_rows < MIN_BLOCK || block_rows > MAX_BLOCK ? "block_rows must be 32 .. 16384" : nullptr; }
 const char* why_not_nrows(long nrows) { return nrows < 0 || nrows > MAX_NROWS ? "nrows must be 0 .. 2^24" : nullptr; }
 
@@ -51,18 +49,15 @@ const char* why_not_plan(int nchan, long block_rows, double t_mean, double t_sig
     return nullptr;
 }
 
-long blocks_of(long nrows, long block_rows) { return (nrows + block_rows - 1) / block_rows; }
-
 // what a shape decides about nrows (within 0 .. 2^24): the least run, the workspace, the three grids
 const char* why_not_run(int nchan, long block_rows, long nrows)
 {
     if (nrows == 0) return nullptr;
     if (nrows < block_rows) return "nrows must be 0 or at least block_rows";
-    const long nblocks = blocks_of(nrows, block_rows);
+    const long nblocks = sp::ceil_div(nrows, block_rows);
     if (nblocks > max_blocks(nchan, (int)block_rows)) return "more blocks than the plan's workspace holds (clean the rows in pieces of whole blocks)";
     const long most = chan_groups(nchan) > apply_groups(nchan, (int)block_rows) ? chan_groups(nchan) : apply_groups(nchan, (int)block_rows);
-    if (nblocks > INT_MAX / most) return "more workgroups than one grid holds";
-    return nullptr;
+    return sp::why_not_grid(nblocks, most);
 }
 
 // [a, a + na) and [b, b + nb) in bytes share a byte
@@ -74,13 +69,7 @@ extern "C" {
 
 const char* rtlws_clean_last_error(void) { return g_err.c_str(); }
 
-int rtlws_clean_supported(int nchan, long block_rows)
-{
-    g_err.clear();
-    const char* why = why_not_shape(nchan, block_rows);
-    if (why) fail("rtlws_clean", why, 0);
-    return why ? 0 : 1;
-}
+int rtlws_clean_supported(int nchan, long block_rows) { return supported("rtlws_clean", why_not_shape(nchan, block_rows)); }
 
 int rtlws_clean_geometry(int nchan, long block_rows, long nrows, int* blocks, int* threads, int* lds, long* nblocks, long* workspace, long* most)
 {
@@ -89,7 +78,7 @@ int rtlws_clean_geometry(int nchan, long block_rows, long nrows, int* blocks, in
     if (const char* why = why_not_shape(nchan, block_rows)) return fail(fn, why, -1);
     if (const char* why = why_not_nrows(nrows)) return fail(fn, why, -1);
     if (const char* why = why_not_run(nchan, block_rows, nrows)) return fail(fn, why, -1);
-    const long nb = blocks_of(nrows, block_rows);
+    const long nb = sp::ceil_div(nrows, block_rows);
     if (blocks) blocks[0] = (int)(nb * chan_groups(nchan)), blocks[1] = (int)nb, blocks[2] = (int)(nb * apply_groups(nchan, (int)block_rows));
     if (threads) threads[0] = STATS_THREADS, threads[1] = flag_threads(nchan), threads[2] = apply_threads(nchan);
     if (lds) lds[0] = STATS_LDS, lds[1] = flag_lds(nchan), lds[2] = apply_lds(nchan);
@@ -101,33 +90,22 @@ int rtlws_clean_geometry(int nchan, long block_rows, long nrows, int* blocks, in
 
 rtlws_clean_plan* rtlws_clean_open(rtlws_engine* e, int nchan, long block_rows, const uint8_t* mask, double t_mean, double t_sigma, int flags)
 {
-    const char* fn = "rtlws_clean_open";
-    g_err.clear();
-    const int device = open_device(fn, why_not_plan(nchan, block_rows, t_mean, t_sigma, flags), e);
-    if (device < 0) return nullptr;
-    const long most = max_blocks(nchan, (int)block_rows);
-    const size_t work = (size_t)workspace_bytes(nchan, most);
-    std::vector<uint8_t> host(nchan, 1);
-    if (mask)
-        for (int i = 0; i < nchan; ++i) host[i] = mask[i] ? 1 : 0;
-    void* d_work = nullptr;
-    hipError_t err = hipMalloc(&d_work, work + (size_t)nchan);
-    if (err == hipSuccess) err = hipMemcpy(static_cast<char*>(d_work) + work, host.data(), (size_t)nchan, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare(nchan, device);
-    if (err != hipSuccess) {
-        if (d_work) (void)hipFree(d_work);
-        fail_hip(fn, "the mask, the workspace or the kernels", err);
-        return nullptr;
-    }
-    return new rtlws_clean_plan{e, device, nchan, (int)block_rows, (flags & FLAG_ZERODM) ? 1 : 0, t_mean, t_sigma, most, d_work};
+    const auto fill = [&](rtlws_clean_plan& p) {
+        p.nchan = nchan, p.block_rows = (int)block_rows, p.zerodm = (flags & FLAG_ZERODM) ? 1 : 0;
+        p.t_mean = t_mean, p.t_sigma = t_sigma, p.max_blocks = max_blocks(nchan, (int)block_rows);
+        const size_t work = (size_t)workspace_bytes(nchan, p.max_blocks);
+        std::vector<uint8_t> host(nchan, 1);
+        if (mask)
+            for (int i = 0; i < nchan; ++i) host[i] = mask[i] ? 1 : 0;
+        hipError_t err = hipMalloc(&p.d_work, work + (size_t)nchan);
+        if (err == hipSuccess) err = hipMemcpy(static_cast<char*>(p.d_work) + work, host.data(), (size_t)nchan, hipMemcpyHostToDevice);
+        return err == hipSuccess ? prepare(nchan, p.device) : err;
+    };
+    return sp::open_plan<rtlws_clean_plan>("rtlws_clean_open", why_not_plan(nchan, block_rows, t_mean, t_sigma, flags), e, fill,
+                                           "the mask, the workspace or the kernels", rtlws_clean_close);
 }
 
-void rtlws_clean_close(rtlws_clean_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_work);
-    delete p;
-}
+void rtlws_clean_close(rtlws_clean_plan* p) { sp::close_plan(p, &rtlws_clean_plan::d_work); }
 
 long rtlws_clean_blocks(const rtlws_clean_plan* p, long nrows)
 {
@@ -135,7 +113,7 @@ long rtlws_clean_blocks(const rtlws_clean_plan* p, long nrows)
     g_err.clear();
     if (const char* why = why_not_nrows(nrows)) return fail(fn, why, -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
-    return blocks_of(nrows, p->block_rows);
+    return sp::ceil_div(nrows, p->block_rows);
 }
 
 int rtlws_clean_run(rtlws_clean_plan* p, const float* d_rows, long in_stride, long nrows, float* d_out, long out_stride, uint8_t* d_keep,
@@ -145,16 +123,16 @@ int rtlws_clean_run(rtlws_clean_plan* p, const float* d_rows, long in_stride, lo
     g_err.clear();
     // what needs no plan
     if (const char* why = why_not_nrows(nrows)) return fail(fn, why, -1);
-    if (in_stride < 4 || in_stride % 4) return fail(fn, "in_stride must be >= 4 and a multiple of 4", -1);
+    if (const char* why = sp::why_not_stride_of_rows(in_stride)) return fail(fn, why, -1);
     if (out_stride < 4 || out_stride % 4) return fail(fn, "out_stride must be >= 4 and a multiple of 4", -1);
     if (!d_rows || !d_out) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_rows) & 15u) return fail(fn, "d_rows must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return fail(fn, "d_out must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_stats) & 3u) return fail(fn, "d_stats must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_nkept) & 3u) return fail(fn, "d_nkept must be 4-byte aligned", -1);
+    if (sp::misaligned(d_rows, 16)) return fail(fn, "d_rows must be 16-byte aligned", -1);
+    if (sp::misaligned(d_out, 16)) return fail(fn, "d_out must be 16-byte aligned", -1);
+    if (sp::misaligned(d_stats, 4)) return fail(fn, "d_stats must be 4-byte aligned", -1);
+    if (sp::misaligned(d_nkept, 4)) return fail(fn, "d_nkept must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
-    if (in_stride < p->nchan) return fail(fn, "in_stride must be >= nchan", -1);
+    if (const char* why = sp::why_not_row_stride(in_stride, p->nchan)) return fail(fn, why, -1);
     if (out_stride < p->nchan) return fail(fn, "out_stride must be >= nchan", -1);
     if (nrows == 0) return 0;
     if (nrows < p->block_rows) return fail(fn, "nrows must be 0 or at least block_rows", -1);
@@ -165,10 +143,9 @@ int rtlws_clean_run(rtlws_clean_plan* p, const float* d_rows, long in_stride, lo
         return fail(fn, "d_out overlaps d_rows (in place: d_out == d_rows with equal strides)", -1);
     if (const char* why = why_not_run(p->nchan, p->block_rows, nrows)) return fail(fn, why, -1);
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     const hipStream_t st = stream_of(p->engine, stream);
-    const long nblocks = blocks_of(nrows, p->block_rows);
+    const long nblocks = sp::ceil_div(nrows, p->block_rows);
     Cell* const cells = static_cast<Cell*>(p->d_work);
     int32_t* const ws_nkept = reinterpret_cast<int32_t*>(cells + p->max_blocks * p->nchan);
     const uint8_t* const mask = reinterpret_cast<const uint8_t*>(ws_nkept + p->max_blocks);
@@ -178,7 +155,7 @@ int rtlws_clean_run(rtlws_clean_plan* p, const float* d_rows, long in_stride, lo
     s1.cells = cells;
     s1.in_stride = in_stride, s1.nrows = nrows;
     s1.nchan = p->nchan, s1.block_rows = p->block_rows, s1.groups = chan_groups(p->nchan);
-    err = launch_stats(s1, nblocks, st);
+    hipError_t err = launch_stats(s1, nblocks, st);
     if (err != hipSuccess) return fail_hip(fn, "kernel launch (stage 1)", err);
     FlagParams s2{};
     s2.cells = cells;

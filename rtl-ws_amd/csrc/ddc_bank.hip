@@ -129,14 +129,10 @@ hipError_t launch_bank(const BankParams& p, hipStream_t st)
     return with_kernel(pick, p.cic_r, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  A plan does
-// not know cic_r: every instantiation
+// load_kernel (rtlws_internal.h).  A plan does not know cic_r: every instantiation
 hipError_t prepare_bank()
 {
-    return with_kernel(visit_all, 0, [](auto kernel) {
-        hipFuncAttributes a;
-        return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
-    });
+    return with_kernel(visit_all, 0, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace ddc

@@ -35,10 +35,7 @@ const char* rtlws_ddc_last_error(void) { return g_err.c_str(); }
 
 int rtlws_ddc_supported(int cic_r, int nchannels)
 {
-    g_err.clear();
-    const char* why = why_not(cic_r, nchannels, 0);
-    if (why) fail("rtlws_ddc", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_ddc", why_not(cic_r, nchannels, 0));
 }
 
 int rtlws_ddc_table(int16_t* cos_sin)

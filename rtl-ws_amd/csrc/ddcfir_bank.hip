@@ -129,13 +129,12 @@ hipError_t launch_bank(const FirParams& p, hipStream_t st)
                        [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), lds, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  The largest
-// launch asks for 64 KiB of dynamic LDS, the most that lds_opt_in (rtlws_internal.h) passes without raising a limit
+// load_kernel (rtlws_internal.h) for the kernel of a filter.  The largest launch asks for 64 KiB of dynamic LDS, the most
+// that lds_opt_in passes without raising a limit
 hipError_t prepare_bank(int decim, int ntaps, int device)
 {
     return with_kernel(decim, ntaps, [&](auto kernel) {
-        hipFuncAttributes a;
-        const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
+        const hipError_t e = load_kernel(kernel);
         return e != hipSuccess ? e : lds_opt_in(kernel, device, (size_t)lds_bytes(MAX_TAPS, MAX_CH));
     });
 }

@@ -45,11 +45,9 @@ const char* rtlws_ddcfir_last_error(void) { return g_err.c_str(); }
 
 int rtlws_ddcfir_supported(int decim, int ntaps, int nchannels)
 {
-    g_err.clear();
     const char* why = why_not_filter(decim, ntaps);
     if (!why) why = ddc::why_not_channels(nchannels);
-    if (why) fail("rtlws_ddcfir", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_ddcfir", why);
 }
 
 long rtlws_ddcfir_samples_needed(int decim, int ntaps, long dec_len)

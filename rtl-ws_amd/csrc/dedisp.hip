@@ -151,13 +151,10 @@ hipError_t launch_dedisp(const Layout& l, const Params& p, hipStream_t st)
     return with_kernel(l, [&](auto kernel) { return launch(kernel, dim3((unsigned)blocks), dim3(THREADS), 0, st, p); });
 }
 
-// hipFuncGetAttributes loads the code object on the current device, so that a launch makes no other call
+// load_kernel (rtlws_internal.h) for the kernel of a form
 hipError_t prepare_dedisp(const Layout& l)
 {
-    return with_kernel(l, [](auto kernel) {
-        hipFuncAttributes a;
-        return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
-    });
+    return with_kernel(l, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace dedisp

@@ -12,12 +12,10 @@
 
 #include "dedisp.h"
 #include "rtlws_dedisp.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
 // The form the table took and its tables on the engine's device
-struct rtlws_dedisp_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_dedisp_plan : rtlws::search::Plan {
     int nchan, ntrials, max_delay;
     rtlws::dedisp::Layout layout;
     int2* d_units;
@@ -27,15 +25,16 @@ struct rtlws_dedisp_plan {
 namespace {
 
 using namespace rtlws::dedisp;
+namespace sp = rtlws::search;
 
 static_assert(MIN_NCHAN == RTLWS_DEDISP_MIN_NCHAN && MAX_NCHAN == RTLWS_DEDISP_MAX_NCHAN && MAX_TRIALS == RTLWS_DEDISP_MAX_TRIALS &&
-                  MAX_DELAY == RTLWS_DEDISP_MAX_DELAY,
-              "rtlws_dedisp.h and dedisp.h disagree");
+                  MAX_DELAY == RTLWS_DEDISP_MAX_DELAY && MIN_NCHAN == sp::MIN_NCHAN && MAX_NCHAN == sp::MAX_NCHAN,
+              "rtlws_dedisp.h, dedisp.h and search_plan.h disagree");
 
 // ---- the rules, each worded once ----
 const char* why_not_shape(int nchan, int ntrials)
 {
-    if (nchan < MIN_NCHAN || nchan > MAX_NCHAN || nchan % 4) return "nchan must be 4 .. 4096 and a multiple of 4";
+    if (const char* why = sp::why_not_nchan(nchan)) return why;
     if (ntrials < 1 || ntrials > MAX_TRIALS) return "ntrials must be 1 .. 4096";
     return nullptr;
 }
@@ -58,12 +57,9 @@ const char* why_not_table(int nchan, int ntrials, const int32_t* delays, const u
 
 const char* why_not_nout(long nout) { return nout < 0 ? "nout must be >= 0" : nullptr; }
 
-long groups_of(int ntrials, int trials) { return (ntrials + trials - 1) / trials; }
+long groups_of(int ntrials, int trials) { return sp::ceil_div(ntrials, trials); }
 
-const char* why_not_grid(long nout, int ntrials, const Layout& l)
-{
-    return (nout + TILE_OUT - 1) / TILE_OUT > INT_MAX / groups_of(ntrials, l.trials) ? "more workgroups than one grid holds" : nullptr;
-}
+const char* why_not_grid(long nout, int ntrials, const Layout& l) { return sp::why_not_grid(sp::ceil_div(nout, TILE_OUT), groups_of(ntrials, l.trials)); }
 
 // ---- the form of a table ----
 // The least and the largest delay of positions i0 .. i0 + width - 1 under trials t0 .. t0 + trials - 1 (those of them
@@ -144,25 +140,13 @@ void build_tables(int nchan, int ntrials, const int32_t* delays, const uint8_t* 
         }
 }
 
-void free_tables(int2* d_units, int* d_rel)
-{
-    if (d_units) (void)hipFree(d_units);
-    if (d_rel) (void)hipFree(d_rel);
-}
-
 }  // namespace
 
 extern "C" {
 
 const char* rtlws_dedisp_last_error(void) { return g_err.c_str(); }
 
-int rtlws_dedisp_supported(int nchan, int ntrials)
-{
-    g_err.clear();
-    const char* why = why_not_shape(nchan, ntrials);
-    if (why) fail("rtlws_dedisp", why, 0);
-    return why ? 0 : 1;
-}
+int rtlws_dedisp_supported(int nchan, int ntrials) { return supported("rtlws_dedisp", why_not_shape(nchan, ntrials)); }
 
 int rtlws_dedisp_delays(int nchan, int shifted, double f_centre_hz, double bandwidth_hz, double row_seconds, int ntrials,
                         double dm0, double dm_step, int32_t* delays)
@@ -172,19 +156,9 @@ int rtlws_dedisp_delays(int nchan, int shifted, double f_centre_hz, double bandw
     if (const char* why = why_not_shape(nchan, ntrials)) return fail(fn, why, -1);
     if (shifted != 0 && shifted != 1) return fail(fn, "shifted must be 0 or 1", -1);
     if (!delays) return fail(fn, "null delays", -1);
-    if (!(std::isfinite(bandwidth_hz) && bandwidth_hz > 0.0)) return fail(fn, "bandwidth_hz must be finite and > 0", -1);
-    if (!(std::isfinite(row_seconds) && row_seconds > 0.0)) return fail(fn, "row_seconds must be finite and > 0", -1);
+    if (const char* why = sp::why_not_band(nchan, f_centre_hz, bandwidth_hz, row_seconds)) return fail(fn, why, -1);
     const int M = nchan;
-    // the lowest channel is c = M / 2, half the band below the centre
-    if (!(std::isfinite(f_centre_hz) && f_centre_hz + (double)(M / 2 - M) * bandwidth_hz / (double)M > 0.0))
-        return fail(fn, "every channel's frequency must be finite and > 0", -1);
-    std::vector<double> excess(M);                            // nu_i^-2 - nu_max^-2, nu in MHz
-    const double top = (f_centre_hz + (double)(M / 2 - 1) * bandwidth_hz / (double)M) / 1e6;
-    for (int i = 0; i < M; ++i) {
-        const int c = shifted ? (i + M / 2) % M : i;
-        const double nu = (f_centre_hz + (double)(c < M / 2 ? c : c - M) * bandwidth_hz / (double)M) / 1e6;
-        excess[i] = 1.0 / (nu * nu) - 1.0 / (top * top);
-    }
+    const std::vector<double> excess = sp::excess(M, shifted, f_centre_hz, bandwidth_hz);
     for (int t = 0; t < ntrials; ++t) {
         const double dm = dm0 + (double)t * dm_step;
         char buf[96];
@@ -193,7 +167,7 @@ int rtlws_dedisp_delays(int nchan, int shifted, double f_centre_hz, double bandw
             return fail(fn, buf, -1);
         }
         for (int i = 0; i < M; ++i) {
-            const double d = std::rint(4.148808e3 * dm * excess[i] / row_seconds);
+            const double d = std::rint(sp::DISPERSION * dm * excess[i] / row_seconds);
             if (!(d <= (double)MAX_DELAY)) {
                 snprintf(buf, sizeof buf, "trial %d: a delay above 65535 rows", t);
                 return fail(fn, buf, -1);
@@ -214,7 +188,7 @@ int rtlws_dedisp_geometry(int nchan, int ntrials, const int32_t* delays, const u
     if (const char* why = why_not_nout(nout)) return fail(fn, why, -1);
     const Layout l = choose_layout(nchan, ntrials, delays, mask);
     if (const char* why = why_not_grid(nout, ntrials, l)) return fail(fn, why, -1);
-    if (blocks) *blocks = (int)((nout + TILE_OUT - 1) / TILE_OUT * groups_of(ntrials, l.trials));
+    if (blocks) *blocks = (int)(sp::ceil_div(nout, TILE_OUT) * groups_of(ntrials, l.trials));
     if (threads) *threads = THREADS;
     if (lds_bytes) *lds_bytes = rtlws::dedisp::lds_bytes(l);
     if (tile_out) *tile_out = TILE_OUT;
@@ -225,36 +199,22 @@ int rtlws_dedisp_geometry(int nchan, int ntrials, const int32_t* delays, const u
 
 rtlws_dedisp_plan* rtlws_dedisp_open(rtlws_engine* e, int nchan, int ntrials, const int32_t* delays, const uint8_t* mask)
 {
-    const char* fn = "rtlws_dedisp_open";
-    g_err.clear();
     int most = 0;
-    const int device = open_device(fn, why_not_table(nchan, ntrials, delays, mask, &most), e);
-    if (device < 0) return nullptr;
-    const Layout l = choose_layout(nchan, ntrials, delays, mask);
-    std::vector<int2> units;
-    std::vector<int> rel;
-    build_tables(nchan, ntrials, delays, mask, l, &units, &rel);
-    int2* d_units = nullptr;
-    int* d_rel = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_units), units.size() * sizeof(int2));
-    if (err == hipSuccess) err = hipMalloc(reinterpret_cast<void**>(&d_rel), rel.size() * sizeof(int));
-    if (err == hipSuccess) err = hipMemcpy(d_units, units.data(), units.size() * sizeof(int2), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d_rel, rel.data(), rel.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_dedisp(l);
-    if (err != hipSuccess) {
-        free_tables(d_units, d_rel);
-        fail_hip(fn, "the tables or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_dedisp_plan{e, device, nchan, ntrials, most, l, d_units, d_rel};
+    const char* why = why_not_table(nchan, ntrials, delays, mask, &most);
+    const auto fill = [&](rtlws_dedisp_plan& p) {
+        p.nchan = nchan, p.ntrials = ntrials, p.max_delay = most;
+        p.layout = choose_layout(nchan, ntrials, delays, mask);
+        std::vector<int2> units;
+        std::vector<int> rel;
+        build_tables(nchan, ntrials, delays, mask, p.layout, &units, &rel);
+        hipError_t err = sp::upload(&p.d_units, units.data(), units.size());
+        if (err == hipSuccess) err = sp::upload(&p.d_rel, rel.data(), rel.size());
+        return err == hipSuccess ? prepare_dedisp(p.layout) : err;
+    };
+    return sp::open_plan<rtlws_dedisp_plan>("rtlws_dedisp_open", why, e, fill, "the tables or the kernel", rtlws_dedisp_close);
 }
 
-void rtlws_dedisp_close(rtlws_dedisp_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) free_tables(p->d_units, p->d_rel);
-    delete p;
-}
+void rtlws_dedisp_close(rtlws_dedisp_plan* p) { sp::close_plan(p, &rtlws_dedisp_plan::d_units, &rtlws_dedisp_plan::d_rel); }
 
 long rtlws_dedisp_rows_needed(const rtlws_dedisp_plan* p, long nout)
 {
@@ -271,20 +231,19 @@ int rtlws_dedisp_run(rtlws_dedisp_plan* p, const float* d_rows, long in_stride, 
     g_err.clear();
     // what needs no plan: a row holds at least 4 values
     if (const char* why = why_not_nout(nout)) return fail(fn, why, -1);
-    if (in_stride < MIN_NCHAN) return fail(fn, "in_stride must be >= nchan", -1);
-    if (in_stride % 4) return fail(fn, "in_stride must be a multiple of 4", -1);
+    if (const char* why = sp::why_not_row_stride(in_stride, MIN_NCHAN)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_stride(in_stride)) return fail(fn, why, -1);
     if (out_stride < nout) return fail(fn, "out_stride must be >= nout", -1);
     if (nout > 0 && (!d_rows || !d_out)) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_rows) & 15u) return fail(fn, "d_rows must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(fn, "d_out must be 4-byte aligned", -1);
+    if (sp::misaligned(d_rows, 16)) return fail(fn, "d_rows must be 16-byte aligned", -1);
+    if (sp::misaligned(d_out, 4)) return fail(fn, "d_out must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
-    if (in_stride < p->nchan) return fail(fn, "in_stride must be >= nchan", -1);
+    if (const char* why = sp::why_not_row_stride(in_stride, p->nchan)) return fail(fn, why, -1);
     if (const char* why = why_not_grid(nout, p->ntrials, p->layout)) return fail(fn, why, -1);
     if (nout == 0) return 0;
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     Params kp;
     kp.rows = d_rows;
     kp.out = d_out;
@@ -299,7 +258,7 @@ int rtlws_dedisp_run(rtlws_dedisp_plan* p, const float* d_rows, long in_stride, 
     kp.ngroups = (int)groups_of(p->ntrials, p->layout.trials);
     kp.chunk = p->layout.chunk;
     kp.stride = p->layout.stride;
-    err = launch_dedisp(p->layout, kp, stream_of(p->engine, stream));
+    const hipError_t err = launch_dedisp(p->layout, kp, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }

@@ -227,14 +227,13 @@ hipError_t launch_merge(const Params& p, hipStream_t st)
     return launch(&ffa_merge, dim3((unsigned)((outputs + 255) / 256)), dim3(256), 0, st, p);
 }
 
-// hipFuncGetAttributes loads the code object on the current device, so that a launch makes no other call; the limit of
-// the pass kernels' dynamic LDS is raised once, to the most any plan takes
+// load_kernel (rtlws_internal.h) for the three kernels; the limit of the pass kernels' dynamic LDS is raised once, to the
+// most any plan takes
 hipError_t prepare(int device)
 {
-    hipFuncAttributes attr;
-    hipError_t err = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&ffa_pass<false>));
-    if (err == hipSuccess) err = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&ffa_pass<true>));
-    if (err == hipSuccess) err = hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&ffa_merge));
+    hipError_t err = load_kernel(&ffa_pass<false>);
+    if (err == hipSuccess) err = load_kernel(&ffa_pass<true>);
+    if (err == hipSuccess) err = load_kernel(&ffa_merge);
     if (err == hipSuccess) err = lds_opt_in(&ffa_pass<false>, device, LDS_CAP);
     if (err == hipSuccess) err = lds_opt_in(&ffa_pass<true>, device, LDS_CAP);
     return err;

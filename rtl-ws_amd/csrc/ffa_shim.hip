@@ -11,12 +11,10 @@
 
 #include "ffa.h"
 #include "rtlws_ffa.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
 // The table and the workspace on the engine's device
-struct rtlws_ffa_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_ffa_plan : rtlws::search::Plan {
     int p0, nper, L, nwidths, seg_log2, top;
     rtlws::ffa::Split split;
     int eval_log2;             // of the last pass
@@ -30,18 +28,14 @@ struct rtlws_ffa_plan {
 namespace {
 
 using namespace rtlws::ffa;
+namespace sp = rtlws::search;
+using sp::log2_of;
 
 static_assert(MIN_P == RTLWS_FFA_MIN_P && MAX_P == RTLWS_FFA_MAX_P && MAX_L == RTLWS_FFA_MAX_L && MAX_CELLS == RTLWS_FFA_MAX_CELLS &&
                   MAX_WIDTHS == RTLWS_FFA_MAX_WIDTHS && MAX_WIDTH == RTLWS_FFA_MAX_WIDTH && MAX_TRIALS == RTLWS_FFA_MAX_TRIALS &&
-                  MAX_PASSES == RTLWS_FFA_MAX_PASSES && WORKSPACE_CAP == RTLWS_FFA_WORKSPACE_CAP,
-              "rtlws_ffa.h and ffa.h disagree");
-
-int log2_of(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
+                  MAX_PASSES == RTLWS_FFA_MAX_PASSES && WORKSPACE_CAP == RTLWS_FFA_WORKSPACE_CAP && MAX_WIDTHS == sp::MAX_WIDTHS &&
+                  MAX_TRIALS == sp::MAX_TRIALS,
+              "rtlws_ffa.h, ffa.h and search_plan.h disagree");
 
 // ---- the rules, each worded once ----
 const char* why_not_plan(int p0, int nper, int L, int nwidths, const int32_t* widths, int seg)
@@ -51,19 +45,12 @@ const char* why_not_plan(int p0, int nper, int L, int nwidths, const int32_t* wi
     if (nper > MAX_P || p0 + nper - 1 > MAX_P) return "p0 + nper - 1 must be <= 1024";
     if (L < 1 || L > MAX_L) return "L must be 1 .. 12";
     if (((long)(p0 + nper - 1) << L) > MAX_CELLS) return "m * (p0 + nper - 1) must be <= 2^22";
-    if (nwidths < 1 || nwidths > MAX_WIDTHS) return "nwidths must be 1 .. 16";
-    if (!widths) return "null widths";
-    for (int k = 0; k < nwidths; ++k) {
-        if (widths[k] < 1 || widths[k] > MAX_WIDTH || widths[k] > p0) return "a width must be 1 .. min(256, p0)";
-        if (k && widths[k] <= widths[k - 1]) return "the widths must be strictly ascending";
-    }
+    if (const char* why = sp::why_not_widths(nwidths, widths, p0 < MAX_WIDTH ? p0 : MAX_WIDTH, "a width must be 1 .. min(256, p0)")) return why;
     if (seg < 1 || seg > (1 << L) || (seg & (seg - 1))) return "seg must be a power of two 1 .. m";
     return nullptr;
 }
 
 const char* why_not_max_trials(int max_trials) { return max_trials < 1 ? "max_trials must be >= 1" : nullptr; }
-
-const char* why_not_ntrials(int ntrials) { return ntrials < 1 || ntrials > MAX_TRIALS ? "ntrials must be 1 .. 65536" : nullptr; }
 
 // what a plan of these (served) arguments is, but for the device's side
 rtlws_ffa_plan shape_of(int p0, int nper, int L, int nwidths, const int32_t* widths, int seg, int max_trials)
@@ -116,10 +103,7 @@ const char* rtlws_ffa_last_error(void) { return g_err.c_str(); }
 
 int rtlws_ffa_supported(int p0, int nper, int L, int nwidths, const int32_t* widths, int seg)
 {
-    g_err.clear();
-    const char* why = why_not_plan(p0, nper, L, nwidths, widths, seg);
-    if (why) fail("rtlws_ffa", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_ffa", why_not_plan(p0, nper, L, nwidths, widths, seg));
 }
 
 int rtlws_ffa_geometry(int p0, int nper, int L, int nwidths, const int32_t* widths, int seg, int max_trials, int* passes,
@@ -146,37 +130,22 @@ int rtlws_ffa_geometry(int p0, int nper, int L, int nwidths, const int32_t* widt
 
 rtlws_ffa_plan* rtlws_ffa_open(rtlws_engine* e, int p0, int nper, int L, int nwidths, const int32_t* widths, int seg, int max_trials)
 {
-    const char* fn = "rtlws_ffa_open";
-    g_err.clear();
     const char* why = why_not_plan(p0, nper, L, nwidths, widths, seg);
     if (!why) why = why_not_max_trials(max_trials);
-    const int device = open_device(fn, why, e);
-    if (device < 0) return nullptr;
-    rtlws_ffa_plan* p = new rtlws_ffa_plan(shape_of(p0, nper, L, nwidths, widths, seg, max_trials));
-    p->engine = e, p->device = device;
-    int table[TABLE_WORDS] = {};
-    fill_table(nwidths, widths, table);
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&p->d_table), sizeof table);
-    if (err == hipSuccess) err = hipMemcpy(p->d_table, table, sizeof table, hipMemcpyHostToDevice);
-    if (err == hipSuccess && p->ws_bytes) err = hipMalloc(reinterpret_cast<void**>(&p->d_ws), p->ws_bytes);
-    if (err == hipSuccess) err = prepare(device);
-    if (err != hipSuccess) {
-        fail_hip(fn, "the table, the workspace or the kernels", err);
-        rtlws_ffa_close(p);
-        return nullptr;
-    }
-    return p;
+    const auto fill = [&](rtlws_ffa_plan& p) {
+        const sp::Plan head = p;                              // shape_of gives a whole plan but for the device's side
+        p = shape_of(p0, nper, L, nwidths, widths, seg, max_trials);
+        static_cast<sp::Plan&>(p) = head;
+        int table[TABLE_WORDS] = {};
+        fill_table(nwidths, widths, table);
+        hipError_t err = sp::upload(&p.d_table, table, TABLE_WORDS);
+        if (err == hipSuccess && p.ws_bytes) err = hipMalloc(reinterpret_cast<void**>(&p.d_ws), p.ws_bytes);
+        return err == hipSuccess ? prepare(p.device) : err;
+    };
+    return sp::open_plan<rtlws_ffa_plan>("rtlws_ffa_open", why, e, fill, "the table, the workspace or the kernels", rtlws_ffa_close);
 }
 
-void rtlws_ffa_close(rtlws_ffa_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) {
-        (void)hipFree(p->d_table);
-        (void)hipFree(p->d_ws);
-    }
-    delete p;
-}
+void rtlws_ffa_close(rtlws_ffa_plan* p) { sp::close_plan(p, &rtlws_ffa_plan::d_table, &rtlws_ffa_plan::d_ws); }
 
 long rtlws_ffa_samples_needed(const rtlws_ffa_plan* p)
 {
@@ -193,21 +162,20 @@ int rtlws_ffa_run(rtlws_ffa_plan* p, const float* d_in, long in_stride, int ntri
     const char* fn = "rtlws_ffa_run";
     g_err.clear();
     // what needs no plan
-    if (const char* why = why_not_ntrials(ntrials)) return fail(fn, why, -1);
-    if (in_stride % 4) return fail(fn, "in_stride must be a multiple of 4", -1);
+    if (const char* why = sp::why_not_ntrials(ntrials)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_stride(in_stride)) return fail(fn, why, -1);
     if (!d_in || !d_peak || !d_at) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_in) & 15u) return fail(fn, "d_in must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_peak) & 3u) return fail(fn, "d_peak must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_at) & 3u) return fail(fn, "d_at must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_prof) & 3u) return fail(fn, "d_prof must be 4-byte aligned", -1);
+    if (sp::misaligned(d_in, 16)) return fail(fn, "d_in must be 16-byte aligned", -1);
+    if (sp::misaligned(d_peak, 4)) return fail(fn, "d_peak must be 4-byte aligned", -1);
+    if (sp::misaligned(d_at, 4)) return fail(fn, "d_at must be 4-byte aligned", -1);
+    if (sp::misaligned(d_prof, 4)) return fail(fn, "d_prof must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     const int pitch = p->p0 + p->nper - 1;
     if (in_stride < ((long)pitch << p->L)) return fail(fn, "in_stride must be >= samples_needed", -1);
     if (d_prof && prof_stride < pitch) return fail(fn, "prof_stride must be >= p0 + nper - 1", -1);
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     const hipStream_t st = stream_of(p->engine, stream);
     const int passes = p->split.passes, last = p->split.stages[passes - 1];
     const size_t rows_bytes = (size_t)p->pairs * ((size_t)pitch << p->L) * sizeof(float);
@@ -236,13 +204,13 @@ int rtlws_ffa_run(rtlws_ffa_plan* p, const float* d_in, long in_stride, int ntri
             kp.from_series = pass == 0;
             kp.ws_src = reinterpret_cast<const float*>(p->d_ws + (size_t)(pass ? pass - 1 : 0) * rows_bytes);
             kp.ws_dst = reinterpret_cast<float*>(p->d_ws + (size_t)pass * rows_bytes);        // not the last pass's
-            err = launch_pass(kp, pass == passes - 1, lds_of(*p, pass), st);
+            const hipError_t err = launch_pass(kp, pass == passes - 1, lds_of(*p, pass), st);
             if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
             kp.a += kp.n;
         }
         if (p->merge) {
             kp.n = last;
-            err = launch_merge(kp, st);
+            const hipError_t err = launch_merge(kp, st);
             if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
         }
     }
@@ -257,11 +225,8 @@ double rtlws_ffa_period(int p, int s, int L)
 
 double rtlws_ffa_snr(double peak, int width, int rows, double sum1, double sum2, long count)
 {
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (count < 2 || width < 1 || rows < 1) return nan;
-    const double mean = sum1 / (double)count;
-    const double var = sum2 / (double)count - mean * mean;
-    if (!(var > 0.0)) return nan;
+    double mean, var;
+    if (width < 1 || rows < 1 || !sp::moments(sum1, sum2, count, &mean, &var)) return std::numeric_limits<double>::quiet_NaN();
     const double n = (double)width * (double)rows;
     return (peak - n * mean) / std::sqrt(n * var);
 }

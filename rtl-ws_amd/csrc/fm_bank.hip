@@ -202,15 +202,13 @@ hipError_t launch_state_copy(const float* state_in, float* state_out, int nfloat
     return hipGetLastError();
 }
 
-// hipFuncGetAttributes loads the code object of the current device: a launch then makes no other call.  The LDS of
-// the kernels is static (above 64 KiB, within the CU's 160 KiB): there is no limit to raise.  A plan does not know
-// cic_r: every instantiation, after the state copy
+// load_kernel (rtlws_internal.h).  The LDS of the kernels is static (above 64 KiB, within the CU's 160 KiB): there is no
+// limit to raise.  A plan does not know cic_r: every instantiation, after the state copy
 hipError_t prepare_bank()
 {
-    hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_bank_state_copy_kernel));
+    const hipError_t e = load_kernel(&fm_bank_state_copy_kernel);
     if (e != hipSuccess) return e;
-    return with_kernel(visit_all, 0, [&](auto kernel) { return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel)); });
+    return with_kernel(visit_all, 0, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace fmbank

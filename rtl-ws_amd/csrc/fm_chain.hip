@@ -22,6 +22,7 @@
 #include "fm_chain.h"
 #include "fm_maps.h"
 #include "fm_math.h"
+#include "rtlws_internal.h"
 
 namespace rtlws {
 namespace fm {
@@ -269,17 +270,14 @@ hipError_t launch_state_copy(const float* state_in, float* state_out, hipStream_
 template <int SRC>
 static hipError_t prepare_src()
 {
-    hipFuncAttributes a;
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_chain_kernel<SRC, true>));
-    if (e == hipSuccess) e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_chain_kernel<SRC, false>));
-    return e;
+    const hipError_t e = load_kernel(&fm_chain_kernel<SRC, true>);
+    return e == hipSuccess ? load_kernel(&fm_chain_kernel<SRC, false>) : e;
 }
 
-// hipFuncGetAttributes loads the code object of the current device: the first launch then makes no other call
+// load_kernel (rtlws_internal.h) for every instantiation: the first launch then makes no other call
 hipError_t prepare_chain()
 {
-    hipFuncAttributes a;
-    hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&fm_state_copy_kernel));
+    hipError_t e = load_kernel(&fm_state_copy_kernel);
     if (e == hipSuccess) e = prepare_src<SRC_CS32>();
     if (e == hipSuccess) e = prepare_src<SRC_CU8_8>();
     if (e == hipSuccess) e = prepare_src<SRC_CU8_10>();

@@ -76,10 +76,7 @@ const char* rtlws_fm_last_error(void) { return g_err.c_str(); }
 
 int rtlws_fm_supported(int block_len, long nblocks, int cic_r)
 {
-    g_err.clear();
-    const char* why = why_not(block_len, nblocks, cic_r, cic_r != 0);
-    if (why) fail("rtlws_fm", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_fm", why_not(block_len, nblocks, cic_r, cic_r != 0));
 }
 
 int rtlws_fm_grid(int block_len, long nblocks, int cic_r, int* blocks, int* threads, int* lds_bytes, int* tile_audio)

@@ -53,10 +53,7 @@ const char* rtlws_fmbank_last_error(void) { return g_err.c_str(); }
 
 int rtlws_fmbank_supported(int cic_r, int nchannels, int block_len, long nblocks)
 {
-    g_err.clear();
-    const char* why = why_not(cic_r, nchannels, block_len, nblocks);
-    if (why) fail("rtlws_fmbank", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_fmbank", why_not(cic_r, nchannels, block_len, nblocks));
 }
 
 int rtlws_fmbank_grid(int cic_r, int nchannels, int block_len, long nblocks, int* blocks, int* threads, int* lds_bytes,

@@ -77,10 +77,7 @@ const char* rtlws_fmfir_last_error(void) { return g_err.c_str(); }
 
 int rtlws_fmfir_supported(int decim, int ntaps, int nchannels, int block_len, long nblocks)
 {
-    g_err.clear();
-    const char* why = why_not(decim, ntaps, nchannels, block_len, nblocks);
-    if (why) fail("rtlws_fmfir", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_fmfir", why_not(decim, ntaps, nchannels, block_len, nblocks));
 }
 
 long rtlws_fmfir_samples_needed(int decim, int ntaps, int block_len, long nblocks)

@@ -28,13 +28,10 @@ hipError_t launch_fold(const Params& p, int ntrials, hipStream_t st)
     });
 }
 
-// hipFuncGetAttributes loads the code object on the current device, so that a launch makes no other call
+// load_kernel (rtlws_internal.h) for the kernel of a bin count
 hipError_t prepare_fold(int nbins)
 {
-    return with_kernel(nbins, [](auto kernel) {
-        hipFuncAttributes a;
-        return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
-    });
+    return with_kernel(nbins, [](auto kernel) { return load_kernel(kernel); });
 }
 
 }  // namespace fold

@@ -4,19 +4,16 @@
 // reads the environment, and nothing of a run is computed on the host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <limits>
 
 #include "fold.h"
 #include "rtlws_fold.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
 // The two tables on the engine's device
-struct rtlws_fold_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_fold_plan : rtlws::search::Plan {
     int nperiods, nbins;
     long sub;
     uint64_t* d_tables;        // steps, then phases
@@ -25,18 +22,20 @@ struct rtlws_fold_plan {
 namespace {
 
 using namespace rtlws::fold;
+namespace sp = rtlws::search;
 
 static_assert(MAX_PERIODS == RTLWS_FOLD_MAX_PERIODS && MIN_BINS == RTLWS_FOLD_MIN_BINS && MAX_BINS == RTLWS_FOLD_MAX_BINS &&
                   MIN_SUB == RTLWS_FOLD_MIN_SUB && MAX_SUB == RTLWS_FOLD_MAX_SUB && MAX_TRIALS == RTLWS_FOLD_MAX_TRIALS &&
-                  MAX_NSAMP == RTLWS_FOLD_MAX_NSAMP,
-              "rtlws_fold.h and fold.h disagree");
+                  MAX_NSAMP == RTLWS_FOLD_MAX_NSAMP && MIN_BINS == sp::MIN_BINS && MAX_BINS == sp::MAX_BINS &&
+                  MAX_TRIALS == sp::MAX_TRIALS && MAX_NSAMP == sp::MAX_NSAMP,
+              "rtlws_fold.h, fold.h and search_plan.h disagree");
 
 // ---- the rules, each worded once ----
 const char* why_not_nperiods(int nperiods) { return nperiods < 1 || nperiods > MAX_PERIODS ? "nperiods must be 1 .. 4096" : nullptr; }
 
 const char* why_not_shape(int nbins, long sub)
 {
-    if (nbins < MIN_BINS || nbins > MAX_BINS) return "nbins must be 2 .. 256";
+    if (const char* why = sp::why_not_nbins(nbins)) return why;
     if (sub < MIN_SUB || sub > MAX_SUB || sub % 4) return "sub must be 64 .. 16777216 and a multiple of 4";
     return nullptr;
 }
@@ -44,22 +43,15 @@ const char* why_not_shape(int nbins, long sub)
 const char* why_not_tables(int nperiods, const uint64_t* steps, const uint64_t* phases, int nbins, long sub)
 {
     if (const char* why = why_not_nperiods(nperiods)) return why;
-    if (!steps) return "null steps";
-    if (!phases) return "null phases";
+    if (const char* why = sp::why_not_steps(steps, phases)) return why;
     return why_not_shape(nbins, sub);
 }
 
-const char* why_not_ntrials(int ntrials) { return ntrials < 1 || ntrials > MAX_TRIALS ? "ntrials must be 1 .. 65536" : nullptr; }
-
-const char* why_not_nsamp(long nsamp) { return nsamp < 0 || nsamp > MAX_NSAMP ? "nsamp must be 0 .. 2^30" : nullptr; }
-
-long subints_of(long nsamp, long sub) { return (nsamp + sub - 1) / sub; }
-
-int groups_of(int nperiods, int nbins) { return (nperiods + LANES * waves_per_block(nbins) - 1) / (LANES * waves_per_block(nbins)); }
+int groups_of(int nperiods, int nbins) { return (int)sp::ceil_div(nperiods, LANES * waves_per_block(nbins)); }
 
 const char* why_not_grid(int nperiods, int nbins, long sub, int ntrials, long nsamp)
 {
-    return subints_of(nsamp, sub) > INT_MAX / ((long)ntrials * groups_of(nperiods, nbins)) ? "more workgroups than one grid holds" : nullptr;
+    return sp::why_not_grid(sp::ceil_div(nsamp, sub), (long)ntrials * groups_of(nperiods, nbins));
 }
 
 }  // namespace
@@ -70,10 +62,7 @@ const char* rtlws_fold_last_error(void) { return g_err.c_str(); }
 
 int rtlws_fold_supported(int nperiods, const uint64_t* steps, const uint64_t* phases, int nbins, long sub)
 {
-    g_err.clear();
-    const char* why = why_not_tables(nperiods, steps, phases, nbins, sub);
-    if (why) fail("rtlws_fold", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_fold", why_not_tables(nperiods, steps, phases, nbins, sub));
 }
 
 int rtlws_fold_geometry(int nperiods, int nbins, long sub, int ntrials, long nsamp, int* blocks, int* threads, int* lds, int* tile,
@@ -83,52 +72,41 @@ int rtlws_fold_geometry(int nperiods, int nbins, long sub, int ntrials, long nsa
     g_err.clear();
     if (const char* why = why_not_nperiods(nperiods)) return fail(fn, why, -1);
     if (const char* why = why_not_shape(nbins, sub)) return fail(fn, why, -1);
-    if (const char* why = why_not_ntrials(ntrials)) return fail(fn, why, -1);
-    if (const char* why = why_not_nsamp(nsamp)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_ntrials(ntrials)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_nsamp(nsamp)) return fail(fn, why, -1);
     if (const char* why = why_not_grid(nperiods, nbins, sub, ntrials, nsamp)) return fail(fn, why, -1);
-    if (blocks) *blocks = (int)(subints_of(nsamp, sub) * ntrials * groups_of(nperiods, nbins));
+    if (blocks) *blocks = (int)(sp::ceil_div(nsamp, sub) * ntrials * groups_of(nperiods, nbins));
     if (threads) *threads = LANES * waves_per_block(nbins);
     if (lds) *lds = lds_bytes(nbins);
     if (tile) *tile = TILE;
     if (wpb) *wpb = waves_per_block(nbins);
-    if (nsub) *nsub = subints_of(nsamp, sub);
+    if (nsub) *nsub = sp::ceil_div(nsamp, sub);
     return 0;
 }
 
 rtlws_fold_plan* rtlws_fold_open(rtlws_engine* e, int nperiods, const uint64_t* steps, const uint64_t* phases, int nbins, long sub)
 {
-    const char* fn = "rtlws_fold_open";
-    g_err.clear();
-    const int device = open_device(fn, why_not_tables(nperiods, steps, phases, nbins, sub), e);
-    if (device < 0) return nullptr;
-    const size_t bytes = (size_t)nperiods * sizeof(uint64_t);
-    uint64_t* d_tables = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_tables), 2 * bytes);
-    if (err == hipSuccess) err = hipMemcpy(d_tables, steps, bytes, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = hipMemcpy(d_tables + nperiods, phases, bytes, hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_fold(nbins);
-    if (err != hipSuccess) {
-        if (d_tables) (void)hipFree(d_tables);
-        fail_hip(fn, "the tables or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_fold_plan{e, device, nperiods, nbins, sub, d_tables};
+    const auto fill = [&](rtlws_fold_plan& p) {
+        p.nperiods = nperiods, p.nbins = nbins, p.sub = sub;
+        const size_t bytes = (size_t)nperiods * sizeof(uint64_t);
+        hipError_t err = hipMalloc(reinterpret_cast<void**>(&p.d_tables), 2 * bytes);
+        if (err == hipSuccess) err = hipMemcpy(p.d_tables, steps, bytes, hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMemcpy(p.d_tables + nperiods, phases, bytes, hipMemcpyHostToDevice);
+        return err == hipSuccess ? prepare_fold(nbins) : err;
+    };
+    return sp::open_plan<rtlws_fold_plan>("rtlws_fold_open", why_not_tables(nperiods, steps, phases, nbins, sub), e, fill, "the tables or the kernel",
+                                          rtlws_fold_close);
 }
 
-void rtlws_fold_close(rtlws_fold_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_tables);
-    delete p;
-}
+void rtlws_fold_close(rtlws_fold_plan* p) { sp::close_plan(p, &rtlws_fold_plan::d_tables); }
 
 long rtlws_fold_subints(const rtlws_fold_plan* p, long nsamp)
 {
     const char* fn = "rtlws_fold_subints";
     g_err.clear();
-    if (const char* why = why_not_nsamp(nsamp)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_nsamp(nsamp)) return fail(fn, why, -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
-    return subints_of(nsamp, p->sub);
+    return sp::ceil_div(nsamp, p->sub);
 }
 
 int rtlws_fold_run(rtlws_fold_plan* p, const float* d_in, long in_stride, int ntrials, long nsamp, float* d_prof, uint32_t* d_hits,
@@ -137,21 +115,20 @@ int rtlws_fold_run(rtlws_fold_plan* p, const float* d_in, long in_stride, int nt
     const char* fn = "rtlws_fold_run";
     g_err.clear();
     // what needs no plan
-    if (const char* why = why_not_ntrials(ntrials)) return fail(fn, why, -1);
-    if (const char* why = why_not_nsamp(nsamp)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_ntrials(ntrials)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_nsamp(nsamp)) return fail(fn, why, -1);
     if (in_stride < nsamp) return fail(fn, "in_stride must be >= nsamp", -1);
-    if (in_stride % 4) return fail(fn, "in_stride must be a multiple of 4", -1);
+    if (const char* why = sp::why_not_stride(in_stride)) return fail(fn, why, -1);
     if (nsamp > 0 && (!d_in || !d_prof)) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_in) & 15u) return fail(fn, "d_in must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_prof) & 3u) return fail(fn, "d_prof must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_hits) & 3u) return fail(fn, "d_hits must be 4-byte aligned", -1);
+    if (sp::misaligned(d_in, 16)) return fail(fn, "d_in must be 16-byte aligned", -1);
+    if (sp::misaligned(d_prof, 4)) return fail(fn, "d_prof must be 4-byte aligned", -1);
+    if (sp::misaligned(d_hits, 4)) return fail(fn, "d_hits must be 4-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     if (const char* why = why_not_grid(p->nperiods, p->nbins, p->sub, ntrials, nsamp)) return fail(fn, why, -1);
     if (nsamp == 0) return 0;
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     Params kp;
     kp.in = d_in;
     kp.prof = d_prof;
@@ -161,11 +138,11 @@ int rtlws_fold_run(rtlws_fold_plan* p, const float* d_in, long in_stride, int nt
     kp.in_stride = in_stride;
     kp.nsamp = nsamp;
     kp.sub = p->sub;
-    kp.nsub = subints_of(nsamp, p->sub);
+    kp.nsub = sp::ceil_div(nsamp, p->sub);
     kp.nperiods = p->nperiods;
     kp.nbins = p->nbins;
     kp.groups = groups_of(p->nperiods, p->nbins);
-    err = launch_fold(kp, ntrials, stream_of(p->engine, stream));
+    const hipError_t err = launch_fold(kp, ntrials, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }
@@ -187,10 +164,8 @@ uint64_t rtlws_fold_phase_at(uint64_t step, uint64_t phi0, long n0) { return phi
 double rtlws_fold_chi2(const float* prof, const uint32_t* hits, int nbins, double sum1, double sum2, long count)
 {
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (count < 2 || nbins < 1 || !prof || !hits) return nan;
-    const double mean = sum1 / (double)count;
-    const double var = sum2 / (double)count - mean * mean;
-    if (!(var > 0.0)) return nan;
+    double mean, var;
+    if (nbins < 1 || !prof || !hits || !sp::moments(sum1, sum2, count, &mean, &var)) return nan;
     double chi2 = 0.0;
     for (int b = 0; b < nbins; ++b) {
         if (hits[b] == 0) return nan;

@@ -88,10 +88,7 @@ const char* rtlws_long_last_error(void) { return g_err.c_str(); }
 
 int rtlws_long_supported(const rtlws_spectra_desc* desc)
 {
-    g_err.clear();
-    const char* why = why_not(desc);
-    if (why) g_err = std::string("rtlws_long: ") + why;
-    return why ? 0 : 1;
+    return supported("rtlws_long", why_not(desc));
 }
 
 rtlws_long_plan* rtlws_long_open(rtlws_engine* e, const rtlws_spectra_desc* desc, long max_frames)

@@ -241,8 +241,7 @@ hipError_t launch_period(int log2n, const Params& p, int ntrials, hipStream_t st
 hipError_t prepare_period(int log2n, int device)
 {
     return pick(Log2Ns{}, log2n, [&](auto n) {
-        hipFuncAttributes a;
-        const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&period_kernel<decltype(n)::value>));
+        const hipError_t e = load_kernel(&period_kernel<decltype(n)::value>);
         return e != hipSuccess ? e : lds_opt_in(&period_kernel<decltype(n)::value>, device, (size_t)lds_bytes(decltype(n)::value));
     });
 }

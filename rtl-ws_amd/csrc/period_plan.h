@@ -15,7 +15,7 @@
 #include "period.h"
 #include "periodlong.h"
 #include "rtlws_periodlong.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
 namespace rtlws {
 namespace periodlong {
@@ -45,23 +45,15 @@ static_assert(pl::MIN_LOG2N == RTLWS_PERIODLONG_MIN_LOG2N && pl::MAX_LOG2N == RT
                   pl::MAX_TRIALS == RTLWS_PERIODLONG_MAX_TRIALS && pl::STAGES == RTLWS_PERIODLONG_STAGES,
               "rtlws_periodlong.h and periodlong.h disagree");
 static_assert(pl::trial_bytes(pl::MAX_LOG2N) <= RTLWS_PERIODLONG_WORKSPACE_CAP, "the cap holds a trial of every frame length");
-static_assert(pl::MAX_TRIALS == rtlws::period::MAX_TRIALS, "one rule of ntrials for the family");
+static_assert(pl::MAX_TRIALS == rtlws::period::MAX_TRIALS && pl::MAX_TRIALS == rtlws::search::MAX_TRIALS, "one rule of ntrials for the series");
+
+// the rule of ntrials and log2_of are search_plan.h's, which words them for every library over the dedispersed series
+using rtlws::search::log2_of;
+using rtlws::search::why_not_ntrials;
 
 [[maybe_unused]] bool power_of_two(int v) { return v > 0 && !(v & (v - 1)); }
 
-[[maybe_unused]] int log2_of(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 // ---- the family's rules, each worded once ----
-[[maybe_unused]] const char* why_not_ntrials(int ntrials)
-{
-    return ntrials < 1 || ntrials > pl::MAX_TRIALS ? "ntrials must be 1 .. 65536" : nullptr;
-}
-
 // what every run refuses first: the trials, nsamp against the library's largest frame (why_nsamp words that limit), the
 // stride
 [[maybe_unused]] const char* why_not_input(int ntrials, int nsamp, int max_log2n, const char* why_nsamp, long in_stride)

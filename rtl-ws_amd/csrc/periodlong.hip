@@ -273,21 +273,19 @@ hipError_t launch_group(const Params& p, int group, hipStream_t st)
 hipError_t prepare(int log2n, int device)
 {
     const int l1 = log2m1_of(log2n), l2 = log2m2_of(log2n);
-    hipFuncAttributes a;
-    // asking for a kernel's attributes loads its code object: nothing is left to load under a capture
-    for (const void* k : {reinterpret_cast<const void*>(&mean_kernel), reinterpret_cast<const void*>(&cols16_kernel),
-                          reinterpret_cast<const void*>(&cols256_kernel), reinterpret_cast<const void*>(&whiten_kernel),
-                          reinterpret_cast<const void*>(&peaks_kernel)}) {
-        const hipError_t e = hipFuncGetAttributes(&a, k);
-        if (e != hipSuccess) return e;
-    }
-    hipError_t e = pick(Log2M2s{}, l2, [&](auto m) {
-        const hipError_t g = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&rows_kernel<decltype(m)::value>));
+    hipError_t e = load_kernel(&mean_kernel);
+    if (e == hipSuccess) e = load_kernel(&cols16_kernel);
+    if (e == hipSuccess) e = load_kernel(&cols256_kernel);
+    if (e == hipSuccess) e = load_kernel(&whiten_kernel);
+    if (e == hipSuccess) e = load_kernel(&peaks_kernel);
+    if (e != hipSuccess) return e;
+    e = pick(Log2M2s{}, l2, [&](auto m) {
+        const hipError_t g = load_kernel(&rows_kernel<decltype(m)::value>);
         return g != hipSuccess ? g : lds_opt_in(&rows_kernel<decltype(m)::value>, device, (size_t)rows_lds(decltype(m)::value));
     });
     if (e != hipSuccess) return e;
     return pick(Log2M1s{}, l1, [&](auto m) {
-        const hipError_t g = hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&untangle_kernel<decltype(m)::value>));
+        const hipError_t g = load_kernel(&untangle_kernel<decltype(m)::value>);
         return g != hipSuccess ? g : lds_opt_in(&untangle_kernel<decltype(m)::value>, device, (size_t)untangle_lds(decltype(m)::value));
     });
 }

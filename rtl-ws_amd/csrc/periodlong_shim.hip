@@ -21,10 +21,7 @@ const char* rtlws_periodlong_last_error(void) { return g_err.c_str(); }
 
 int rtlws_periodlong_supported(int log2n, int levels, int norm, int seg, int klo)
 {
-    g_err.clear();
-    const char* why = why_not_long_plan(log2n, levels, norm, seg, klo);
-    if (why) fail("rtlws_periodlong", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_periodlong", why_not_long_plan(log2n, levels, norm, seg, klo));
 }
 
 int rtlws_periodlong_geometry(int log2n, int levels, int norm, int seg, int klo, int ntrials, int* blocks, int* threads, int* lds,

@@ -36,10 +36,7 @@ const char* rtlws_pfb_last_error(void) { return g_err.c_str(); }
 
 int rtlws_pfb_supported(int log2_channels, int taps_per_branch, int hop)
 {
-    g_err.clear();
-    const char* why = hop == 0 ? "hop must be M or M / 2" : why_not(log2_channels, taps_per_branch, hop, 0);
-    if (why) fail("rtlws_pfb", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_pfb", hop == 0 ? "hop must be M or M / 2" : why_not(log2_channels, taps_per_branch, hop, 0));
 }
 
 int rtlws_pfb_design(int log2_channels, int taps_per_branch, int16_t* taps)

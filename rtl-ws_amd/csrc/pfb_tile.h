@@ -191,15 +191,8 @@ __device__ __forceinline__ void tile_passes(const PfbParams& p, long m0, int tid
 using Log2Ms = Vals<4, 5, 6, 7, 8, 9, 10>;
 static_assert(MIN_LOG2_M == 4 && MAX_LOG2_M == 10, "pfb_bank.h and the launch tables disagree");
 
-// A plan's prepare step: hipFuncGetAttributes loads the code object of the current device, so that a launch makes no
-// other call.  The tiles are static LDS, which a launch takes up to the 160 KiB of a compute unit as it is: the
-// opt-in of lds_opt_in (rtlws_internal.h) is for dynamic LDS and has nothing to raise here
-template <typename P>
-hipError_t load_kernel(void (*kernel)(P))
-{
-    hipFuncAttributes a;
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
-}
+// A plan's prepare step is load_kernel (rtlws_internal.h) alone.  The tiles are static LDS, which a launch takes up to the
+// 160 KiB of a compute unit as it is: the opt-in of lds_opt_in is for dynamic LDS and has nothing to raise here
 
 }  // namespace pfb
 }  // namespace rtlws

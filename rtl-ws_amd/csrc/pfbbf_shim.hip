@@ -80,10 +80,7 @@ const char* rtlws_pfbbf_last_error(void) { return g_err.c_str(); }
 
 int rtlws_pfbbf_supported(int log2_channels, int taps_per_branch, int hop, int ninputs, int nbeams)
 {
-    g_err.clear();
-    const char* why = why_not(log2_channels, taps_per_branch, hop, 0, ninputs, nbeams, 0);
-    if (why) fail("rtlws_pfbbf", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_pfbbf", why_not(log2_channels, taps_per_branch, hop, 0, ninputs, nbeams, 0));
 }
 
 long rtlws_pfbbf_samples_needed(int log2_channels, int taps_per_branch, int hop, int k_avg, long count)

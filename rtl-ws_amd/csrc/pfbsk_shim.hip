@@ -62,11 +62,9 @@ const char* rtlws_pfbsk_last_error(void) { return g_err.c_str(); }
 
 int rtlws_pfbsk_supported(int log2_channels, int taps_per_branch, int hop, int k_avg, int nsub, int output)
 {
-    g_err.clear();
     const char* why = why_not(log2_channels, taps_per_branch, hop, k_avg, nsub, 0);
     if (!why && !known_output(output)) why = "unknown output";
-    if (why) fail("rtlws_pfbsk", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_pfbsk", why);
 }
 
 long rtlws_pfbsk_samples_needed(int log2_channels, int taps_per_branch, int hop, int k_avg, int nsub, long nspectra)

@@ -41,11 +41,9 @@ const char* rtlws_pfbspec_last_error(void) { return g_err.c_str(); }
 
 int rtlws_pfbspec_supported(int log2_channels, int taps_per_branch, int hop, int k_avg, int output)
 {
-    g_err.clear();
     const char* why = why_not(log2_channels, taps_per_branch, hop, k_avg, 0);
     if (!why && !known_output(output)) why = "unknown output";
-    if (why) fail("rtlws_pfbspec", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_pfbspec", why);
 }
 
 long rtlws_pfbspec_samples_needed(int log2_channels, int taps_per_branch, int hop, int k_avg, long nspectra)

@@ -48,10 +48,7 @@ const char* rtlws_pfbxc_last_error(void) { return g_err.c_str(); }
 
 int rtlws_pfbxc_supported(int log2_channels, int taps_per_branch, int hop, int k_avg, int ninputs)
 {
-    g_err.clear();
-    const char* why = why_not(log2_channels, taps_per_branch, hop, k_avg, ninputs, 0);
-    if (why) fail("rtlws_pfbxc", why, 0);
-    return why ? 0 : 1;
+    return supported("rtlws_pfbxc", why_not(log2_channels, taps_per_branch, hop, k_avg, ninputs, 0));
 }
 
 long rtlws_pfbxc_samples_needed(int log2_channels, int taps_per_branch, int hop, int k_avg, long nspectra)

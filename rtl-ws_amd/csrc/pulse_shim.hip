@@ -4,7 +4,6 @@
 // host: without a device there is no plan.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -12,12 +11,10 @@
 
 #include "pulse.h"
 #include "rtlws_pulse.h"
-#include "shim_common.h"
+#include "search_plan.h"
 
 // The rows the table took and its pieces on the engine's device
-struct rtlws_pulse_plan {
-    rtlws_engine* engine;
-    int device;
+struct rtlws_pulse_plan : rtlws::search::Plan {
     int nwidths;
     long seg;
     rtlws::pulse::Layout layout;
@@ -27,34 +24,24 @@ struct rtlws_pulse_plan {
 namespace {
 
 using namespace rtlws::pulse;
+namespace sp = rtlws::search;
 
 static_assert(MAX_WIDTHS == RTLWS_PULSE_MAX_WIDTHS && MAX_WIDTH == RTLWS_PULSE_MAX_WIDTH && MIN_SEG == RTLWS_PULSE_MIN_SEG &&
-                  MAX_SEG == RTLWS_PULSE_MAX_SEG && MAX_TRIALS == RTLWS_PULSE_MAX_TRIALS && MAX_NOUT == RTLWS_PULSE_MAX_NOUT,
-              "rtlws_pulse.h and pulse.h disagree");
+                  MAX_SEG == RTLWS_PULSE_MAX_SEG && MAX_TRIALS == RTLWS_PULSE_MAX_TRIALS && MAX_NOUT == RTLWS_PULSE_MAX_NOUT &&
+                  MAX_WIDTHS == sp::MAX_WIDTHS && MAX_TRIALS == sp::MAX_TRIALS,
+              "rtlws_pulse.h, pulse.h and search_plan.h disagree");
 
 // ---- the rules, each worded once ----
 const char* why_not_table(int nwidths, const int32_t* widths, long seg)
 {
-    if (nwidths < 1 || nwidths > MAX_WIDTHS) return "nwidths must be 1 .. 16";
-    if (!widths) return "null widths";
-    for (int k = 0; k < nwidths; ++k) {
-        if (widths[k] < 1 || widths[k] > MAX_WIDTH) return "every width must be 1 .. 1024";
-        if (k && widths[k] <= widths[k - 1]) return "the widths must be strictly ascending";
-    }
+    if (const char* why = sp::why_not_widths(nwidths, widths, MAX_WIDTH, "every width must be 1 .. 1024")) return why;
     if (seg < MIN_SEG || seg > MAX_SEG || seg % 4) return "seg must be 64 .. 1048576 and a multiple of 4";
     return nullptr;
 }
 
-const char* why_not_ntrials(int ntrials) { return ntrials < 1 || ntrials > MAX_TRIALS ? "ntrials must be 1 .. 65536" : nullptr; }
-
 const char* why_not_nout(long nout) { return nout < 0 || nout > MAX_NOUT ? "nout must be 0 .. 2^30" : nullptr; }
 
-long segments_of(long nout, long seg) { return (nout + seg - 1) / seg; }
-
-const char* why_not_grid(int ntrials, long nout, long seg)
-{
-    return segments_of(nout, seg) > INT_MAX / ntrials ? "more workgroups than one grid holds" : nullptr;
-}
+const char* why_not_grid(int ntrials, long nout, long seg) { return sp::why_not_grid(sp::ceil_div(nout, seg), ntrials); }
 
 // ---- the rows of a table ----
 Layout layout_of(int nwidths, const int32_t* widths)
@@ -104,13 +91,7 @@ extern "C" {
 
 const char* rtlws_pulse_last_error(void) { return g_err.c_str(); }
 
-int rtlws_pulse_supported(int nwidths, const int32_t* widths, long seg)
-{
-    g_err.clear();
-    const char* why = why_not_table(nwidths, widths, seg);
-    if (why) fail("rtlws_pulse", why, 0);
-    return why ? 0 : 1;
-}
+int rtlws_pulse_supported(int nwidths, const int32_t* widths, long seg) { return supported("rtlws_pulse", why_not_table(nwidths, widths, seg)); }
 
 int rtlws_pulse_geometry(int nwidths, const int32_t* widths, long seg, int ntrials, long nout, int* blocks, int* threads,
                          int* lds_bytes, int* tile_out, int* levels_kept, long* nseg)
@@ -118,45 +99,31 @@ int rtlws_pulse_geometry(int nwidths, const int32_t* widths, long seg, int ntria
     const char* fn = "rtlws_pulse_geometry";
     g_err.clear();
     if (const char* why = why_not_table(nwidths, widths, seg)) return fail(fn, why, -1);
-    if (const char* why = why_not_ntrials(ntrials)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_ntrials(ntrials)) return fail(fn, why, -1);
     if (const char* why = why_not_nout(nout)) return fail(fn, why, -1);
     if (const char* why = why_not_grid(ntrials, nout, seg)) return fail(fn, why, -1);
     const Layout l = layout_of(nwidths, widths);
-    if (blocks) *blocks = (int)(segments_of(nout, seg) * ntrials);
+    if (blocks) *blocks = (int)(sp::ceil_div(nout, seg) * ntrials);
     if (threads) *threads = THREADS;
     if (lds_bytes) *lds_bytes = LDS_WORDS[l.lds] * 4;
     if (tile_out) *tile_out = l.tile_out;
     if (levels_kept) *levels_kept = l.levels_kept;
-    if (nseg) *nseg = segments_of(nout, seg);
+    if (nseg) *nseg = sp::ceil_div(nout, seg);
     return 0;
 }
 
 rtlws_pulse_plan* rtlws_pulse_open(rtlws_engine* e, int nwidths, const int32_t* widths, long seg)
 {
-    const char* fn = "rtlws_pulse_open";
-    g_err.clear();
-    const int device = open_device(fn, why_not_table(nwidths, widths, seg), e);
-    if (device < 0) return nullptr;
-    const Layout l = layout_of(nwidths, widths);
-    const std::vector<int> table = build_table(nwidths, widths, l);
-    int* d_table = nullptr;
-    hipError_t err = hipMalloc(reinterpret_cast<void**>(&d_table), table.size() * sizeof(int));
-    if (err == hipSuccess) err = hipMemcpy(d_table, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (err == hipSuccess) err = prepare_pulse(l);
-    if (err != hipSuccess) {
-        if (d_table) (void)hipFree(d_table);
-        fail_hip(fn, "the table or the kernel", err);
-        return nullptr;
-    }
-    return new rtlws_pulse_plan{e, device, nwidths, seg, l, d_table};
+    const auto fill = [&](rtlws_pulse_plan& p) {
+        p.nwidths = nwidths, p.seg = seg, p.layout = layout_of(nwidths, widths);
+        const std::vector<int> table = build_table(nwidths, widths, p.layout);
+        const hipError_t err = sp::upload(&p.d_table, table.data(), table.size());
+        return err == hipSuccess ? prepare_pulse(p.layout) : err;
+    };
+    return sp::open_plan<rtlws_pulse_plan>("rtlws_pulse_open", why_not_table(nwidths, widths, seg), e, fill, "the table or the kernel", rtlws_pulse_close);
 }
 
-void rtlws_pulse_close(rtlws_pulse_plan* p)
-{
-    if (!p) return;
-    if (hipSetDevice(p->device) == hipSuccess) (void)hipFree(p->d_table);
-    delete p;
-}
+void rtlws_pulse_close(rtlws_pulse_plan* p) { sp::close_plan(p, &rtlws_pulse_plan::d_table); }
 
 long rtlws_pulse_samples_needed(const rtlws_pulse_plan* p, long nout)
 {
@@ -173,7 +140,7 @@ long rtlws_pulse_segments(const rtlws_pulse_plan* p, long nout)
     g_err.clear();
     if (const char* why = why_not_nout(nout)) return fail(fn, why, -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
-    return segments_of(nout, p->seg);
+    return sp::ceil_div(nout, p->seg);
 }
 
 int rtlws_pulse_run(rtlws_pulse_plan* p, const float* d_in, long in_stride, int ntrials, long nout, float* d_peak, int32_t* d_at,
@@ -182,15 +149,15 @@ int rtlws_pulse_run(rtlws_pulse_plan* p, const float* d_in, long in_stride, int 
     const char* fn = "rtlws_pulse_run";
     g_err.clear();
     // what needs no plan: a trial holds at least its nout samples
-    if (const char* why = why_not_ntrials(ntrials)) return fail(fn, why, -1);
+    if (const char* why = sp::why_not_ntrials(ntrials)) return fail(fn, why, -1);
     if (const char* why = why_not_nout(nout)) return fail(fn, why, -1);
     if (in_stride < nout) return fail(fn, "in_stride must be >= samples_needed", -1);
-    if (in_stride % 4) return fail(fn, "in_stride must be a multiple of 4", -1);
+    if (const char* why = sp::why_not_stride(in_stride)) return fail(fn, why, -1);
     if (nout > 0 && (!d_in || !d_peak || !d_at)) return fail(fn, "null pointer", -1);
-    if (reinterpret_cast<uintptr_t>(d_in) & 15u) return fail(fn, "d_in must be 16-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_peak) & 3u) return fail(fn, "d_peak must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_at) & 3u) return fail(fn, "d_at must be 4-byte aligned", -1);
-    if (reinterpret_cast<uintptr_t>(d_mom) & 7u) return fail(fn, "d_mom must be 8-byte aligned", -1);
+    if (sp::misaligned(d_in, 16)) return fail(fn, "d_in must be 16-byte aligned", -1);
+    if (sp::misaligned(d_peak, 4)) return fail(fn, "d_peak must be 4-byte aligned", -1);
+    if (sp::misaligned(d_at, 4)) return fail(fn, "d_at must be 4-byte aligned", -1);
+    if (sp::misaligned(d_mom, 8)) return fail(fn, "d_mom must be 8-byte aligned", -1);
     if (!p) return fail(fn, NULL_PLAN, -1);
     // what the plan decides; still before anything is asked of the device
     const long need = nout ? nout + p->layout.w_max - 1 : 0;
@@ -198,8 +165,7 @@ int rtlws_pulse_run(rtlws_pulse_plan* p, const float* d_in, long in_stride, int 
     if (const char* why = why_not_grid(ntrials, nout, p->seg)) return fail(fn, why, -1);
     if (nout == 0) return 0;
 
-    hipError_t err = hipSetDevice(p->device);
-    if (err != hipSuccess) return fail_hip(fn, "hipSetDevice", err);
+    if (sp::use_device(fn, p)) return -3;
     Params kp;
     kp.in = d_in;
     kp.peak = d_peak;
@@ -209,23 +175,20 @@ int rtlws_pulse_run(rtlws_pulse_plan* p, const float* d_in, long in_stride, int 
     kp.in_stride = in_stride;
     kp.nout = nout;
     kp.seg = p->seg;
-    kp.nseg = segments_of(nout, p->seg);
+    kp.nseg = sp::ceil_div(nout, p->seg);
     kp.need = need;
     kp.nwidths = p->nwidths;
     kp.top = p->layout.top;
     kp.w_max = p->layout.w_max;
-    err = launch_pulse(p->layout, kp, ntrials, stream_of(p->engine, stream));
+    const hipError_t err = launch_pulse(p->layout, kp, ntrials, stream_of(p->engine, stream));
     if (err != hipSuccess) return fail_hip(fn, "kernel launch", err);
     return 0;
 }
 
 double rtlws_pulse_snr(double peak, int width, double sum1, double sum2, long count)
 {
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (count < 2 || width < 1) return nan;
-    const double mean = sum1 / (double)count;
-    const double var = sum2 / (double)count - mean * mean;
-    if (!(var > 0.0)) return nan;
+    double mean, var;
+    if (width < 1 || !sp::moments(sum1, sum2, count, &mean, &var)) return std::numeric_limits<double>::quiet_NaN();
     return (peak - (double)width * mean) / std::sqrt((double)width * var);
 }
 

@@ -328,6 +328,15 @@ hipError_t launch(void (*kernel)(P), dim3 grid, dim3 block, size_t lds_bytes, hi
     return hipGetLastError();
 }
 
+// A plan's prepare step: asking for a kernel's attributes loads its code object on the current device, so that a launch
+// makes no other runtime call and nothing is left to load under a capture
+template <typename... A>
+hipError_t load_kernel(void (*kernel)(A...))
+{
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kernel));
+}
+
 // A kernel launched with more than 64 KiB of dynamic LDS raises its limit to `bytes` with hipFuncSetAttribute, once
 // per kernel and device (`device`, the current one) before its first launch there; nothing to do at 64 KiB or less.
 // Thread-safe; once done, a lookup and no runtime call.

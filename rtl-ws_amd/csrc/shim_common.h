@@ -1,6 +1,6 @@
 // shim_common.h -- what every satellite library's extern "C" glue (*_shim.hip, one per library) says the same way: the
-// library's thread-local error text, how a refusal and a failed runtime call are recorded, the head of a plan's open,
-// and which stream a call runs on.  Everything has internal linkage: a library has one shim, so it has one error slot of its own, and a
+// library's thread-local error text, how a refusal and a failed runtime call are recorded, the answer of
+// rtlws_*_supported, the head of a plan's open, and which stream a call runs on.  Everything has internal linkage: a library has one shim, so it has one error slot of its own, and a
 // refusal in one library does not touch another's *_last_error().
 #ifndef RTLWS_SHIM_COMMON_H
 #define RTLWS_SHIM_COMMON_H
@@ -30,6 +30,14 @@ thread_local std::string g_err;
     snprintf(buf, sizeof buf, "%s: %s: %s", fn, what, hipGetErrorString(e));
     g_err = buf;
     return -3;
+}
+
+// rtlws_*_supported: `why` is the verdict of the library's rules; 1, or 0 with "<lib>: <why>" recorded
+[[maybe_unused]] int supported(const char* lib, const char* why)
+{
+    g_err.clear();
+    if (why) fail(lib, why, 0);
+    return why ? 0 : 1;
 }
 
 // what a run answers to a null plan, beside the null engine's text below: the open that would have made it failed

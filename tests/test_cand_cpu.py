@@ -19,7 +19,7 @@ import fold_ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rtl-ws_amd", "csrc")
 INCLUDE = os.path.join(ROOT, "include")
-NEW_SOURCES = [os.path.join(CSRC, f) for f in ("cand.h", "cand.hip", "cand_shim.hip")] + [os.path.join(INCLUDE, "rtlws_cand.h")]
+NEW_SOURCES = [os.path.join(CSRC, f) for f in ("cand.h", "cand.hip", "cand_shim.hip", "search_plan.h")] + [os.path.join(INCLUDE, "rtlws_cand.h")]
 
 
 @pytest.fixture(scope="module")

@@ -15,7 +15,7 @@ import cdd_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rtl-ws_amd", "csrc")
-NEW_SOURCES = [os.path.join(CSRC, f) for f in ("cdd.h", "cdd.hip", "cdd_shim.hip")] + [os.path.join(ROOT, "include", "rtlws_cdd.h")]
+NEW_SOURCES = [os.path.join(CSRC, f) for f in ("cdd.h", "cdd.hip", "cdd_shim.hip", "search_plan.h")] + [os.path.join(ROOT, "include", "rtlws_cdd.h")]
 
 
 @pytest.fixture(scope="module")

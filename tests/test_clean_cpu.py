@@ -17,7 +17,7 @@ import dedisp_ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rtl-ws_amd", "csrc")
 INCLUDE = os.path.join(ROOT, "include")
-NEW_SOURCES = [os.path.join(CSRC, f) for f in ("clean.h", "clean.hip", "clean_shim.hip")] + [os.path.join(INCLUDE, "rtlws_clean.h")]
+NEW_SOURCES = [os.path.join(CSRC, f) for f in ("clean.h", "clean.hip", "clean_shim.hip", "search_plan.h")] + [os.path.join(INCLUDE, "rtlws_clean.h")]
 INF = float("inf")
 SEEDS = range(20)
 

@@ -14,7 +14,7 @@ import ffa_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rtl-ws_amd", "csrc")
-NEW_SOURCES = [os.path.join(CSRC, f) for f in ("ffa.h", "ffa.hip", "ffa_shim.hip")] + [os.path.join(ROOT, "include", "rtlws_ffa.h")]
+NEW_SOURCES = [os.path.join(CSRC, f) for f in ("ffa.h", "ffa.hip", "ffa_shim.hip", "search_plan.h")] + [os.path.join(ROOT, "include", "rtlws_ffa.h")]
 
 
 @pytest.fixture(scope="module")
