@@ -1,5 +1,6 @@
 // dedisp.h -- shared between dedisp.hip (the kernels) and dedisp_shim.hip (rtlws_dedisp.h's host glue): the tile, the
-// forms a plan can take and the tables it uploads.
+// forms a plan can take and the tables it uploads.  The subband dedisperser's first stage is this tile
+// too (subdedisp.h); the rule that chooses a form is dedisp_form.h's.
 #ifndef RTLWS_CSRC_DEDISP_H
 #define RTLWS_CSRC_DEDISP_H
 

@@ -1,5 +1,5 @@
 // dedisp_shim.hip -- extern "C" glue of include/rtlws_dedisp.h (librtlws_dedisp.so): argument rules, the delay
-// formula, the choice of a table's form (dedisp.h) and the tables of that form, the plan, the launch.  The engine
+// formula, the plan (the choice of a table's form and the tables of that form: dedisp_form.h), the launch.  The engine
 // (device, stream) is librtlws_hip.so's; nothing here reads the environment, and nothing of a run is computed on the
 // host: without a device there is no plan.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "dedisp.h"
+#include "dedisp_form.h"
 #include "rtlws_dedisp.h"
 #include "search_plan.h"
 
@@ -35,7 +36,7 @@ static_assert(MIN_NCHAN == RTLWS_DEDISP_MIN_NCHAN && MAX_NCHAN == RTLWS_DEDISP_M
 const char* why_not_shape(int nchan, int ntrials)
 {
     if (const char* why = sp::why_not_nchan(nchan)) return why;
-    if (ntrials < 1 || ntrials > MAX_TRIALS) return "ntrials must be 1 .. 4096";
+    if (ntrials < 1 || ntrials > MAX_TRIALS) return WHY_NTRIALS;
     return nullptr;
 }
 
@@ -43,12 +44,12 @@ const char* why_not_shape(int nchan, int ntrials)
 const char* why_not_table(int nchan, int ntrials, const int32_t* delays, const uint8_t* mask, int* max_delay)
 {
     if (const char* why = why_not_shape(nchan, ntrials)) return why;
-    if (!delays) return "null delays";
+    if (!delays) return WHY_NULL_DELAYS;
     int most = 0;
     for (long t = 0; t < ntrials; ++t)
         for (int i = 0; i < nchan; ++i) {
             const int32_t d = delays[t * nchan + i];
-            if (d < 0 || d > MAX_DELAY) return "every delay must be 0 .. 65535";
+            if (d < 0 || d > MAX_DELAY) return WHY_DELAY;
             if ((!mask || mask[i]) && d > most) most = d;
         }
     *max_delay = most;
@@ -57,88 +58,7 @@ const char* why_not_table(int nchan, int ntrials, const int32_t* delays, const u
 
 const char* why_not_nout(long nout) { return nout < 0 ? "nout must be >= 0" : nullptr; }
 
-long groups_of(int ntrials, int trials) { return sp::ceil_div(ntrials, trials); }
-
 const char* why_not_grid(long nout, int ntrials, const Layout& l) { return sp::why_not_grid(sp::ceil_div(nout, TILE_OUT), groups_of(ntrials, l.trials)); }
-
-// ---- the form of a table ----
-// The least and the largest delay of positions i0 .. i0 + width - 1 under trials t0 .. t0 + trials - 1 (those of them
-// there are), over the positions the mask keeps; false where it keeps none
-bool unit_range(int nchan, int ntrials, const int32_t* delays, const uint8_t* mask, int t0, int trials, int i0, int width, int* lo, int* hi)
-{
-    int least = INT_MAX, most = -1;
-    for (int i = i0; i < i0 + width; ++i) {
-        if (mask && !mask[i]) continue;
-        for (int t = t0; t < t0 + trials && t < ntrials; ++t) {
-            const int d = delays[(long)t * nchan + i];
-            least = d < least ? d : least;
-            most = d > most ? d : most;
-        }
-    }
-    *lo = least;
-    *hi = most;
-    return most >= 0;
-}
-
-// the widest spread of delays inside a unit of `width` positions and a group of `trials` trials
-int widest_spread(int nchan, int ntrials, const int32_t* delays, const uint8_t* mask, int trials, int width)
-{
-    int widest = 0;
-    for (int t0 = 0; t0 < ntrials; t0 += trials)
-        for (int i0 = 0; i0 < nchan; i0 += width) {
-            int lo, hi;
-            if (unit_range(nchan, ntrials, delays, mask, t0, trials, i0, width, &lo, &hi) && hi - lo > widest) widest = hi - lo;
-        }
-    return widest;
-}
-
-// chunk positions of columns as long as `height`, in the smaller LDS where they fit, else the larger; false: in neither
-bool fits(int trials, int chunk, int height, Layout* l)
-{
-    const int stride = fit_stride(height, chunk / 4);
-    const long words = (long)chunk * stride + TILE_OUT;
-    if (words > BIG_WORDS) return false;
-    *l = Layout{trials, 0, words > SMALL_WORDS, chunk, stride};
-    return true;
-}
-
-// The largest group of 8, 4, 2, 1 trials (no larger than ntrials fills half of) whose windows fit beside whole
-// 128-byte pieces of the rows; one trial with narrower pieces; one trial, every position by itself (a column is then
-// TILE_OUT rows whatever the table)
-Layout choose_layout(int nchan, int ntrials, const int32_t* delays, const uint8_t* mask)
-{
-    Layout l;
-    for (int trials = MAX_TRIALS_PER_BLOCK; trials >= 1; trials /= 2) {
-        if (trials > 1 && trials >= 2 * ntrials) continue;
-        const int height = TILE_OUT + widest_spread(nchan, ntrials, delays, mask, trials, 4);
-        for (int chunk = MAX_CHUNK; chunk >= (trials > 1 ? MAX_CHUNK : 4); chunk /= 2)
-            if (fits(trials, chunk, height, &l)) return l;
-    }
-    return Layout{1, 1, 0, MAX_CHUNK, fit_stride(TILE_OUT, MAX_CHUNK / 4)};
-}
-
-// the tables of dedisp.h's Params for a form
-void build_tables(int nchan, int ntrials, const int32_t* delays, const uint8_t* mask, const Layout& l, std::vector<int2>* units,
-                  std::vector<int>* rel)
-{
-    const int width = l.lone ? 1 : 4, per_group = nchan / width;
-    const long groups = groups_of(ntrials, l.trials);
-    units->assign(groups * per_group, make_int2(-1, 0));
-    rel->assign(groups * nchan * l.trials, l.chunk * l.stride);
-    for (long g = 0; g < groups; ++g)
-        for (int u = 0; u < per_group; ++u) {
-            int lo, hi;
-            if (!unit_range(nchan, ntrials, delays, mask, (int)g * l.trials, l.trials, u * width, width, &lo, &hi)) continue;
-            (*units)[g * per_group + u] = make_int2(lo, hi - lo);
-            for (int i = u * width; i < (u + 1) * width; ++i) {
-                if (mask && !mask[i]) continue;
-                for (int k = 0; k < l.trials; ++k) {
-                    const long t = g * l.trials + k < ntrials ? g * l.trials + k : ntrials - 1;      // past the table: the last trial again
-                    (*rel)[(g * nchan + i) * l.trials + k] = i % l.chunk * l.stride + delays[t * nchan + i] - lo;
-                }
-            }
-        }
-}
 
 }  // namespace
 
@@ -154,8 +74,8 @@ int rtlws_dedisp_delays(int nchan, int shifted, double f_centre_hz, double bandw
     const char* fn = "rtlws_dedisp_delays";
     g_err.clear();
     if (const char* why = why_not_shape(nchan, ntrials)) return fail(fn, why, -1);
-    if (shifted != 0 && shifted != 1) return fail(fn, "shifted must be 0 or 1", -1);
-    if (!delays) return fail(fn, "null delays", -1);
+    if (shifted != 0 && shifted != 1) return fail(fn, WHY_SHIFTED, -1);
+    if (!delays) return fail(fn, WHY_NULL_DELAYS, -1);
     if (const char* why = sp::why_not_band(nchan, f_centre_hz, bandwidth_hz, row_seconds)) return fail(fn, why, -1);
     const int M = nchan;
     const std::vector<double> excess = sp::excess(M, shifted, f_centre_hz, bandwidth_hz);
@@ -163,13 +83,13 @@ int rtlws_dedisp_delays(int nchan, int shifted, double f_centre_hz, double bandw
         const double dm = dm0 + (double)t * dm_step;
         char buf[96];
         if (!(std::isfinite(dm) && dm >= 0.0)) {
-            snprintf(buf, sizeof buf, "trial %d: the dispersion measure must be finite and >= 0", t);
+            snprintf(buf, sizeof buf, WHY_DM, t);
             return fail(fn, buf, -1);
         }
         for (int i = 0; i < M; ++i) {
             const double d = std::rint(sp::DISPERSION * dm * excess[i] / row_seconds);
             if (!(d <= (double)MAX_DELAY)) {
-                snprintf(buf, sizeof buf, "trial %d: a delay above 65535 rows", t);
+                snprintf(buf, sizeof buf, WHY_SWEEP, "trial", t);
                 return fail(fn, buf, -1);
             }
             delays[(long)t * M + i] = (int32_t)d;
