@@ -245,8 +245,13 @@ def _search(cand, engine, cube, a, g, want_prof=True, want_tphase=True, name=Non
 SEARCH_SHAPES = ((1, 1, 1), (3, 5, 7), (17, 33, 65), (17, 1, 65), (1, 33, 7), (33, 8, 16), (64, 5, 1))
 
 
-@pytest.mark.parametrize("nchan", [4, 68])
-@pytest.mark.parametrize("nbins", [2, 50, 64, 65, 256])
+# the counts of bins a lane holds, ceil(nbins / 64) = 1 .. 4: both sides of every border (64 | 65, 128 | 129, 192 | 193), the
+# three upper ones at the channel count whose stage 1 crosses the chunk
+FIRST_SEARCH_BINS = (2, 50, 64, 65, 256)
+SEARCH_BINS = [(nbins, nchan) for nchan in (4, 68) for nbins in FIRST_SEARCH_BINS] + [(nbins, 68) for nbins in (128, 129, 192, 193)]
+
+
+@pytest.mark.parametrize("nbins,nchan", SEARCH_BINS)
 def test_every_count_of_bins_per_lane_and_every_tile_border(cand, engine, nbins, nchan):
     """Gaussian f32 with exponents over 2^-6 .. 2^6, where the order of the additions shows; shifts that include 0 and
     nbins - 1; two candidates"""

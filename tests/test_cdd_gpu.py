@@ -117,7 +117,7 @@ def _power_inputs(cdd, engine, log2n):
     """per N: (lead, trail) with hop divisible by 3, the tables, the input, and the run's own ksum == 0 voltages, once"""
     if log2n not in _POWER_INPUTS:
         n, nchan, nseg = 1 << log2n, 4, 2
-        lead, trail = (5, 12) if log2n == 9 else (5, 11)
+        lead, trail = (5, 12) if log2n % 2 else (5, 11)        # 2^log2n is 2 (mod 3) at an odd log2n, 1 at an even one
         assert (n - lead - trail) % 3 == 0
         tables = _tables(cdd, log2n, nchan, seed=60 + log2n)
         x = _gauss(nchan, cdd_ref.samples_needed(n, lead, trail, nseg), seed=160 + log2n)
@@ -127,10 +127,10 @@ def _power_inputs(cdd, engine, log2n):
     return _POWER_INPUTS[log2n]
 
 
-@pytest.mark.parametrize("layout", ["time", "channel"])
-@pytest.mark.parametrize("which", ["1", "3", "hop"])
-@pytest.mark.parametrize("log2n", [9, 14])
-def test_power_rows_are_the_voltages_bits(cdd, engine, log2n, which, layout):
+def _power(cdd, engine, log2n, which, layout):
+    """the power rows of _power_inputs' run at ksum `which` ("hop": one row a segment) in one layout, with NaN in the
+    input's padding and a preset pattern around the rows: bit for bit the f32 restatement over the run's own voltages,
+    and within the row allowance of the f64 reference"""
     lead, trail, nseg, tables, x, volts = _power_inputs(cdd, engine, log2n)
     nchan, n = tables.shape
     hop = n - lead - trail
@@ -150,6 +150,17 @@ def test_power_rows_are_the_voltages_bits(cdd, engine, log2n, which, layout):
     share = float((np.abs(got.astype(np.float64) - ref) / allowance).max())
     print("cdd power log2n %d ksum %d %s-major: worst share of the row allowance %.3g" % (log2n, ksum, layout, share))
     assert share <= 1.0
+
+
+# every ksum at the two ends of N; between them, where the epilogue's `rows` loop and the tile's places take every other
+# shape (one to eight rows a thread, the three- and the four-digit places), ksum 3 in both layouts
+POWER_CASES = ([(log2n, which, layout) for layout in ("time", "channel") for which in ("1", "3", "hop") for log2n in (9, 14)]
+               + [(log2n, "3", layout) for layout in ("time", "channel") for log2n in (10, 11, 12, 13)])
+
+
+@pytest.mark.parametrize("log2n,which,layout", POWER_CASES)
+def test_power_rows_are_the_voltages_bits(cdd, engine, log2n, which, layout):
+    _power(cdd, engine, log2n, which, layout)
 
 
 def test_the_waterfall_feeds_dedisp(cdd, engine):

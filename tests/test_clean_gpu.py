@@ -1,8 +1,10 @@
 """GPU suite of include/rtlws_clean.h (librtlws_clean.so) against its numpy restatement (tests/clean_ref.py), every output
 word bit for bit: out (f32 on uint32 views, NaN by place), keep, stats and nkept; NaN in both strides' padding of the
 input, a preset pattern in the output's padding and behind every output.  Every row shape (G = 1, a padded tree, part of a
-wavefront, both sides of the 256-channel group, the one-row workgroup) at every block length and run length with the
-filter on and off; signed rows; a static mask, non-finite samples, constant channels, an all-flagged block and the
+wavefront, both sides of the 256-channel group, the one-row workgroup; every count of lanes a row takes, 1 .. 1024, so
+every depth of the zero-DM tree inside a wavefront and across one to sixteen of them; every length stage 2 sorts, 4 .. 4096,
+and both sides of its 64 KiB of LDS) at every block length and run length with the filter on and off; the median's
+index at one, two, all but one and all channels valid; signed rows; a static mask, non-finite samples, constant channels, an all-flagged block and the
 thresholds' ends; in place; each optional output NULL; one plan many times and beside another; a run from a later block;
 the three launches captured and replayed; every refusal of a run; and the chain into rtlws_dedisp_run."""
 
@@ -16,10 +18,20 @@ pytestmark = pytest.mark.gpu
 
 FILL = np.float32(-12345.678)
 INF = float("inf")
-NCHANS, BLOCKS = (4, 12, 64, 252, 256, 260, 1024, 4096), (32, 33, 40, 512)
+# the feature's own channel counts, and those that tests/search_family_matrix.py found no test at: a cross-lane tree of 1, 3
+# and 5 levels (8, 20, 128), the padded row of four wavefronts (516), the rows of eight (1028, 2048), and the two sides of
+# stage 2's 64 KiB of LDS (2048, 2052); between them sort lengths 8, 32, 128 and 2048
+FIRST_NCHANS = (4, 12, 64, 252, 256, 260, 1024, 4096)
+NCHANS, BLOCKS = tuple(sorted(FIRST_NCHANS + (8, 20, 128, 516, 1028, 2048, 2052))), (32, 33, 40, 512)
+# the rows of eight and of sixteen wavefronts beside 4096: the short blocks and three run lengths, which keep a case to a
+# few seconds (the restatement's time goes with rows x channels)
+WIDE = (1028, 2048, 2052)
+SHAPES = [(nchan, B) for B in BLOCKS for nchan in NCHANS if not (nchan in WIDE and B == 512)]
 
 
-def _nrows(B):
+def _nrows(B, nchan=4):
+    if nchan in WIDE:
+        return (B, B + 1, 2 * B + B // 2)
     return (B, B + 1, 2 * B, 2 * B + B // 2, 5 * B + 7)
 
 
@@ -78,16 +90,36 @@ def _check(clean, engine, x, B, mask=None, t_mean=6.0, t_sigma=6.0, zerodm=True,
 def test_the_cases_cover_the_borders(clean):
     """G = 1, a padded tree, a part of a wavefront and a whole one, one to sixteen wavefronts a row; blocks whose residue
     classes are unequal; a last block of one row, of half a block and of seven rows"""
-    assert [clean_ref.pow2_at_least(m // 4) for m in NCHANS] == [1, 4, 16, 64, 64, 128, 256, 1024]
-    assert [clean.geometry(m, 32, 32)[2][2] for m in NCHANS] == [256, 256, 256, 256, 256, 256, 256, 1024]
-    assert [clean.geometry(m, 32, 32)[1][0] for m in NCHANS] == [1, 1, 1, 1, 1, 2, 4, 16]
+    assert [clean_ref.pow2_at_least(m // 4) for m in NCHANS] == [1, 2, 4, 8, 16, 32, 64, 64, 128, 256, 256, 512, 512, 1024, 1024]
+    assert [clean.geometry(m, 32, 32)[2][2] for m in NCHANS] == [256] * 11 + [512, 512, 1024, 1024]
+    assert [clean.geometry(m, 32, 32)[1][0] for m in NCHANS] == [1, 1, 1, 1, 1, 1, 1, 1, 2, 3, 4, 5, 8, 9, 16]
     assert [B % 8 for B in BLOCKS] == [0, 1, 0, 0] and max(_nrows(512)) <= 2600
+    # what the library itself reports, class by class: the lanes a row takes (a block of 16384 rows is 1024 G / T
+    # workgroups of the third launch: 16 T / G rows each), the wavefronts of a row, the keys stage 2 sorts, its threads,
+    # and its LDS on both sides of 64 KiB
+    lanes, waves, keys, threads, lds = [], [], [], [], []
+    for m in NCHANS:
+        rc, blocks, thr, bytes_, _, _, _ = clean.geometry(m, 16384, 16384)
+        assert rc == 0 and (blocks[2] * thr[2]) % 1024 == 0
+        G = blocks[2] * thr[2] // 1024
+        assert G == clean_ref.pow2_at_least(m // 4) and bytes_[2] == (8 * thr[2] if G > 64 else 0)
+        lanes.append(G)
+        waves.append(max(G // 64, 1))
+        keys.append((bytes_[1] - 128) // 16)
+        threads.append(thr[1])
+        lds.append(bytes_[1])
+    assert set(lanes) == {1 << k for k in range(11)}                            # every depth of the cross-lane tree, 0 .. 6, and of the LDS tree
+    assert set(waves) == {1, 2, 4, 8, 16}                                       # every entry of clean.hip's RowWaves
+    assert keys == [clean_ref.pow2_at_least(m) for m in NCHANS] and set(keys) == {4 << k for k in range(11)}
+    assert {(t, k // t if k > t else 1) for t, k in zip(threads, keys)} == {(64, 1), (64, 2), (128, 2), (256, 2), (512, 2), (1024, 2), (1024, 4)}
+    assert [k for t, k in zip(threads, keys) if (t, k // t) == (64, 2)] == [128] and [k for t, k in zip(threads, keys) if (t, k // t) == (1024, 2)] == [2048, 2048]
+    assert max(v for v in lds if v <= 65536) == lds[NCHANS.index(2048)] == 32896 and min(v for v in lds if v > 65536) == lds[NCHANS.index(2052)] == 65664
+    assert all(m < 1028 or m == 4096 for m in NCHANS if m not in WIDE) and len(SHAPES) == len(NCHANS) * len(BLOCKS) - len(WIDE)
 
 
-@pytest.mark.parametrize("B", BLOCKS)
-@pytest.mark.parametrize("nchan", NCHANS)
+@pytest.mark.parametrize("nchan,B", SHAPES)
 def test_every_row_shape_block_length_and_run_length(clean, engine, nchan, B):
-    for nrows in _nrows(B):
+    for nrows in _nrows(B, nchan):
         x = dedisp_ref.pooled_rows(nrows, nchan, seed=nchan + B + nrows)
         for zerodm in (True, False):
             _check(clean, engine, x, B, zerodm=zerodm, name=(nchan, B, nrows, zerodm))
@@ -101,7 +133,7 @@ def test_signed_rows(clean, engine, nchan, B):
     assert np.signbit(ref[0]).any() and 0 < ref[1].mean()
 
 
-@pytest.mark.parametrize("nchan,B", [(12, 32), (260, 33), (4096, 40)])
+@pytest.mark.parametrize("nchan,B", [(12, 32), (260, 33), (4096, 40), (2048, 33)])
 def test_special_values_and_thresholds(clean, engine, nchan, B):
     """a static mask, a NaN, an Inf and a constant channel, a block of constants (nothing kept there), at t = 0, 6 and
     +Inf in both places"""
@@ -122,11 +154,37 @@ def test_special_values_and_thresholds(clean, engine, nchan, B):
     _check(clean, engine, x, B, mask, 6.0, 6.0, False, name=("special, unfiltered", nchan))
 
 
-@pytest.mark.parametrize("nchan,B", [(4, 32), (252, 33), (1024, 40)])
+@pytest.mark.parametrize("nchan,B", [(4, 32), (252, 33), (1024, 40), (2048, 40)])
 def test_in_place(clean, engine, nchan, B):
     x = dedisp_ref.pooled_rows(2 * B + B // 2, nchan, seed=nchan + 2)
     for zerodm in (True, False):
         _check(clean, engine, x, B, zerodm=zerodm, in_place=True, name=("in place", nchan, zerodm))
+
+
+@pytest.mark.parametrize("nchan", [128, 2048])
+def test_the_median_is_element_nvalid_minus_one_over_two(clean, engine, nchan):
+    """a static mask that leaves 1, 2, sort_len - 1 and sort_len channels valid, where a thread of stage 2 holds two keys
+    (64 threads at 128 keys, 1024 at 2048): with t = 0 in one test and +Inf in the other the block keeps the one channel
+    whose mu (or sd) is element (nvalid - 1) / 2 of the valid ones in ascending order -- at nvalid 2 the smaller of the
+    two, at an even nvalid the lower of the middle pair -- found here by numpy's own sort of the statistics"""
+    B, nrows = 32, 33
+    assert clean_ref.pow2_at_least(nchan) == nchan and clean.geometry(nchan, B, nrows)[2][1] == nchan // 2
+    x = dedisp_ref.pooled_rows(nrows, nchan, seed=nchan + 3)
+    order = np.random.default_rng(nchan).permutation(nchan)
+    for nvalid in (1, 2, nchan - 1, nchan):
+        mask = np.zeros(nchan, np.uint8)
+        mask[order[:nvalid]] = 1
+        for which, (t_mean, t_sigma) in enumerate(((0.0, INF), (INF, 0.0))):
+            ref = _check(clean, engine, x, B, mask, t_mean, t_sigma, True, name=("median", nchan, nvalid, which))
+            for b in range(2):
+                j0 = clean_ref.window_start(b, B, nrows)
+                mu, sd, _, _, valid = clean_ref.stats_ref(x[j0:j0 + B], mask)
+                assert valid.sum() == nvalid
+                stat = (mu, sd)[which]
+                at = np.flatnonzero(valid)[np.argsort(stat[valid], kind="stable")]
+                assert len(set(stat[valid].tolist())) == nvalid                 # no ties: one channel is the median
+                assert np.flatnonzero(ref[1][b]).tolist() == [at[(nvalid - 1) // 2]] and ref[3][b] == 1, (nvalid, which, b)
+        _check(clean, engine, x, B, mask, 6.0, 6.0, True, name=("median, 6 MADs", nchan, nvalid))
 
 
 def test_each_optional_output_null_in_turn(clean, engine):

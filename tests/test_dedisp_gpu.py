@@ -260,8 +260,7 @@ def _plan_of(built, case, delays, mask=None):
     return forms.NOUT + most
 
 
-@pytest.mark.parametrize("case", forms.CASES, ids=[forms.case_id(c) for c in forms.CASES])
-def test_every_border_of_the_plan(built, engine, case):
+def _border_case(built, engine, case):
     """A table whose plan stands on one side of a border of its forms, 36 positions (a last chunk of one quad behind
     every chunk width), tile_out + 1 outputs: with no mask and with one that keeps the delayed position, bit for bit;
     NaN in the padding columns and behind rows_needed"""
@@ -275,6 +274,11 @@ def test_every_border_of_the_plan(built, engine, case):
     for m in (None, mask):
         got = engine.dedisp(rows, delays, m, nout=forms.NOUT, in_stride=forms.NCHAN + 4)
         _assert_bits(got, dedisp_ref.dedisp_ref(rows, delays, m, forms.NOUT), "no mask" if m is None else "masked")
+
+
+@pytest.mark.parametrize("case", forms.CASES, ids=[forms.case_id(c) for c in forms.CASES])
+def test_every_border_of_the_plan(built, engine, case):
+    _border_case(built, engine, case)
 
 
 SIX = pytest.mark.parametrize("case", forms.SIX_FORMS, ids=[forms.case_id(c) for c in forms.SIX_FORMS])

@@ -14,8 +14,11 @@ from pulse_ref import LADDER, MIXED16
 pytestmark = pytest.mark.gpu
 
 FILL = np.float32(-12345.678)
-PLANS = {"w1": (1,), "w2": (2,), "w3": (3,), "w257": (257,), "w258": (258,), "w1023": (1023,), "w1024": (1024,), "ladder": LADDER,
-         "mixed16": MIXED16}
+FIRST_PLANS = {"w1": (1,), "w2": (2,), "w3": (3,), "w257": (257,), "w258": (258,), "w1023": (1023,), "w1024": (1024,), "ladder": LADDER,
+               "mixed16": MIXED16}
+# ... and the least width whose eight rows of a 1024-output tile pass 32 KiB: pulse_kernel<16384, 4>, the one instantiation
+# of the launch table that none of the tables above (nor any other test's) takes (tests/search_family_matrix.py)
+PLANS = dict(FIRST_PLANS, w151=(151,))
 NOUTS = ("1", "T-1", "T", "T+1", "2T+5")
 SEGS = ("64", "68", "T", "T+4", "2T+4", ">nout")
 WORST = {}
@@ -76,13 +79,15 @@ def _run(built, engine, x, widths, seg, nout, want_moments=True, name=None):
 def test_the_cases_cover_the_borders(built):
     """The shapes of test_every_plan_at_every_border: every tile size, every LDS size, tiles of one output and of
     tile_out, a last segment of one output, seg above nout, halos one and two past a multiple of 256"""
-    tiles, sizes = set(), set()
+    tiles, sizes, both = set(), set(), set()
     for name, widths in PLANS.items():
         rc, _, threads, lds, tile, kept, _ = built.pulse_geometry(widths, 64)
         assert rc == 0 and threads == 256 and (tile, lds, kept) == pulse_ref.plan(widths)[:3]
         tiles.add(tile)
         sizes.add(lds)
+        both.add((tile, lds))
     assert tiles == {1024, 512, 256} and sizes == {16384, 32768, 65536}
+    assert both == {(1024, 16384), (1024, 32768), (1024, 65536), (512, 65536), (256, 65536)}          # the five entries of pulse.hip's launch table
     assert (1024 + 257 - 1) % 256 == 0 and (1024 + 258 - 1) % 256 == 1            # level 0 of a full tile, in lanes
     t = 1024
     assert _size("T+1", t) % _size("T", t) == 1                                   # a last segment of one output

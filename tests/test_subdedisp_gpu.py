@@ -166,8 +166,7 @@ def test_the_helper_s_sweeps(sd, engine, which):
 
 # ---- every form of either stage, both sides of every border ---------------------------------------------------------
 
-@pytest.mark.parametrize("case", forms.STAGE1_CASES, ids=forms1.case_id)
-def test_every_border_of_stage_1(sd, engine, case):
+def _stage1_case(sd, engine, case):
     first, d1, d2 = forms.stage1_case_tables(case)
     got = sd.geometry(first, d1, d2, None, forms.NOUT)
     assert (got[0], got[5], got[3][0]) == (0, case.plan_per, forms1.form(case.plan_spread, case.plan_per)[1])
@@ -175,13 +174,22 @@ def test_every_border_of_stage_1(sd, engine, case):
     _check(sd, engine, rows, first, d1, d2, None, forms.NOUT, name=forms1.case_id(case))
 
 
-@pytest.mark.parametrize("case", forms.STAGE2_CASES, ids=forms.case2_id)
-def test_every_border_of_stage_2(sd, engine, case):
+def _stage2_case(sd, engine, case):
     first, d1, d2 = forms.stage2_case_tables(case)
     got = sd.geometry(first, d1, d2, None, forms.NOUT)
     assert (got[0], got[6], got[3][1]) == (0, case.plan_per, forms.form2(case.plan_spread, case.plan_per)[0])
     rows = _rows(ref.rows_needed(d1, d2, None, forms.NOUT), forms.NCHAN2, seed=case.spread + case.per)
     _check(sd, engine, rows, first, d1, d2, None, forms.NOUT, name=forms.case2_id(case))
+
+
+@pytest.mark.parametrize("case", forms.STAGE1_CASES, ids=forms1.case_id)
+def test_every_border_of_stage_1(sd, engine, case):
+    _stage1_case(sd, engine, case)
+
+
+@pytest.mark.parametrize("case", forms.STAGE2_CASES, ids=forms.case2_id)
+def test_every_border_of_stage_2(sd, engine, case):
+    _stage2_case(sd, engine, case)
 
 
 def _form_tables(stage, k):
