@@ -1,5 +1,5 @@
 // search_plan.h -- the host side the waterfall-and-series family shares (dedisp_shim.hip, pulse_shim.hip, fold_shim.hip,
-// ffa_shim.hip, cdd_shim.hip, cand_shim.hip, clean_shim.hip, subdedisp_shim.hip, sift_shim.hip): the head every opaque plan type derives
+// ffa_shim.hip, cdd_shim.hip, cand_shim.hip, clean_shim.hip, subdedisp_shim.hip, sift_shim.hip, cutout_shim.hip): the head every opaque plan type derives
 // from with its open, close and the head of a run; the rules more than one library states, each worded once and returning
 // its text or nullptr; the band's dispersion formula; the moments of a series.  A shim composes the rules in the order its
 // header documents.  Internal linkage, like shim_common.h: a library has one shim.
